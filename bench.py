@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: batched rANS float codec, encode + decode, on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bf16|u8|fp16|fp32]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bf16|u8|fp16|fp32] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps of the headline loop, checks the round trip and prints the result
+line.  Everything else it can measure (the one-buffer-set and steady-state loops, each direction alone, per-kernel
+profiles and the roofline, BASELINE configs 2 and 4, the CPU baseline) runs only under `--full`.
+`--dump-outputs DIR` writes what the last timed step computed to DIR/*.npy (see `dump_outputs`).
 
 `--gpus N` with N > 1 and no torchrun environment starts the N ranks itself
 (torch.distributed.run, one process per GPU, RCCL); under the driver's own
@@ -20,7 +25,7 @@ neither an input nor an archive nor an output line can still be in the 256 MiB
 memory-side cache when its turn comes: every byte the step moves comes from / goes to
 HBM.  A loop that re-codes ONE buffer set (what rounds 1-3 reported, and what the
 reference's own benchmark does) is 15-20 % faster because half its traffic is served
-by that cache; it is printed as a named extra (`ms_per_step_one_buffer_set*`), as are
+by that cache; `--full` prints it as a named extra (`ms_per_step_one_buffer_set*`), as are
 the steady-state figures after a pre-roll of >= 400 steps (`*_steady_state`: short
 regions right after an idle fence include the clock ramp).
 
@@ -34,7 +39,7 @@ no exchange step); timing is barrier + synchronize on both sides, MAX over
 ranks.  After the timed region the ranks all-gather their compressed sizes
 (RCCL) only to report the aggregate ratio.
 
-The JSON line also carries
+Under `--full` the JSON line also carries
   roofline     -- the dominant kernel OF THE HEADLINE LOOP: its algorithmic bytes /
                   its mean duration, durations measured with HIP events on the
                   launch stream in a second, instrumented pass of the same loop;
@@ -274,6 +279,35 @@ def compact_config_line(dg, kind, device, steps, warmup, rotate=4, batch=256, el
     del sets, codec, data
     torch.cuda.empty_cache()
     return out
+
+
+DUMP_SAMPLE = 1 << 22  # values per sampled output of --dump-outputs: 16 MiB as float32
+
+
+def dump_outputs(codec, out_dir):
+    """Writes what a caller of the timed path received from its last step (`codec` = the buffer set it coded) as
+    float32 / float64 .npy files under out_dir, about 32 MiB in all:
+      compressed_sizes, decompress_status, decompressed_sizes -- one value per element of the batch;
+      compressed_bytes_sample -- archive bytes at fixed seeded (element, fraction of that element's archive) positions;
+      decompressed_sample     -- decoded values at fixed seeded positions of the [batch, elems] output.
+    The positions depend only on the arguments, so two builds run with the same arguments compare value for value."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(0)
+    sizes = codec.sizes.cpu().numpy().astype(np.int64)
+    save = lambda name, a, dt: np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=dt))
+    save("compressed_sizes", sizes, np.float64)
+    save("decompress_status", codec.status.cpu().numpy(), np.float64)
+    save("decompressed_sizes", codec.osz.cpu().numpy(), np.float64)
+
+    rows = rng.integers(0, codec.B, DUMP_SAMPLE)
+    cols = np.floor(rng.random(DUMP_SAMPLE) * sizes[rows]).astype(np.int64)  # inside the element's archive
+    pos = torch.from_numpy(rows * codec.row_cap + cols).to(codec.comp.device)
+    save("compressed_bytes_sample", codec.comp.reshape(-1)[pos].cpu().numpy(), np.float32)
+
+    out = codec.out.reshape(-1)
+    pos = torch.from_numpy(np.sort(rng.integers(0, out.numel(), min(DUMP_SAMPLE, out.numel())))).to(out.device)
+    save("decompressed_sample", out[pos].float().cpu().numpy(), np.float32)
 
 
 def baseline_metric():
@@ -613,6 +647,65 @@ def bind_rank_to_gpu_numa_node(dev_index):
     return info
 
 
+def full_report(args, codec, cold, extras, prof_cold, prof_warm, comp_total, dir_alg):
+    """--full: the per-kernel tables of the headline and one-buffer-set loops, the roofline of the dominant kernel and
+    the figures by direction."""
+    def kernel_table(prof):
+        table = {}
+        for name, rec in prof.items():
+            avg_ms = rec["total_ms"] / max(rec["launches"], 1)
+            ab = algorithmic_bytes(name, codec, comp_total)
+            table[name] = {"avg_us": round(avg_ms * 1e3, 2), "launches": rec["launches"]}
+            if ab:
+                table[name]["algorithmic_GBps"] = round(ab / (avg_ms * 1e-3) / 1e9, 1)
+        return table
+
+    kernels = kernel_table(prof_cold)
+    kernels_warm = kernel_table(prof_warm)
+    hot = [k for k in kernels if "algorithmic_GBps" in kernels[k]]
+    dom = max(hot, key=lambda k: kernels[k]["avg_us"]) if hot else None
+    roofline = None
+    if dom:
+        ach = kernels[dom]["algorithmic_GBps"]
+        roofline = {
+            "bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": round(ach / HBM_PEAK_GBPS, 4),
+            "avg_us": kernels[dom]["avg_us"],
+            "algorithmic_bytes": algorithmic_bytes(dom, codec, comp_total),
+            "loop": "rotating buffer sets (cache-cold): the headline loop" if cold else "one buffer set (--rotate 1)",
+        }
+        # the PMC passes are taken on the default shape only, and count only for the build they were taken on
+        traffic, note = (measured_traffic(args.workload, dom) if (args.batch == 256 and args.elems == 512 * 1024)
+                         else (None, "PMC passes exist for the default shape only"))
+        roofline["traffic"] = traffic
+        roofline["traffic_source"] = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (tools/gpu_pmc.sh), "
+                                      "(2*FETCH_SIZE + WRITE_SIZE) KiB per launch; " + note)
+
+    def direction(table):
+        """compress = algorithmic bytes of the direction / (histogram + encode), decompress = ... / decode"""
+        hist = next((v["avg_us"] for k, v in table.items() if "histogram" in k or "stats" in k), 0.0)
+        enc = sum(v["avg_us"] for k, v in table.items() if k.startswith("k_ans_encode"))
+        dec = sum(v["avg_us"] for k, v in table.items() if k.startswith("k_ans_decode"))
+        frac = lambda us: round(dir_alg / (us * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4) if us else None
+        return {"compress": {"kernels_us": round(hist + enc, 2), "histogram_us": hist, "encode_us": enc, "frac": frac(hist + enc)},
+                "decompress": {"kernels_us": round(dec, 2), "frac": frac(dec)}}
+
+    call_frac = lambda key: (round(dir_alg / (extras[key] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if extras.get(key) else None)
+    by_direction = {
+        "algorithmic_bytes_per_direction": dir_alg, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+        "cold": direction(kernels) if cold else None,            # kernels of the rotating round trip
+        "warm_one_buffer_set": direction(kernels_warm),
+        # each direction running ALONE (wall clock of the library call, launch gaps included)
+        "cold_alone": {"compress": {"ms": extras.get("ms_compress_only"), "frac": call_frac("ms_compress_only")},
+                       "decompress": {"ms": extras.get("ms_decompress_only"), "frac": call_frac("ms_decompress_only")}} if cold else None,
+        "warm_alone": {"compress": {"ms": extras["ms_compress_only_one_buffer_set"], "frac": call_frac("ms_compress_only_one_buffer_set")},
+                       "decompress": {"ms": extras["ms_decompress_only_one_buffer_set"], "frac": call_frac("ms_decompress_only_one_buffer_set")}},
+        "dominant_kernel_cold": dom,
+    }
+    return {"roofline": roofline, "roofline_by_direction": by_direction, "kernels": kernels,
+            "kernels_one_buffer_set": kernels_warm if cold else None}
+
+
 def rccl_version():
     try:
         v = torch.cuda.nccl.version()
@@ -656,9 +749,18 @@ def main():
                     help="default line only: skip the compact lines of BASELINE configs 2 (u8) and 4 (fp16, probBits 11)")
     ap.add_argument("--timeline", action="store_true",
                     help="only the timed steps (no per-phase timing / kernel profile): for rocprofv3 timelines")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the one-buffer-set and steady-state loops, each direction alone, per-kernel "
+                         "profiles and the roofline, BASELINE configs 2 and 4 and the CPU baseline (a plain run: the "
+                         "headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/*.npy (float32 / float64, seeded samples of "
+                         "the archive bytes and decoded values)")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs and (args.collective or args.reference_protocol):
+        sys.exit("bench.py: --dump-outputs writes the outputs of the codec step; not with --collective / --reference-protocol")
 
     # DGPU_BENCH_ONE_DEVICE=1 (with --dist-backend gloo): every rank on GPU 0 -- lets the N > 1 code path
     # be exercised on a single-GPU box; never used for measurements
@@ -777,10 +879,22 @@ def main():
     for c2 in sets:
         c2.verify()
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sets[(W + K - 1) % rot_sets], args.dump_outputs)
+
     if args.timeline:
         if rank == 0:
             print(json.dumps({"ms_per_step": round(elapsed / K * 1e3, 4), "loop": "rotating" if cold else "one_buffer_set"}))
         return
+
+    sizes = codec.sizes.to(torch.int64)
+    comp_total = int(sizes.sum().item())
+    if distributed:
+        # the only collective: all-gather the per-element compressed sizes (RCCL over xGMI)
+        all_sizes = D.gather_sizes(codec.sizes, args.batch * world)
+        ratio = float(all_sizes.to(torch.int64).sum().item()) / (codec.in_bytes * world)
+    else:
+        ratio = comp_total / codec.in_bytes
 
     extras = {}
     ms = lambda seconds, steps=K: round(over_ranks(seconds) / steps * 1e3, 4)
@@ -791,8 +905,9 @@ def main():
     KS = max(K, 200)
     # ONE buffer set (rounds 1-3's headline, and the shape of the reference's own benchmark, which re-codes its
     # tensors): the ~180 MB archive and half of the input / output lines are served by the memory-side cache
-    extras["ms_per_step_one_buffer_set"] = ms(timed_loop(step_one, W, K))
-    if not args.quick:
+    if args.full:
+        extras["ms_per_step_one_buffer_set"] = ms(timed_loop(step_one, W, K))
+    if args.full and not args.quick:
         extras["ms_per_step_steady_state"] = ms(timed_loop(step_rot, preroll + W, KS), KS)
         extras["ms_per_step_one_buffer_set_steady_state"] = ms(timed_loop(step_one, preroll + W, KS), KS)
         # The rows of one tensor are a stride batch to the library (no parameter block on the device).  The same steps
@@ -806,101 +921,40 @@ def main():
         codec.verify()
         codec.scatter_pointers()
     # The two directions ALONE -- a sender that only compresses, a receiver that only decompresses
-    if cold:
+    if args.full and cold:
         extras["ms_compress_only"] = ms(timed_loop(lambda i: sets[i % rot_sets].encode(), W, K))
         extras["ms_decompress_only"] = ms(timed_loop(lambda i: sets[i % rot_sets].decode(), W, K))
-    if cold and not args.quick:
+    if args.full and cold and not args.quick:
         # ... and the round trip with the histogram pass reading through the cache (dgpu_set_histogram_load_policy(1)):
         # best for exactly this loop, not the default because it loses wherever only one direction runs (docs/HISTORY.md section 3)
         codec.lib.dgpu_set_histogram_load_policy(1)
         extras["ms_per_step_cached_histogram_loads"] = ms(timed_loop(step_rot, W, K))
         extras["ms_compress_only_cached_histogram_loads"] = ms(timed_loop(lambda i: sets[i % rot_sets].encode(), W, K))
         codec.lib.dgpu_set_histogram_load_policy(-1)
-    extras["ms_compress_only_one_buffer_set"] = ms(timed_loop(lambda i: codec.encode(), W, K))
-    extras["ms_decompress_only_one_buffer_set"] = ms(timed_loop(lambda i: codec.decode(), W, K))
+    if args.full:
+        extras["ms_compress_only_one_buffer_set"] = ms(timed_loop(lambda i: codec.encode(), W, K))
+        extras["ms_decompress_only_one_buffer_set"] = ms(timed_loop(lambda i: codec.decode(), W, K))
 
-    sizes = codec.sizes.to(torch.int64)
-    comp_total = int(sizes.sum().item())
-    if distributed:
-        # the only collective: all-gather the per-element compressed sizes (RCCL over xGMI)
-        all_sizes = D.gather_sizes(codec.sizes, args.batch * world)
-        ratio = float(all_sizes.to(torch.int64).sum().item()) / (codec.in_bytes * world)
-    else:
-        ratio = comp_total / codec.in_bytes
-
-    # per-kernel durations (HIP events around every launch) of the headline loop and of the one-buffer-set loop;
-    # at least 100 launches per kernel: stable averages for small K
-    P = max(K, 100)
-    for i in range(W):
-        step_rot(i)
-    prof_cold = kernel_profile(codec, P, step_rot)
-    for i in range(W):
-        step_one(i)
-    prof_warm = kernel_profile(codec, P, step_one) if cold else prof_cold
-    for c2 in sets:
-        c2.verify()
+        # per-kernel durations (HIP events around every launch) of the headline loop and of the one-buffer-set loop;
+        # at least 100 launches per kernel: stable averages for small K
+        P = max(K, 100)
+        for i in range(W):
+            step_rot(i)
+        prof_cold = kernel_profile(codec, P, step_rot)
+        for i in range(W):
+            step_one(i)
+        prof_warm = kernel_profile(codec, P, step_one) if cold else prof_cold
+        for c2 in sets:
+            c2.verify()
 
     if rank == 0:
         ms_per_step = elapsed / K * 1e3
         value = world * 2 * codec.in_bytes / (elapsed / K) / 1e9
-
-        def kernel_table(prof):
-            table = {}
-            for name, rec in prof.items():
-                avg_ms = rec["total_ms"] / max(rec["launches"], 1)
-                ab = algorithmic_bytes(name, codec, comp_total)
-                table[name] = {"avg_us": round(avg_ms * 1e3, 2), "launches": rec["launches"]}
-                if ab:
-                    table[name]["algorithmic_GBps"] = round(ab / (avg_ms * 1e-3) / 1e9, 1)
-            return table
-
-        kernels = kernel_table(prof_cold)
-        kernels_warm = kernel_table(prof_warm)
-        hot = [k for k in kernels if "algorithmic_GBps" in kernels[k]]
-        dom = max(hot, key=lambda k: kernels[k]["avg_us"]) if hot else None
-        roofline = None
-        if dom:
-            ach = kernels[dom]["algorithmic_GBps"]
-            roofline = {
-                "bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(ach / HBM_PEAK_GBPS, 4),
-                "avg_us": kernels[dom]["avg_us"],
-                "algorithmic_bytes": algorithmic_bytes(dom, codec, comp_total),
-                "loop": "rotating buffer sets (cache-cold): the headline loop" if cold else "one buffer set (--rotate 1)",
-            }
-            # the PMC passes are taken on the default shape only, and count only for the build they were taken on
-            traffic, note = (measured_traffic(args.workload, dom) if (args.batch == 256 and args.elems == 512 * 1024)
-                             else (None, "PMC passes exist for the default shape only"))
-            roofline["traffic"] = traffic
-            roofline["traffic_source"] = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (tools/gpu_pmc.sh), "
-                                          "(2*FETCH_SIZE + WRITE_SIZE) KiB per launch; " + note)
         # whole-step figure: algorithmic bytes of encode + decode over the step time
         E = codec.B * codec.elems
         wb = (2 if ft in (1, 2) else 4) if ft else 1
         dir_alg = E * wb + comp_total  # one direction: every input byte read once, every output byte written once
         step_alg = 2 * dir_alg
-
-        def direction(table):
-            """compress = algorithmic bytes of the direction / (histogram + encode), decompress = ... / decode"""
-            hist = next((v["avg_us"] for k, v in table.items() if "histogram" in k or "stats" in k), 0.0)
-            enc = sum(v["avg_us"] for k, v in table.items() if k.startswith("k_ans_encode"))
-            dec = sum(v["avg_us"] for k, v in table.items() if k.startswith("k_ans_decode"))
-            frac = lambda us: round(dir_alg / (us * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4) if us else None
-            return {"compress": {"kernels_us": round(hist + enc, 2), "histogram_us": hist, "encode_us": enc, "frac": frac(hist + enc)},
-                    "decompress": {"kernels_us": round(dec, 2), "frac": frac(dec)}}
-
-        call_frac = lambda key: (round(dir_alg / (extras[key] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if extras.get(key) else None)
-        by_direction = {
-            "algorithmic_bytes_per_direction": dir_alg, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-            "cold": direction(kernels) if cold else None,            # kernels of the rotating round trip
-            "warm_one_buffer_set": direction(kernels_warm),
-            # each direction running ALONE (wall clock of the library call, launch gaps included)
-            "cold_alone": {"compress": {"ms": extras.get("ms_compress_only"), "frac": call_frac("ms_compress_only")},
-                           "decompress": {"ms": extras.get("ms_decompress_only"), "frac": call_frac("ms_decompress_only")}} if cold else None,
-            "warm_alone": {"compress": {"ms": extras["ms_compress_only_one_buffer_set"], "frac": call_frac("ms_compress_only_one_buffer_set")},
-                           "decompress": {"ms": extras["ms_decompress_only_one_buffer_set"], "frac": call_frac("ms_decompress_only_one_buffer_set")}},
-            "dominant_kernel_cold": dom,
-        }
         out = {
             "metric": "rans_encode_decode_GBps",
             "baseline_metric": baseline_metric(),
@@ -923,7 +977,6 @@ def main():
             "step_algorithmic_GBps": round(step_alg / (elapsed / K) / 1e9, 1),
             "step_frac_of_hbm_peak": round(step_alg / (elapsed / K) / 1e9 / HBM_PEAK_GBPS, 4),
             **extras,
-            "steady_state_preroll_steps": preroll,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -934,27 +987,26 @@ def main():
                               "C ABI: dgpu_ans_encode_batch_pointer + dgpu_ans_decode_batch_pointer",
                        "sharding": f"{world} ranks x {args.batch} independent tensors, no data-path collective"},
             "compression_ratio": round(ratio, 4),
-            "roofline": roofline,
-            "roofline_by_direction": by_direction,
-            "kernels": kernels,
-            "kernels_one_buffer_set": kernels_warm if cold else None,
             "round_trip_bit_exact": None if ablation_run() else True,
             **({"ablation": "DGPU_BENCH_ABLATION=1: the round trip was NOT checked; not a measurement"} if ablation_run() else {}),
         }
-        default_line = (world == 1 and args.workload == "bf16" and args.batch == 256 and args.elems == 512 * 1024
-                        and not args.prob_bits and not args.quick)
-        if default_line and not args.no_other_configs:
-            # The other single-GPU BASELINE configurations on the same protocol (cache-cold loop, bit-exact check), so
-            # that the one command the driver runs carries driver-run evidence for every one of them.
-            del sets[1:]
-            torch.cuda.empty_cache()
-            KO, WO = max(K, 50), max(W, 5)
-            out["other_configs"] = {
-                "config2_u8": compact_config_line(dg, "u8", device, KO, WO, rot_sets),
-                "config4_fp16_p11": compact_config_line(dg, "fp16", device, KO, WO, rot_sets),
-            }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(args.workload, prob_bits)
+        if args.full:
+            out["steady_state_preroll_steps"] = preroll
+            out.update(full_report(args, codec, cold, extras, prof_cold, prof_warm, comp_total, dir_alg))
+            default_line = (world == 1 and args.workload == "bf16" and args.batch == 256 and args.elems == 512 * 1024
+                            and not args.prob_bits and not args.quick)
+            if default_line and not args.no_other_configs:
+                # The other single-GPU BASELINE configurations on the same protocol (cache-cold loop, bit-exact check), so
+                # that one `--full` run carries evidence for every one of them.
+                del sets[1:]
+                torch.cuda.empty_cache()
+                KO, WO = max(K, 50), max(W, 5)
+                out["other_configs"] = {
+                    "config2_u8": compact_config_line(dg, "u8", device, KO, WO, rot_sets),
+                    "config4_fp16_p11": compact_config_line(dg, "fp16", device, KO, WO, rot_sets),
+                }
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(args.workload, prob_bits)
         print(json.dumps(out), flush=True)
 
     if distributed:

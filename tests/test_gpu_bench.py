@@ -10,7 +10,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
-SMALL = ["--steps", "6", "--warmup", "2", "--batch", "64", "--no-cpu-baseline", "--rotate", "2"]
+SMALL = ["--steps", "6", "--warmup", "2", "--batch", "64", "--no-cpu-baseline", "--rotate", "2", "--full"]
 
 
 def _clean_env(**extra):
@@ -45,7 +45,7 @@ def _check_contract(d, n_gpus):
 
 
 def test_default_style_line_and_cpu_baseline():
-    p = subprocess.run([sys.executable, BENCH, "--steps", "6", "--warmup", "2", "--batch", "64", "--rotate", "2"],
+    p = subprocess.run([sys.executable, BENCH, "--steps", "6", "--warmup", "2", "--batch", "64", "--rotate", "2", "--full"],
                        capture_output=True, text=True, timeout=900, env=_clean_env())
     d = _line(p)
     _check_contract(d, 1)
@@ -55,6 +55,34 @@ def test_default_style_line_and_cpu_baseline():
     # got (cpu_seconds_per_wall_second: other processes of this test session -- pytest-xdist workers -- share the quota)
     got = min(c["cores"], max(1.0, c["host"]["cpu_seconds_per_wall_second"]))
     assert c["cores"] <= c["host"]["visible_cpus"] and c["value"] > 0.5 * got * c["single_thread"]["value"], c
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    # a plain run (no --full): the headline only, and --dump-outputs writes the same float32 / float64 arrays every time
+    import numpy as np
+
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, BENCH, "--steps", "5", "--warmup", "2", "--batch", "64", "--rotate", "2",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, env=_clean_env())
+        lines.append(_line(p))
+        dumps.append({f.name: np.load(f) for f in sorted((tmp_path / run).iterdir())})
+    d = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["round_trip_bit_exact"] and d["rotating_sets"] == 2
+    assert abs(d["value"] - 2 * d["config"]["per_gpu_batch_bytes"] / (d["ms_per_step"] * 1e-3) / 1e9) < 0.01 * d["value"]
+    for key in ("roofline", "kernels", "ms_per_step_one_buffer_set", "cpu_baseline", "other_configs"):
+        assert key not in d, key
+    a, b = dumps
+    assert set(a) == set(b) == {"compressed_sizes.npy", "compressed_bytes_sample.npy", "decompress_status.npy",
+                                "decompressed_sizes.npy", "decompressed_sample.npy"}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and np.array_equal(a[name], b[name]), name
+    assert a["compressed_sizes.npy"].shape == (64,) and (a["decompress_status.npy"] == 1).all()
+    assert (a["decompressed_sizes.npy"] == 512 * 1024).all()
+    assert abs(a["compressed_sizes.npy"].sum() / d["config"]["per_gpu_batch_bytes"] - d["compression_ratio"]) < 1e-3
 
 
 def _free_port():
@@ -100,7 +128,7 @@ def test_eight_ranks_on_one_device():
     torch_free0 = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.mem_get_info(0)[0])"], capture_output=True,
                                  text=True, timeout=300)
     p = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--dist-backend", "gloo", "--steps", "4", "--warmup", "1", "--batch", "32",
-                        "--no-cpu-baseline", "--rotate", "2", "--quick"], capture_output=True, text=True, timeout=1200,
+                        "--no-cpu-baseline", "--rotate", "2", "--quick", "--full"], capture_output=True, text=True, timeout=1200,
                        env=_clean_env(DGPU_BENCH_ONE_DEVICE="1"))
     d = _line(p)
     _check_contract(d, 8)

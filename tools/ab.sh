@@ -11,7 +11,7 @@ for v in "$@"; do
   name=${v%%@*}; envs=""
   [ "$v" != "$name" ] && envs=$(echo "${v#*@}" | tr '@' ' ')
   lib=""; [ "$name" != "base" ] && lib=$PWD/dietgpu_amd/lib/$name
-  env DGPU_LIB=$lib $envs python bench.py --quick --steps ${AB_STEPS:-100} --warmup 10 --no-cpu-baseline --workload $WL $AB_ARGS > /tmp/o.json 2>/tmp/e.txt || tail -3 /tmp/e.txt
+  env DGPU_LIB=$lib $envs python bench.py --full --quick --steps ${AB_STEPS:-100} --warmup 10 --no-cpu-baseline --workload $WL $AB_ARGS > /tmp/o.json 2>/tmp/e.txt || tail -3 /tmp/e.txt
   python -c "
 import json; d=json.load(open('/tmp/o.json'))
 k=lambda t: {n[2:]: v['avg_us'] for n,v in (t or {}).items()}
