@@ -20,10 +20,7 @@
 #include <vector>
 
 #include "format.h"
-#include "kernels_decode.h"
-#include "kernels_encode.h"
-#include "kernels_pairs.h"
-#include "kernels_stats.h"
+#include "kernel_variants.h"
 
 using namespace dgpu;
 
@@ -109,6 +106,14 @@ class KernelTimer {
     KernelTimer kt_(name, stream);       \
     hipLaunchKernelGGL(__VA_ARGS__);     \
   } while (0)
+
+// One launch of a kernel variant (kernel_variants.h) on `stream`.
+template <typename... Args, typename... Given>
+int launchVariant(const KernelVariant<Args...>& v, dim3 grid, hipStream_t stream, const Given&... args) {
+  DGPU_LAUNCH(v.name, stream, v.fn, grid, dim3(v.threads), v.ldsBytes, stream, args...);
+  DGPU_HIP(hipGetLastError());
+  return DGPU_OK;
+}
 
 // ---------------------------------------------------------------------------
 // Library-owned device state per (device, stream): everything a call needs that
@@ -820,154 +825,17 @@ uint32_t numComputeUnits() {
   return n;
 }
 
-// The encoder runs as persistent workgroups: as many as fit on the chip at once
-// (or fewer, if there are fewer tiles).  Float inputs use the small-stage /
-// spilling variant (6 workgroups per CU), raw bytes the worst-case stage (3 per CU; kernels_encode.h).
-constexpr bool encodeSpills(uint32_t ft) { return ft != 0; }
-
-// (`resident` also sizes the spill-slot pool of the hardware-dispatched float encoders, whose wavefronts hold a pair
-// of slots across their look-back wait: the pool must cover whichever form of the kernel is launched, so where both
-// forms exist the larger occupancy of the two counts -- today they compile to the same register count.)
-template <int P, uint32_t FT, uint32_t TB>
-uint32_t encodeGridPFT(uint32_t tickets) {
-  static const uint32_t perCu = [] {
-    int n = 0, m = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &n, (k_ans_encode<P, FT, encodeSpills(FT), TB, true>), encThreads(TB), encLdsBytes(P, encodeSpills(FT), FT, TB)) != hipSuccess || n < 1) {
-      n = 1;
-    }
-    if constexpr (!(encodeSpills(FT) && TB >= kBlocksPerTile)) {  // (8-block float tiles exist in the persistent form only)
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-              &m, (k_ans_encode<P, FT, encodeSpills(FT), TB, false>), encThreads(TB), encLdsBytes(P, encodeSpills(FT), FT, TB)) != hipSuccess) {
-        m = 0;
-      }
-    }
-    return (uint32_t)std::max(n, m);
-  }();
-  return std::max(1u, std::min(tickets, perCu * numComputeUnits()));
-}
-// ... the persistent 8-block bf16 / fp32 encoder with the wide stage (kernels_encode.h, kSpillStageWordsWide)
-template <int P, uint32_t FT>
-uint32_t encodeGridWidePF(uint32_t tickets) {
-  if constexpr (FT == kBFloat16 || FT == kFloat32) {
-    static const uint32_t perCu = [] {
-      int n = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (k_ans_encode<P, FT, true, kBlocksPerTile, true, true>), encThreads(kBlocksPerTile),
-                                                       encLdsBytes(P, true, FT, kBlocksPerTile, true)) != hipSuccess || n < 1) {
-        n = 1;
-      }
-      return (uint32_t)n;
-    }();
-    return std::max(1u, std::min(tickets, perCu * numComputeUnits()));
-  } else {
-    return encodeGridPFT<P, FT, kBlocksPerTile>(tickets);
-  }
-}
-// Batches of single-block elements: two ELEMENTS per wavefront (kernels_pairs.h) instead of one with an idle half.
-template <int P, uint32_t FT>
-uint32_t encodePairGridPF(uint32_t elements) {
-  static const uint32_t perCu = [] {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (k_ans_encode_pair<P, FT, encodeSpills(FT)>), 64,
-                                                     encPairLdsBytes(P, encodeSpills(FT), FT)) != hipSuccess || n < 1) {
-      n = 1;
-    }
-    return (uint32_t)n;
-  }();
-  // (workgroups = wavefronts that can be resident at once: the size of the spill-slot pool; the LAUNCH is one
-  // workgroup per pair, encodeCommon)
-  return std::max(1u, std::min((elements + 1u) / 2u, perCu * numComputeUnits()));
-}
-template <int P, uint32_t FT>
-uint32_t encodeGridPF(uint32_t tickets, uint32_t tileBlocks, bool wide) {
-  if (tileBlocks == kBlocksPerSingleTile) return encodePairGridPF<P, FT>(tickets);  // (one ticket per element)
-  if (wide && tileBlocks == kBlocksPerTile) return encodeGridWidePF<P, FT>(tickets);
-  return tileBlocks == kBlocksPerTinyTile ? encodeGridPFT<P, FT, kBlocksPerTinyTile>(tickets)
-      : tileBlocks == kBlocksPerSmallTile ? encodeGridPFT<P, FT, kBlocksPerSmallTile>(tickets)
-                                          : encodeGridPFT<P, FT, kBlocksPerTile>(tickets);
+// The workgroups of `v` that are on the chip at once when `workgroups` of them are launched: the grid of a persistent
+// launch, and the wavefronts that can hold spill slots at a time.
+template <typename... Args>
+uint32_t residentWorkgroups(const KernelVariant<Args...>& v, uint32_t workgroups) {
+  return std::max(1u, std::min(workgroups, workgroupsPerCu(v) * numComputeUnits()));
 }
 
-template <int P, uint32_t FT, bool kPersistent>
-int launchEncodePFD(const EncodeArgs& a, uint32_t tileBlocks, uint32_t grid, bool wide, hipStream_t stream) {
-  constexpr bool kSpill = encodeSpills(FT);
-  if constexpr (FT == kBFloat16 || FT == kFloat32) {
-    if (wide && tileBlocks == kBlocksPerTile) {
-      DGPU_LAUNCH("k_ans_encode", stream, (k_ans_encode<P, FT, true, kBlocksPerTile, true, true>), dim3(grid), dim3(kBlocksPerTile * 32),
-                  encLdsBytes(P, true, FT, kBlocksPerTile, true), stream, a);
-      DGPU_HIP(hipGetLastError());
-      return DGPU_OK;
-    }
-  }
-  if (tileBlocks == kBlocksPerTinyTile) {
-    DGPU_LAUNCH("k_ans_encode", stream, (k_ans_encode<P, FT, kSpill, kBlocksPerTinyTile, kPersistent>), dim3(grid), dim3(kBlocksPerTinyTile * 32),
-                encLdsBytes(P, kSpill, FT, kBlocksPerTinyTile), stream, a);
-  } else if (tileBlocks == kBlocksPerSmallTile) {
-    DGPU_LAUNCH("k_ans_encode", stream, (k_ans_encode<P, FT, kSpill, kBlocksPerSmallTile, kPersistent>), dim3(grid), dim3(kBlocksPerSmallTile * 32),
-                encLdsBytes(P, kSpill, FT, kBlocksPerSmallTile), stream, a);
-  } else {
-    // (8-block float tiles exist in the persistent form only: encoderHardwareDispatch never asks for the other)
-    constexpr bool kPers = kPersistent || kSpill;
-    DGPU_LAUNCH("k_ans_encode", stream, (k_ans_encode<P, FT, kSpill, kBlocksPerTile, kPers>), dim3(grid), dim3(kBlocksPerTile * 32),
-                encLdsBytes(P, kSpill, FT, kBlocksPerTile), stream, a);
-  }
-  DGPU_HIP(hipGetLastError());
-  return DGPU_OK;
-}
-// `hwDispatch`: grid == a.numTickets, one workgroup per tile (k_ans_encode<..., kPersistent = false>)
-template <int P, uint32_t FT>
-int launchEncodePF(const EncodeArgs& a, uint32_t tileBlocks, uint32_t grid, bool hwDispatch, bool wide, hipStream_t stream) {
-  constexpr bool kSpill = encodeSpills(FT);
-  if (tileBlocks == kBlocksPerSingleTile) {
-    DGPU_LAUNCH("k_ans_encode_pair", stream, (k_ans_encode_pair<P, FT, kSpill>), dim3(grid), dim3(64), encPairLdsBytes(P, kSpill, FT), stream, a);
-    DGPU_HIP(hipGetLastError());
-    return DGPU_OK;
-  }
-  if (hwDispatch) return launchEncodePFD<P, FT, false>(a, tileBlocks, grid, wide, stream);
-  return launchEncodePFD<P, FT, true>(a, tileBlocks, grid, wide, stream);
-}
-
-#define DGPU_ENCODE_DISPATCH(P_, FT_, EXPR)                                   \
-  switch (FT_) {                                                              \
-    case 0:                                                                   \
-      switch (P_) { case 9: { constexpr int kP = 9; constexpr uint32_t kFT = 0; EXPR; } break;          \
-                    case 10: { constexpr int kP = 10; constexpr uint32_t kFT = 0; EXPR; } break;        \
-                    default: { constexpr int kP = 11; constexpr uint32_t kFT = 0; EXPR; } break; }      \
-      break;                                                                  \
-    case kFloat16:                                                            \
-      switch (P_) { case 9: { constexpr int kP = 9; constexpr uint32_t kFT = kFloat16; EXPR; } break;   \
-                    case 10: { constexpr int kP = 10; constexpr uint32_t kFT = kFloat16; EXPR; } break; \
-                    default: { constexpr int kP = 11; constexpr uint32_t kFT = kFloat16; EXPR; } break; } \
-      break;                                                                  \
-    case kBFloat16:                                                           \
-      switch (P_) { case 9: { constexpr int kP = 9; constexpr uint32_t kFT = kBFloat16; EXPR; } break;  \
-                    case 10: { constexpr int kP = 10; constexpr uint32_t kFT = kBFloat16; EXPR; } break; \
-                    default: { constexpr int kP = 11; constexpr uint32_t kFT = kBFloat16; EXPR; } break; } \
-      break;                                                                  \
-    default:                                                                  \
-      switch (P_) { case 9: { constexpr int kP = 9; constexpr uint32_t kFT = kFloat32; EXPR; } break;   \
-                    case 10: { constexpr int kP = 10; constexpr uint32_t kFT = kFloat32; EXPR; } break; \
-                    default: { constexpr int kP = 11; constexpr uint32_t kFT = kFloat32; EXPR; } break; } \
-      break;                                                                  \
-  }
-
-uint32_t encodeGrid(int P, uint32_t ft, uint32_t tileBlocks, uint32_t tickets, bool wide) {
-  uint32_t g = 1;
-  DGPU_ENCODE_DISPATCH(P, ft, g = (encodeGridPF<kP, kFT>(tickets, tileBlocks, wide)));
-  return g;
-}
 // The wide stage (five workgroups per CU, no flushes on N(0,1) exponents) for persistent 8-block bf16 / fp32 tiles of
 // batches whose elements have few tiles; elements of many tiles keep six workgroups per CU in flight behind their
 // in-order commit (kernels_encode.h, kSpillStageWordsWide; profiles/r06_ab_encoder_five_per_cu_*.txt).
 constexpr uint32_t kWideStageMaxTiles = 32;
-bool encoderWideStage(uint32_t floatType, uint32_t tileBlocks, uint32_t maxTiles) {
-  return (floatType == kBFloat16 || floatType == kFloat32) && tileBlocks == kBlocksPerTile && maxTiles <= kWideStageMaxTiles;
-}
-
-int launchEncode(int P, uint32_t ft, const EncodeArgs& a, uint32_t tileBlocks, uint32_t grid, bool hwDispatch, bool wide, hipStream_t stream) {
-  int rc = DGPU_OK;
-  DGPU_ENCODE_DISPATCH(P, ft, rc = (launchEncodePF<kP, kFT>(a, tileBlocks, grid, hwDispatch, wide, stream)));
-  return rc;
-}
 
 // blocks per encoder tile for a batch whose largest element has `maxSize` symbols
 uint32_t encTileBlocksFor(uint32_t maxSize) {
@@ -995,8 +863,7 @@ std::atomic<int> g_encDispatch{[] {
   const char* e = getenv("DGPU_ENC_DISPATCH");
   return e && *e ? atoi(e) : -1;
 }()};
-bool encoderHardwareDispatch(uint32_t numTickets, uint32_t resident, uint32_t floatType, uint32_t tileBlocks) {
-  if (encodeSpills(floatType) && tileBlocks >= kBlocksPerTile) return false;  // (no hardware-dispatched build of those)
+bool encoderHardwareDispatch(uint32_t numTickets, uint32_t resident) {
   const int m = g_encDispatch.load();
   if (m >= 0) return m != 0;
   return numTickets > resident;  // more tiles than slots: let the hardware balance them
@@ -1445,21 +1312,33 @@ int encodeCommon(
     groupWords = gw;
   }
 
-  // The encoder's grid.  `resident` = the workgroups of the kernel that fit on the chip at once.  8-block float tiles
-  // run as `resident` persistent workgroups that walk the tickets with a static map; raw bytes and float tiles of 2 / 4
-  // blocks run one workgroup per tile when there are more tiles than that, dispatched by the hardware in ticket order
-  // (encoderHardwareDispatch); k_ans_encode_pair always runs one workgroup per pair.  Spill slots (float inputs):
-  // [resident][slots per workgroup] -- a persistent workgroup's own, or a pool handed out through spillFlags.
+  // The encoder's variant and grid.  8-block float tiles run as persistent workgroups, as many as fit on the chip at
+  // once, that walk the tickets with a static map; raw bytes and float tiles of 2 / 4 blocks run one workgroup per tile
+  // when there are more tiles than that, dispatched by the hardware in ticket order (encoderHardwareDispatch);
+  // k_ans_encode_pair always runs one workgroup per pair.  `resident` = the workgroups of the kernel that fit on the
+  // chip at once.  Spill slots (float inputs): [resident][slots per workgroup] -- a persistent workgroup's
+  // own, or a pool handed out through spillFlags.
+  const bool pairs = tileBlocks == kBlocksPerSingleTile;
   const uint32_t numTickets = lists ? numListedTiles : (elemMap ? numElems : B * maxTiles);
-  const bool wideStage = encoderWideStage(floatType, tileBlocks, maxTiles);
-  const uint32_t resident = maxTiles > 0 ? encodeGrid(P, floatType, tileBlocks, numTickets, wideStage) : 0u;
-  const bool hwDispatch = tileBlocks != kBlocksPerSingleTile && encoderHardwareDispatch(numTickets, resident, floatType, tileBlocks);
+  const uint32_t numWorkgroups = pairs ? (numTickets + 1u) / 2u : numTickets;  // (one per pair of elements / per tile)
+  const bool wideStage = maxTiles <= kWideStageMaxTiles;
+  const EncodeVariant persistent = encoderVariant(P, floatType, tileBlocks, false, wideStage);
+  const EncodeVariant hardware = encoderVariant(P, floatType, tileBlocks, true, wideStage);
+  const bool bothForms = hardware.fn != persistent.fn;
+  // The persistent grid is the persistent variant's own occupancy.  The spill pool must cover whichever form is
+  // launched and the policy is decided before the form is: where both forms exist the larger occupancy counts there
+  // (on gfx950 both allocate the same registers and LDS).
+  const uint32_t residentPersistent = maxTiles > 0 ? residentWorkgroups(persistent, numWorkgroups) : 0u;
+  const uint32_t resident =
+      (bothForms && maxTiles > 0) ? std::max(residentPersistent, residentWorkgroups(hardware, numWorkgroups)) : residentPersistent;
+  const bool hwDispatch = bothForms && encoderHardwareDispatch(numTickets, resident);
+  const EncodeVariant& enc = hwDispatch ? hardware : persistent;
   uint16_t* spill = nullptr;
   uint32_t* spillFlags = nullptr;
   uint32_t spillPairs = 0;
   if (maxTiles > 0 && encodeSpills(floatType)) {
     // (single-block batches: two slots per workgroup, one per element of its pair)
-    const uint32_t slotsPerWg = tileBlocks == kBlocksPerSingleTile ? 2u : tileBlocks;
+    const uint32_t slotsPerWg = pairs ? 2u : tileBlocks;
     // (the size classes of one call run one after the other on the stream: they share the region of the first one
     // that is large enough)
     const size_t spillWords = (size_t)resident * slotsPerWg * encSpillSlotWords(P);
@@ -1470,7 +1349,7 @@ int encodeCommon(
       spill = sp;
       if (shared) shared->spill = sp, shared->spillWords = spillWords;
     }
-    if (tileBlocks == kBlocksPerSingleTile || hwDispatch) {
+    if (pairs || hwDispatch) {
       // one workgroup per pair / tile: the slots are a POOL with a pair for every wavefront that can be resident,
       // handed out through library-owned flags that are zero at rest
       uint32_t *arrive = nullptr, *acc = nullptr;
@@ -1511,20 +1390,9 @@ int encodeCommon(
     // histograms, no arrival counters.  (Measured on 32768 elements, profiles/r04_ab_single_block_elements.txt:
     // bf16 75.5 -> 65.5 us, fp16 80.5 -> 73.7; float32 -- 16 bytes of input per symbol and lane -- 69 -> 75.5, so
     // float32 keeps the workgroup per element.)
-    const dim3 grid(divUp(numElems, kSingleStatWaves)), block(64u * kSingleStatWaves);
-#define DGPU_STATS_SINGLE(FT)                                                                                           \
-    if (histogramLoadsNonTemporal(floatType)) {                                                                         \
-      DGPU_LAUNCH("k_stats_single", stream, (k_stats_single<FT, true>), grid, block, 0, stream, in, n, elemMap, numElems); \
-    } else {                                                                                                            \
-      DGPU_LAUNCH("k_stats_single", stream, (k_stats_single<FT, false>), grid, block, 0, stream, in, n, elemMap, numElems); \
-    }
-    switch (floatType) {
-      case 0: DGPU_STATS_SINGLE(0u) break;
-      case kFloat16: DGPU_STATS_SINGLE(kFloat16) break;
-      default: DGPU_STATS_SINGLE(kBFloat16) break;
-    }
-#undef DGPU_STATS_SINGLE
-    DGPU_HIP(hipGetLastError());
+    int rc = launchVariant(statsSingleVariant(floatType, histogramLoadsNonTemporal(floatType)), dim3(divUp(numElems, kSingleStatWaves)), stream,
+                           in, n, elemMap, numElems);
+    if (rc) return rc;
   } else if (!hist_dev) {
     const bool histList = lists && numListedHistParts != 0;
     const bool accumulate = !histList && histAccumulates(B, maxSize * wordBytes, floatType == 0);
@@ -1548,43 +1416,15 @@ int encodeCommon(
     fuse.norm = n;
     // bins with 32 lane slots unless a workgroup sees too little data to pay for zeroing / folding them
     const bool smallBins = histList ? listedHistPartBytes <= 64u * 1024u : (uint64_t)maxSize * wordBytes / grid.x <= 64u * 1024u;
-#define DGPU_HIST_LAUNCH_NT(S, NT)                                                                                \
-    switch (floatType) {                                                                                          \
-      case 0:                                                                                                     \
-        DGPU_LAUNCH("k_histogram", stream, (k_histogram<S, NT>), grid, dim3(256), 0, stream, in, histTemp, 1u, fuse); \
-        break;                                                                                                    \
-      case kFloat16:                                                                                              \
-        DGPU_LAUNCH("k_float_histogram", stream, (k_float_histogram<kFloat16, S, NT>), grid, dim3(256), 0, stream, in, histTemp, 1u, fuse); \
-        break;                                                                                                    \
-      case kBFloat16:                                                                                             \
-        DGPU_LAUNCH("k_float_histogram", stream, (k_float_histogram<kBFloat16, S, NT>), grid, dim3(256), 0, stream, in, histTemp, 1u, fuse); \
-        break;                                                                                                    \
-      default:                                                                                                    \
-        DGPU_LAUNCH("k_float_histogram", stream, (k_float_histogram<kFloat32, S, NT>), grid, dim3(256), 0, stream, in, histTemp, 1u, fuse); \
-        break;                                                                                                    \
-    }
-#define DGPU_HIST_LAUNCH(S)                 \
-    if (histogramLoadsNonTemporal(floatType)) { \
-      DGPU_HIST_LAUNCH_NT(S, true)          \
-    } else {                                \
-      DGPU_HIST_LAUNCH_NT(S, false)         \
-    }
-    if (smallBins) {
-      DGPU_HIST_LAUNCH(kHistSlotsSmall)
-    } else {
-      DGPU_HIST_LAUNCH(kHistSlotsLarge)
-    }
-#undef DGPU_HIST_LAUNCH
-#undef DGPU_HIST_LAUNCH_NT
-    DGPU_HIP(hipGetLastError());
+    rc = launchVariant(histogramVariant(floatType, smallBins, histogramLoadsNonTemporal(floatType)), grid, stream, in, histTemp, 1u, fuse);
+    if (rc) return rc;
   } else {
     // caller-supplied histogram: stand-alone normalisation
     DGPU_LAUNCH("k_normalize", stream, k_normalize, dim3(B), dim3(256), 0, stream, n);
     DGPU_HIP(hipGetLastError());
   }
   if (maxTiles > 0) {
-    // (k_ans_encode_pair: one workgroup per pair of elements; numTickets counts elements there)
-    const uint32_t grid = tileBlocks == kBlocksPerSingleTile ? (numTickets + 1u) / 2u : (hwDispatch ? numTickets : resident);
+    const uint32_t grid = (pairs || hwDispatch) ? numWorkgroups : residentPersistent;
     EncodeArgs e;
     e.in = in;
     e.out = archives;
@@ -1610,23 +1450,18 @@ int encodeCommon(
     e.outCapacity = outCapacity;
     e.useChecksum = (useChecksum && floatType) ? 1 : 0;
     e.checksum = (useChecksum && floatType) ? checksumTemp : nullptr;
-    int rc = launchEncode(P, floatType, e, tileBlocks, grid, hwDispatch, wideStage, stream);
+    int rc = launchVariant(enc, dim3(grid), stream, e);
     if (rc) return rc;
   }
   return DGPU_OK;
 }
 
-int ansEncodeImpl(
-    void* temp_dev, size_t tempBytes, size_t* tempUsed, int P, int useChecksum, uint32_t B,
-    const HostParams* hp /*null => stride views below*/, const BatchView* strideIn,
-    const BatchView* strideOut, uint32_t maxSize, const uint32_t* histogram_dev,
-    uint32_t* outSize_dev, hipStream_t stream) {
-  DGPU_REQUIRE(validProbBits(P), "probBits must be 9, 10 or 11");
-  DGPU_REQUIRE(B <= 65535u, "numInBatch must be <= 65535");
-  DGPU_REQUIRE(encodableSize(maxSize), "input larger than 1717538816 bytes: its maximum compressed size exceeds INT32_MAX (GpuANSEncode.cu:22)");
-  if (tempUsed) *tempUsed = 0;
-  if (B == 0) return DGPU_OK;
-
+// Shared tail of the encode entry points (ft: 0 for raw bytes): the batch as stride views or uploaded pointers, with
+// the work lists of its size classes or of a ragged batch, then encodeCommon once per class or once for the batch.
+int encodeBatch(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, uint32_t B,
+    const HostParams* hp /*null => stride views below*/, const BatchView* strideIn, const BatchView* strideOut,
+    uint32_t maxSize, const uint32_t* histogram_dev /*may be null*/, uint32_t* outSize_dev, hipStream_t stream) {
   StreamLease streamLease(stream);
   TempArena arena(temp_dev, tempBytes, streamLease);
   ParamLease lease;
@@ -1641,8 +1476,8 @@ int ansEncodeImpl(
     const uint32_t* sz = nullptr;
     HostParams listed;
     const HostParams* up = hp;
-    if ((histogram_dev == nullptr && planEncodeClassesCached(hp->sizes, 0u, &classes, &listed.work)) ||
-        planEncode(hp->sizes, 0u, maxSize, histogram_dev == nullptr, &plan, &listed.work)) {
+    if ((histogram_dev == nullptr && planEncodeClassesCached(hp->sizes, ft, &classes, &listed.work)) ||
+        planEncode(hp->sizes, ft, maxSize, histogram_dev == nullptr, &plan, &listed.work)) {
       listed.inPtrs = hp->inPtrs, listed.outPtrs = hp->outPtrs, listed.sizes = hp->sizes;
       up = &listed;
     }
@@ -1654,21 +1489,35 @@ int ansEncodeImpl(
     in = *strideIn;
     out = *strideOut;
   }
-  if (!classes.empty()) {
+  // (float inputs: no exponent plane in temp memory, the encoder splits the float words itself)
+  int rc = DGPU_OK;
+  if (classes.empty()) {
+    rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, B, in, out, ft, maxSize, histogram_dev, outSize_dev, 0xffffffffu, &plan,
+                      work_dev);
+  } else {
+    // every size class on the kernels of its own geometry, one after the other (EncodeClass)
     EncodeShared shared;
-    int rc = DGPU_OK;
     for (const EncodeClass& c : classes) {
-      rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, B, in, out, 0, c.maxSize, nullptr, outSize_dev, 0xffffffffu, nullptr,
+      rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, B, in, out, ft, c.maxSize, nullptr, outSize_dev, 0xffffffffu, nullptr,
                         work_dev, &c, &shared);
       if (rc) break;
     }
-    if (tempUsed) *tempUsed = arena.requested();
-    return rc;
   }
-  int rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, B, in, out, 0, maxSize, histogram_dev, outSize_dev, 0xffffffffu,
-                        &plan, work_dev);
   if (tempUsed) *tempUsed = arena.requested();
   return rc;
+}
+
+int ansEncodeImpl(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, int P, int useChecksum, uint32_t B,
+    const HostParams* hp /*null => stride views below*/, const BatchView* strideIn,
+    const BatchView* strideOut, uint32_t maxSize, const uint32_t* histogram_dev,
+    uint32_t* outSize_dev, hipStream_t stream) {
+  DGPU_REQUIRE(validProbBits(P), "probBits must be 9, 10 or 11");
+  DGPU_REQUIRE(B <= 65535u, "numInBatch must be <= 65535");
+  DGPU_REQUIRE(encodableSize(maxSize), "input larger than 1717538816 bytes: its maximum compressed size exceeds INT32_MAX (GpuANSEncode.cu:22)");
+  if (tempUsed) *tempUsed = 0;
+  if (B == 0) return DGPU_OK;
+  return encodeBatch(temp_dev, tempBytes, tempUsed, 0u, P, useChecksum, B, hp, strideIn, strideOut, maxSize, histogram_dev, outSize_dev, stream);
 }
 
 int floatCompressImpl(
@@ -1681,46 +1530,7 @@ int floatCompressImpl(
   DGPU_REQUIRE(encodableSize(maxSize), "tensor larger than 1717538816 words: the maximum compressed size of its exponent plane exceeds INT32_MAX (GpuANSEncode.cu:22)");
   if (tempUsed) *tempUsed = 0;
   if (B == 0) return DGPU_OK;
-
-  StreamLease streamLease(stream);
-  TempArena arena(temp_dev, tempBytes, streamLease);
-  ParamLease lease;
-  BatchView in, out;
-  int rc = DGPU_OK;
-  RaggedPlan plan;
-  const uint32_t* work_dev = nullptr;
-  std::vector<EncodeClass> classes;
-  if (!asStrideViews(hp, false, &in, &out)) {
-    const uint64_t *inP = nullptr, *outP = nullptr;
-    const uint32_t* sz = nullptr;
-    HostParams listed;
-    const HostParams* up = &hp;
-    if (planEncodeClassesCached(hp.sizes, ft, &classes, &listed.work) || planEncode(hp.sizes, ft, maxSize, true, &plan, &listed.work)) {
-      listed.inPtrs = hp.inPtrs, listed.outPtrs = hp.outPtrs, listed.sizes = hp.sizes;
-      up = &listed;
-    }
-    rc = uploadParams(lease, stream, *up, &inP, &outP, &sz, nullptr, &work_dev);
-    if (rc) return rc;
-    in = viewPointers(inP, sz, 0);
-    out = viewPointers(outP, nullptr, 0);
-  }
-
-  // No exponent plane in temp memory: the encoder splits the float words itself.
-  if (!classes.empty()) {
-    // every size class on the kernels of its own geometry, one after the other (EncodeClass)
-    EncodeShared shared;
-    for (const EncodeClass& c : classes) {
-      rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, B, in, out, ft, c.maxSize, nullptr, outSize_dev, 0xffffffffu, nullptr,
-                        work_dev, &c, &shared);
-      if (rc) break;
-    }
-    if (tempUsed) *tempUsed = arena.requested();
-    return rc;
-  }
-  rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, B, in, out, ft, maxSize, nullptr, outSize_dev, 0xffffffffu, &plan,
-                    work_dev);
-  if (tempUsed) *tempUsed = arena.requested();
-  return rc;
+  return encodeBatch(temp_dev, tempBytes, tempUsed, ft, P, useChecksum, B, &hp, nullptr, nullptr, maxSize, nullptr, outSize_dev, stream);
 }
 
 // Order of k_ans_decode's workgroups (kernels_decode.h: decodeTileOf).  Measured on MI355X, cold round trip
@@ -1746,36 +1556,6 @@ uint32_t decodeOrder(uint32_t B) {
   const int forced = g_decOrder.load();
   if (forced >= 0 && forced <= (int)kDecOrderXcd) return (uint32_t)forced;
   return B >= 64u ? kDecOrderXcd : kDecOrderElementMajor;
-}
-
-template <int P, uint32_t FT>
-int launchDecodePF(const DecodeArgs& a, uint32_t tileBlocks, dim3 grid, hipStream_t stream) {
-  if (tileBlocks == kDecBlocksPerSingleTile) {
-    // every capacity <= 4096 symbols: two elements per wavefront (kernels_pairs.h)
-    const uint32_t elems = (a.order == kDecOrderMap && a.workMap) ? a.numListed : a.numInBatch;  // (a size class: its elements)
-    DGPU_LAUNCH("k_ans_decode_pair", stream, (k_ans_decode_pair<P, FT>), dim3((elems + 1u) / 2u), dim3(64), decPairLdsBytes(P, FT),
-                stream, a);
-  } else if (tileBlocks == kDecBlocksPerTinyTile) {
-    DGPU_LAUNCH("k_ans_decode", stream, (k_ans_decode<P, FT, kDecBlocksPerTinyTile>), grid, dim3(kDecBlocksPerTinyTile * 32u),
-                decLdsBytes(P, FT, kDecBlocksPerTinyTile), stream, a);
-  } else if (tileBlocks == kDecBlocksPerSmallTile) {
-    DGPU_LAUNCH("k_ans_decode", stream, (k_ans_decode<P, FT, kDecBlocksPerSmallTile>), grid, dim3(kDecBlocksPerSmallTile * 32u),
-                decLdsBytes(P, FT, kDecBlocksPerSmallTile), stream, a);
-  } else {
-    DGPU_LAUNCH("k_ans_decode", stream, (k_ans_decode<P, FT, kDecBlocksPerTile>), grid, dim3(kDecBlocksPerTile * 32u),
-                decLdsBytes(P, FT, kDecBlocksPerTile), stream, a);
-  }
-  DGPU_HIP(hipGetLastError());
-  return DGPU_OK;
-}
-
-template <uint32_t FT>
-int launchDecodeF(int P, const DecodeArgs& a, uint32_t tileBlocks, dim3 grid, hipStream_t stream) {
-  switch (P) {
-    case 9: return launchDecodePF<9, FT>(a, tileBlocks, grid, stream);
-    case 10: return launchDecodePF<10, FT>(a, tileBlocks, grid, stream);
-    default: return launchDecodePF<11, FT>(a, tileBlocks, grid, stream);
-  }
 }
 
 int decodeImpl(
@@ -1850,54 +1630,41 @@ int decodeImpl(
   const uint32_t maxBlocks = divUp(maxCapacity, kBlockSize);
   const uint32_t tileBlocks = decTileBlocksFor(maxBlocks);
   const uint32_t maxTiles = std::max(1u, divUp(maxBlocks, tileBlocks));
+  // what every launch of the call has in common
+  DecodeArgs d;
+  d.in = in;
+  d.out = out;
+  d.floatType = ft;
+  d.outSuccess = useChecksum ? successForChecksum : outSuccess_dev;
+  d.outSize = useChecksum ? sizesForChecksum : outSize_dev;
+  d.inBytes = inBytes_dev;
+  d.uniformInBytes = uniformInBytes;
+  d.numInBatch = B;
+  // (k_ans_decode_pair, every capacity <= 4096 symbols: one workgroup per pair of elements)
+  auto launch = [&](uint32_t blocks, uint32_t tiles, uint32_t elems) {
+    return launchVariant(decoderVariant(P, ft, blocks), dim3(blocks == kDecBlocksPerSingleTile ? (elems + 1u) / 2u : tiles), stream, d);
+  };
   // every size class of the batch on the decoder of its own geometry, one after the other (DecodeClass)
   for (const DecodeClass& c : classes) {
-    DecodeArgs d;
-    d.in = in;
-    d.out = out;
-    d.floatType = ft;
-    d.outSuccess = useChecksum ? successForChecksum : outSuccess_dev;
-    d.outSize = useChecksum ? sizesForChecksum : outSize_dev;
-    d.inBytes = inBytes_dev;
-    d.uniformInBytes = uniformInBytes;
-    d.numInBatch = B;
     d.maxTiles = std::max(1u, divUp(c.maxBlocks, c.tileBlocks));
     d.order = kDecOrderMap;
     d.workMap = work_dev + (c.tileBlocks == 1u ? c.elemsAt : c.tilesAt);
     d.numListed = c.numElems;
-    const dim3 grid(std::max(c.numTiles, 1u));
-    int rc;
-    if (ft == 0) rc = launchDecodeF<0>(P, d, c.tileBlocks, grid, stream);
-    else if (ft == kFloat16) rc = launchDecodeF<kFloat16>(P, d, c.tileBlocks, grid, stream);
-    else if (ft == kBFloat16) rc = launchDecodeF<kBFloat16>(P, d, c.tileBlocks, grid, stream);
-    else rc = launchDecodeF<kFloat32>(P, d, c.tileBlocks, grid, stream);
+    int rc = launch(c.tileBlocks, std::max(c.numTiles, 1u), c.numElems);
     if (rc) return rc;
   }
   if (classes.empty()) {
-    DecodeArgs d;
-    d.in = in;
-    d.out = out;
-    d.floatType = ft;
-    d.outSuccess = useChecksum ? successForChecksum : outSuccess_dev;
-    d.outSize = useChecksum ? sizesForChecksum : outSize_dev;
-    d.inBytes = inBytes_dev;
-    d.uniformInBytes = uniformInBytes;
-    d.numInBatch = B;
     d.maxTiles = maxTiles;
     d.order = decodeOrder(B);
     d.workMap = nullptr;
     d.numListed = 0;
-    dim3 grid((d.order == kDecOrderXcd ? roundUp(B, 8u) : B) * maxTiles);
+    uint32_t grid = (d.order == kDecOrderXcd ? roundUp(B, 8u) : B) * maxTiles;
     if (work_dev && numListedTiles) {
       d.order = kDecOrderMap;
       d.workMap = work_dev;
-      grid = dim3(numListedTiles);
+      grid = numListedTiles;
     }
-    int rc;
-    if (ft == 0) rc = launchDecodeF<0>(P, d, tileBlocks, grid, stream);
-    else if (ft == kFloat16) rc = launchDecodeF<kFloat16>(P, d, tileBlocks, grid, stream);
-    else if (ft == kBFloat16) rc = launchDecodeF<kBFloat16>(P, d, tileBlocks, grid, stream);
-    else rc = launchDecodeF<kFloat32>(P, d, tileBlocks, grid, stream);
+    int rc = launch(tileBlocks, grid, B);
     if (rc) return rc;
   }
 
@@ -2472,7 +2239,8 @@ int dgpu_ans_histogram_batch_stride(
   noFuse.arrive = nullptr;
   noFuse.acc = nullptr;
   noFuse.norm = NormalizeArgs{};
-  hipLaunchKernelGGL((k_histogram<kHistSlotsLarge, true>), grid, dim3(256), 0, (hipStream_t)stream, in, histogram_dev, 0u, noFuse);
+  const HistogramVariant hist = histogramVariant(0u, false, true);
+  hipLaunchKernelGGL(hist.fn, grid, dim3(hist.threads), hist.ldsBytes, (hipStream_t)stream, in, histogram_dev, 0u, noFuse);
   DGPU_HIP(hipGetLastError());
   return DGPU_OK;
 }

@@ -1,0 +1,160 @@
+// Which template instantiation of a kernel a launch uses.  Every family's instantiations share one signature, so a
+// launchable variant is a value: the kernel, its workgroup size, its dynamic LDS bytes and its profiling name.  The
+// selection functions below are the only place where an instantiation is named and where "which forms exist" is
+// stated; asking for a form that does not exist returns the nearest one that does.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <map>
+#include <mutex>
+#include <type_traits>
+
+#include "format.h"
+#include "kernels_decode.h"
+#include "kernels_encode.h"
+#include "kernels_pairs.h"
+#include "kernels_stats.h"
+
+namespace dgpu {
+
+template <typename... Args>
+struct KernelVariant {
+  void (*fn)(Args...);
+  uint32_t threads;   // workgroup size
+  uint32_t ldsBytes;  // dynamic LDS
+  const char* name;   // for DGPU_LAUNCH / dgpu_prof_summary
+};
+using EncodeVariant = KernelVariant<EncodeArgs>;
+using DecodeVariant = KernelVariant<DecodeArgs>;
+using HistogramVariant = KernelVariant<BatchView, uint32_t*, uint32_t, HistFuse>;
+using StatsSingleVariant = KernelVariant<BatchView, NormalizeArgs, const uint32_t*, uint32_t>;
+
+// Workgroups of `v` that fit on one CU at once (at least 1).  Asked of the runtime once per variant and process.
+template <typename... Args>
+uint32_t workgroupsPerCu(const KernelVariant<Args...>& v) {
+  static std::mutex mu;
+  static std::map<const void*, uint32_t> cache;
+  std::lock_guard<std::mutex> g(mu);
+  auto it = cache.find((const void*)v.fn);
+  if (it != cache.end()) return it->second;
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, v.fn, (int)v.threads, v.ldsBytes) != hipSuccess || n < 1) n = 1;
+  return cache[(const void*)v.fn] = (uint32_t)n;
+}
+
+// Run-time value -> compile-time constant: f receives a std::integral_constant.
+template <uint32_t V>
+using UintC = std::integral_constant<uint32_t, V>;
+template <typename F>
+auto withFloatType(uint32_t ft, F&& f) {
+  switch (ft) {
+    case 0: return f(UintC<0>{});
+    case kFloat16: return f(UintC<kFloat16>{});
+    case kBFloat16: return f(UintC<kBFloat16>{});
+    default: return f(UintC<kFloat32>{});
+  }
+}
+template <typename F>
+auto withProbBits(int P, F&& f) {
+  switch (P) {
+    case 9: return f(std::integral_constant<int, 9>{});
+    case 10: return f(std::integral_constant<int, 10>{});
+    default: return f(std::integral_constant<int, 11>{});
+  }
+}
+template <typename F>
+auto withProbBitsAndFloatType(int P, uint32_t ft, F&& f) {
+  return withFloatType(ft, [&](auto kFT) { return withProbBits(P, [&](auto kP) { return f(kP, kFT); }); });
+}
+
+// Float inputs use the small-stage / spilling encoder (6 workgroups per CU), raw bytes the worst-case stage (3 per
+// CU; kernels_encode.h).
+constexpr bool encodeSpills(uint32_t ft) { return ft != 0; }
+
+// The encoder of tiles of `tileBlocks` blocks.
+//   * single-block tiles go to k_ans_encode_pair: two ELEMENTS per wavefront, always one workgroup per pair;
+//   * hwDispatch: one workgroup per tile, dispatched by the hardware in ticket order, instead of persistent workgroups
+//     that walk the tickets.  8-block float tiles exist in the persistent form only (hardware dispatch measured no
+//     gain there);
+//   * wide: the wide stage (kSpillStageWordsWide) exists for persistent 8-block bf16 / fp32 tiles only.
+inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, bool hwDispatch, bool wide) {
+  return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> EncodeVariant {
+    constexpr int kP = decltype(p)::value;
+    constexpr uint32_t kFT = decltype(f)::value;
+    constexpr bool kSpill = encodeSpills(kFT);
+    if (tileBlocks == kBlocksPerSingleTile) {
+      return {k_ans_encode_pair<kP, kFT, kSpill>, 64u, encPairLdsBytes(kP, kSpill, kFT), "k_ans_encode_pair"};
+    }
+    auto tiled = [](auto tb, auto persistent, auto wideStage) -> EncodeVariant {
+      constexpr uint32_t kTB = decltype(tb)::value;
+      constexpr bool kPersistent = decltype(persistent)::value, kWide = decltype(wideStage)::value;
+      return {k_ans_encode<kP, kFT, kSpill, kTB, kPersistent, kWide>, encThreads(kTB), encLdsBytes(kP, kSpill, kFT, kTB, kWide),
+              "k_ans_encode"};
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (tileBlocks == kBlocksPerTinyTile) {
+      return hwDispatch ? tiled(UintC<kBlocksPerTinyTile>{}, no, no) : tiled(UintC<kBlocksPerTinyTile>{}, yes, no);
+    }
+    if (tileBlocks == kBlocksPerSmallTile) {
+      return hwDispatch ? tiled(UintC<kBlocksPerSmallTile>{}, no, no) : tiled(UintC<kBlocksPerSmallTile>{}, yes, no);
+    }
+    if constexpr (kFT == kBFloat16 || kFT == kFloat32) {
+      if (wide) return tiled(UintC<kBlocksPerTile>{}, yes, yes);
+    }
+    if constexpr (!kSpill) {
+      if (hwDispatch) return tiled(UintC<kBlocksPerTile>{}, no, no);
+    }
+    return tiled(UintC<kBlocksPerTile>{}, yes, no);
+  });
+}
+
+// The decoder of tiles of `tileBlocks` blocks; batches whose every capacity is one block go to k_ans_decode_pair (two
+// elements per wavefront, kernels_pairs.h).
+inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks) {
+  return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> DecodeVariant {
+    constexpr int kP = decltype(p)::value;
+    constexpr uint32_t kFT = decltype(f)::value;
+    if (tileBlocks == kDecBlocksPerSingleTile) return {k_ans_decode_pair<kP, kFT>, 64u, decPairLdsBytes(kP, kFT), "k_ans_decode_pair"};
+    auto tiled = [](auto tb) -> DecodeVariant {
+      constexpr uint32_t kTB = decltype(tb)::value;
+      return {k_ans_decode<kP, kFT, kTB>, decThreads(kTB), decLdsBytes(kP, kFT, kTB), "k_ans_decode"};
+    };
+    if (tileBlocks == kDecBlocksPerTinyTile) return tiled(UintC<kDecBlocksPerTinyTile>{});
+    if (tileBlocks == kDecBlocksPerSmallTile) return tiled(UintC<kDecBlocksPerSmallTile>{});
+    return tiled(UintC<kDecBlocksPerTile>{});
+  });
+}
+
+// The histogram pass: bins with kHistSlotsSmall or kHistSlotsLarge lane slots, non-temporal or ordinary input loads.
+inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTemporal) {
+  return withFloatType(ft, [&](auto f) -> HistogramVariant {
+    constexpr uint32_t kFT = decltype(f)::value;
+    auto of = [](auto slots, auto nt) -> HistogramVariant {
+      constexpr uint32_t kS = decltype(slots)::value;
+      constexpr bool kNt = decltype(nt)::value;
+      if constexpr (kFT == 0) {
+        return {k_histogram<kS, kNt>, 256u, 0u, "k_histogram"};
+      } else {
+        return {k_float_histogram<kFT, kS, kNt>, 256u, 0u, "k_float_histogram"};
+      }
+    };
+    constexpr UintC<kHistSlotsSmall> small{};
+    constexpr UintC<kHistSlotsLarge> large{};
+    if (nonTemporal) return smallBins ? of(small, std::true_type{}) : of(large, std::true_type{});
+    return smallBins ? of(small, std::false_type{}) : of(large, std::false_type{});
+  });
+}
+
+// One wavefront counts and normalises a single-block element (kernels_pairs.h).  Not built for float32, whose batches
+// keep the workgroup per element (encodeCommon).
+inline StatsSingleVariant statsSingleVariant(uint32_t ft, bool nonTemporal) {
+  return withFloatType(ft, [&](auto f) -> StatsSingleVariant {
+    constexpr uint32_t kFT = decltype(f)::value == kFloat32 ? kBFloat16 : decltype(f)::value;
+    if (nonTemporal) return {k_stats_single<kFT, true>, 64u * kSingleStatWaves, 0u, "k_stats_single"};
+    return {k_stats_single<kFT, false>, 64u * kSingleStatWaves, 0u, "k_stats_single"};
+  });
+}
+
+}  // namespace dgpu

@@ -73,7 +73,7 @@ constexpr uint32_t kSpillStageWords = 1024;       // bf16 / fp32: the compressed
 // the archive out of the memory-side cache: decode 122 us); 1280 words (5 workgroups per CU): 91 / 104.
 constexpr uint32_t kSpillStageWordsFp16 = 1280;
 // ... and bf16 / fp32 batches of elements of few tiles take the same 1280 words (k_ans_encode, kWide; capi.hip,
-// encoderWideStage): five workgroups per CU instead of six and no block of N(0,1) exponents -- 717 words on average,
+// kWideStageMaxTiles): five workgroups per CU instead of six and no block of N(0,1) exponents -- 717 words on average,
 // the flush check fires above 768 -- ever flushes: 256 x 512 Ki bf16 encode 90.2 -> 87.5 us, fp32 step - 1.6 %; elements
 // of hundreds of tiles lose (16 x 8 Mi 112 -> 116 us: fewer tiles in flight behind the in-order commit) and keep 1024
 // (profiles/r06_ab_encoder_five_per_cu_*.txt).
