@@ -12,8 +12,11 @@ from .ops import (  # noqa: F401
     compress_data,
     compress_data_simple,
     compress_data_split_size,
+    block_cover,
     decompress_data,
+    decompress_data_range,
     decompress_data_simple,
+    decompress_data_slice,
     decompress_data_split_size,
     max_any_compressed_output_size,
     max_any_compressed_size,

@@ -903,9 +903,10 @@ std::atomic<int> g_workLists{[] {
 // elementMajor (encoder): an element's tiles are consecutive -- descriptors and claim words are then indexed by the
 // ticket -- elements in descending size (the large ones start first, the small ones fill the end); *tileBase receives
 // each element's first ticket.  Otherwise (decoder: no dependence between tiles) tile-major.
+// always (ranged decode, which has no rectangle to fall back to): list whatever the policy and the test hook say.
 bool planTileList(const std::vector<uint32_t>& sizes, uint32_t tileSymbols, uint32_t maxTiles, uint32_t minTiles, std::vector<uint32_t>* work,
-                  std::vector<uint32_t>* tileBase = nullptr) {
-  const int mode = g_workLists.load();
+                  std::vector<uint32_t>* tileBase = nullptr, bool always = false) {
+  const int mode = always ? 1 : g_workLists.load();
   const size_t B = sizes.size();
   if (mode == 0 || B == 0 || B > 65535u || maxTiles > 65536u || tileSymbols == 0) return false;
   std::vector<uint32_t> tiles(B);
@@ -1714,6 +1715,72 @@ int decodeImpl(
   return status;
 }
 
+// Ranged decode (k_ans_decode_range): blocks [firstBlock[i], firstBlock[i] + numBlocks[i]) of every element, into a
+// buffer that holds the range.  One geometry per call, chosen from the largest range; the work list holds the tiles of
+// each range, counted from its first block: as many as the request and the capacity allow (the element may turn out to
+// end earlier -- those workgroups leave after the header, as the tiles beyond a short element do in a whole decode).
+// firstBlock and numBlocks travel in front of the list.  No temp memory, no host synchronisation.
+int decodeRangeImpl(
+    size_t* tempUsed, uint32_t ft, int P, uint32_t B, const void* const* in, const uint32_t* inBytes,
+    const uint32_t* firstBlock, const uint32_t* numBlocks, void* const* out, const uint32_t* outCapacity,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+  DGPU_REQUIRE(validProbBits(P), "probBits must be 9, 10 or 11");
+  DGPU_REQUIRE(ft == 0 || validFloatType(ft), "floatType must be float16, bfloat16 or float32");
+  DGPU_REQUIRE(B <= 65535u, "numInBatch must be <= 65535");
+  if (tempUsed) *tempUsed = 0;
+  if (B == 0) return DGPU_OK;
+  DGPU_REQUIRE(in && inBytes && firstBlock && numBlocks && out && outCapacity, "ranged decode: null array with numInBatch > 0");
+  HostParams hp;
+  hp.inPtrs.resize(B);
+  hp.outPtrs.resize(B);
+  hp.sizes.assign(outCapacity, outCapacity + B);
+  hp.inBytes.assign(inBytes, inBytes + B);
+  std::vector<uint32_t> rangeSymbols(B);  // what the tiles of element i have to cover (0: no tile)
+  uint32_t maxBlocks = 0;
+  for (uint32_t i = 0; i < B; ++i) {
+    DGPU_REQUIRE(((uintptr_t)in[i] % 16) == 0, "compressed input must be 16-byte aligned");
+    // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
+    DGPU_REQUIRE(outCapacity[i] <= 0xfffff000u, "ranged decode: outCapacity must not exceed 0xfffff000");
+    hp.inPtrs[i] = (uint64_t)(uintptr_t)in[i];
+    hp.outPtrs[i] = (uint64_t)(uintptr_t)out[i];
+    // (an element that asks for blocks has tile 0, which reports it, even with no capacity at all)
+    const uint32_t blocks = numBlocks[i] ? std::max(1u, std::min(numBlocks[i], divUp(outCapacity[i], kBlockSize))) : 0u;
+    rangeSymbols[i] = blocks * kBlockSize;
+    maxBlocks = std::max(maxBlocks, blocks);
+  }
+  const uint32_t tileBlocks = maxBlocks <= 2u * kDecBlocksPerSmallTile ? kDecBlocksPerSmallTile : kDecBlocksPerTile;  // as decTileBlocksFor
+  hp.work.assign(firstBlock, firstBlock + B);
+  hp.work.insert(hp.work.end(), numBlocks, numBlocks + B);
+  if (maxBlocks == 0u) {
+    hp.work.push_back(0xffffffffu);  // nothing but empty requests: one workgroup, which reports them
+  } else if (!planTileList(rangeSymbols, tileBlocks * kBlockSize, divUp(maxBlocks, tileBlocks), 0u, &hp.work, nullptr, true)) {
+    return fail(DGPU_ERR_INVALID_ARGUMENT, "ranged decode: the ranges have too many tiles for one call");
+  }
+  const uint32_t numTiles = (uint32_t)(hp.work.size() - 2u * (size_t)B);
+
+  ParamLease lease;
+  const uint64_t *inP = nullptr, *outP = nullptr;
+  const uint32_t *cap = nullptr, *inBytes_dev = nullptr, *work_dev = nullptr;
+  int rc = uploadParams(lease, stream, hp, &inP, &outP, &cap, &inBytes_dev, &work_dev);
+  if (rc) return rc;
+  DecodeArgs d;
+  d.in = viewPointers(inP, nullptr, 0);
+  d.out = viewPointers(outP, cap, 0);
+  d.floatType = ft;
+  d.outSuccess = outSuccess_dev;
+  d.outSize = outSize_dev;
+  d.inBytes = inBytes_dev;
+  d.uniformInBytes = 0;
+  d.numInBatch = B;
+  d.maxTiles = std::max(1u, divUp(maxBlocks, tileBlocks));
+  d.order = kDecOrderMap;
+  d.firstBlock = work_dev;
+  d.numBlocks = work_dev + B;
+  d.workMap = work_dev + 2u * (size_t)B;
+  d.numListed = 0;
+  return launchVariant(decoderVariant(P, ft, tileBlocks, true), dim3(numTiles), stream, d);
+}
+
 int splitSizesToPointers(
     const void* base, const uint32_t* splitSizes, uint32_t B, uint32_t wordBytes,
     std::vector<uint64_t>* ptrs, std::vector<uint32_t>* sizes, uint32_t* maxSize) {
@@ -2049,6 +2116,27 @@ int dgpu_float_decompress_split_size_bounded(
   DGPU_REQUIRE(validFloatType(floatType), "floatType must be float16, bfloat16 or float32");
   return decodeSplitCommon(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum, numInBatch, in, out_dev,
                            outSplitSizes, outSuccess_dev, outSize_dev, stream, errBatch, inBytes);
+}
+
+// ---- ranged decode (no upstream equivalent) -------------------------------------
+int dgpu_ans_decode_batch_pointer_range(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, int probBits, uint32_t numInBatch,
+    const void* const* in, const uint32_t* inBytes, const uint32_t* firstBlock, const uint32_t* numBlocks,
+    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream) {
+  (void)temp_dev;
+  (void)tempBytes;
+  return decodeRangeImpl(tempUsed, 0, probBits, numInBatch, in, inBytes, firstBlock, numBlocks, out, outCapacity,
+                         outSuccess_dev, outSize_dev, (hipStream_t)stream);
+}
+int dgpu_float_decompress_range(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, uint32_t numInBatch,
+    const void* const* in, const uint32_t* inBytes, const uint32_t* firstBlock, const uint32_t* numBlocks,
+    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream) {
+  (void)temp_dev;
+  (void)tempBytes;
+  DGPU_REQUIRE(validFloatType(floatType), "floatType must be float16, bfloat16 or float32");
+  return decodeRangeImpl(tempUsed, floatType, probBits, numInBatch, in, inBytes, firstBlock, numBlocks, out, outCapacity,
+                         outSuccess_dev, outSize_dev, (hipStream_t)stream);
 }
 
 // ---- float stride batches with capacities on both sides (the compressed collectives) --------------------

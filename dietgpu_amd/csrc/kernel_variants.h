@@ -112,10 +112,19 @@ inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, boo
 
 // The decoder of tiles of `tileBlocks` blocks; batches whose every capacity is one block go to k_ans_decode_pair (two
 // elements per wavefront, kernels_pairs.h).
-inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks) {
+//   * ranged: k_ans_decode_range, which decodes a block range of every element; it exists for 16- and 4-block tiles
+//     (a range of one or two blocks takes the 4-block form).
+inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, bool ranged = false) {
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> DecodeVariant {
     constexpr int kP = decltype(p)::value;
     constexpr uint32_t kFT = decltype(f)::value;
+    if (ranged) {
+      auto tiled = [](auto tb) -> DecodeVariant {
+        constexpr uint32_t kTB = decltype(tb)::value;
+        return {k_ans_decode_range<kP, kFT, kTB>, decThreads(kTB), decLdsBytes(kP, kFT, kTB), "k_ans_decode_range"};
+      };
+      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
+    }
     if (tileBlocks == kDecBlocksPerSingleTile) return {k_ans_decode_pair<kP, kFT>, 64u, decPairLdsBytes(kP, kFT), "k_ans_decode_pair"};
     auto tiled = [](auto tb) -> DecodeVariant {
       constexpr uint32_t kTB = decltype(tb)::value;

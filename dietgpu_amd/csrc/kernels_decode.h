@@ -61,6 +61,9 @@ struct DecodeArgs {
   const uint32_t* workMap; // kDecOrderMap: [grid] element << 16 | tile, the tiles that exist (the host knows the capacities);
                            // k_ans_decode_pair: [numListed] the elements to pair up
   uint32_t numListed;      // k_ans_decode_pair with a workMap: its entries
+  // k_ans_decode_range only (see decodeTile): blocks [firstBlock[b], firstBlock[b] + numBlocks[b]) of element b
+  const uint32_t* firstBlock = nullptr;  // [B]
+  const uint32_t* numBlocks = nullptr;   // [B]; 0xffffffff = to the end of the element
 };
 __device__ __forceinline__ uint64_t decodeInBytes(const DecodeArgs& a, uint32_t b) {
   return a.inBytes ? (uint64_t)a.inBytes[b] : (a.uniformInBytes ? (uint64_t)a.uniformInBytes : ~0ull);
@@ -581,9 +584,27 @@ __device__ __forceinline__ void decodeBlock(
   runGroups(std::integral_constant<bool, kFull>{}, (int)groups - 1, 0);
 }
 
-// grid = (maxTiles, B), 32 threads per block of the tile (512 or 128), LDS = word rings + 64-bit LUT.
-template <int P, uint32_t FT, uint32_t kTileBlocks>
-__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeArgs a) {
+// One workgroup of the tiled decoder: 32 threads per block of the tile (512 or 128), LDS = word rings + 64-bit LUT.
+// The body of k_ans_decode (kRanged = false) and of k_ans_decode_range (kRanged = true), below.
+//
+// kRanged: blocks [firstBlock[b], firstBlock[b] + numBlocks[b]) of element b, clipped to the element's end, and block
+// firstBlock + k goes to out + k * 4096 words: the output buffer holds the range, not the element.
+//   * Tiles are counted from the range's first block (half-wave hw of tile t has block firstBlock + t * kTileBlocks + hw),
+//     so the waves of a range are filled from the bottom whatever the parity of firstBlock, every wave but the last holds
+//     two full blocks, and the work list (always kDecOrderMap) has ceil(blocks of the range / kTileBlocks) tiles per
+//     element.  Blocks past the range's end behave like blocks past the element's end: not fetched, decoded or stored.
+//   * Tile 0 of the list reports the element and vouches for the descriptors OF THE RANGE only: a corrupt descriptor
+//     outside the range is neither read nor noticed, and does not affect the call.  The cost follows the range.
+//   * Header checks as for the whole element (magic, version, probBits, float type, block count, pdf sum, the archive
+//     inside inBytes); success also needs firstBlock * 4096 <= total (a range that begins exactly at the end is empty
+//     and succeeds) and the clipped range inside the capacity.  outSize = words (bytes) of the clipped range.  The
+//     capacity is that of the range buffer, so it does not bound the element's size; inBytes (always given) does.
+//   * Read from the archive: the headers, the pdf table, descriptors, lane states and compressed words of the range's
+//     blocks and their slices of the non-compressed plane(s).  A checksum in the archive is ignored.
+//   * An element with numBlocks == 0 has no tile; workgroup 0 of the grid reports it (size 0, success) without reading
+//     its archive.  A call of nothing but such elements lists one entry whose element index is not below numInBatch.
+template <int P, uint32_t FT, uint32_t kTileBlocks, bool kRanged>
+__device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks);
   // the LUT-build scratch (cdf, pdf: 2 KiB, read while the LUT is stored) sits in the ring area
   static_assert(kTileBlocks * kRingBytes >= 2048u, "");
@@ -600,6 +621,26 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeAr
   const uint32_t hw = wave * 2u + (upper ? 1u : 0u);
   uint32_t b, tile;
   if (!decodeTileOf(a, blockIdx.x, &b, &tile)) return;  // uniform (kDecOrderXcd pads the grid to a multiple of 8 elements)
+  uint32_t rFirst = 0;   // kRanged: first block of the range
+  uint64_t rEnd = 0;     // kRanged: one past its last block, as requested (not yet clipped to the element)
+  if constexpr (kRanged) {
+    if (blockIdx.x == 0) {
+      for (uint32_t e = tid; e < a.numInBatch; e += kDecThreads) {
+        if (a.numBlocks[e] == 0u) {
+          if (a.outSuccess) a.outSuccess[e] = 1;
+          if (a.outSize) a.outSize[e] = 0;
+        }
+      }
+    }
+    if (b >= a.numInBatch) return;  // uniform: the entry of a list without tiles
+    rFirst = a.firstBlock[b];
+    rEnd = (uint64_t)rFirst + a.numBlocks[b];
+  }
+  // kRanged: words (bytes) of the range in an element of `total`; 0 for a range that begins past the end
+  auto rangeWords = [&](uint32_t total) -> uint32_t {
+    const uint64_t lo = (uint64_t)rFirst * kBlockSize, hi = rEnd * kBlockSize;
+    return lo > total ? 0u : (uint32_t)((hi < total ? hi : (uint64_t)total) - lo);
+  };
 
   const uint8_t* archive = a.in.ptr(b);
   uint32_t floatSize = 0;
@@ -615,13 +656,14 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeAr
     // the float header locates the ANS archive: check it before following it
     // (GpuFloatHeader::checkMagicAndVersion / getFloatType asserts, GpuFloatUtils.cuh:31-41, GpuFloatDecompress.cuh:332-382)
     const FloatHeader fh = *(const FloatHeader*)archive;
+    // (kRanged: the capacity is the range's and is checked against the range below)
     const bool fhOk = fh.magicAndVersion == ((kFloatMagic << 16) | kFloatVersion) && (fh.options & 0xfu) == FT &&
-        fh.size <= a.out.size(b) &&
+        (kRanged || fh.size <= a.out.size(b)) &&
         (uint64_t)sizeof(FloatHeader) + floatUncompDataSize(FT, fh.size) + sizeof(AnsHeader) <= inBytes;
     if (!fhOk) {  // uniform
       if (tile == 0 && tid == 0) {
         if (a.outSuccess) a.outSuccess[b] = 0;
-        if (a.outSize) a.outSize[b] = fh.size;
+        if (a.outSize) a.outSize[b] = kRanged ? rangeWords(fh.size) : fh.size;
       }
       return;
     }
@@ -634,12 +676,18 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeAr
   // a checked float header says that an ANS archive of that many blocks follows.  Raw ANS archives learn their block
   // count from the header and fetch descriptor and states after it, as before.  A load that is not to be made yet
   // reads the first bytes of the header again.
-  const uint32_t block = tile * kTileBlocks + hw;
+  uint32_t block = tile * kTileBlocks + hw;
+  bool inRange = true;
+  if constexpr (kRanged) {
+    const uint64_t blk = (uint64_t)rFirst + block;
+    inRange = blk < rEnd;
+    block = inRange ? (uint32_t)blk : 0u;
+  }
   const bool extentKnown = inBytes != ~0ull;
   const uint32_t ansOff = ansOffsetInArchive(FT, floatSize);
   const uint32_t nbSpec = FT ? divUp(floatSize, kBlockSize) : 0u;
   const bool pdfEarly = extentKnown ? (uint64_t)ansOff + ansOverhead(0u) <= inBytes : FT != 0u;
-  const bool blockEarly = FT != 0u && block < nbSpec && (!extentKnown || (uint64_t)ansOff + ansOverhead(nbSpec) <= inBytes);
+  const bool blockEarly = FT != 0u && inRange && block < nbSpec && (!extentKnown || (uint64_t)ansOff + ansOverhead(nbSpec) <= inBytes);
   const AnsHeader header = *(const AnsHeader*)ans;
   uint2 pdfRaw = make_uint2(0u, 0u);
   if (wave == 0) pdfRaw = *(const uint2*)(pdfEarly ? ans + sizeof(AnsHeader) + 8u * lane : ans);  // pdf[4 lane .. 4 lane + 3]
@@ -658,6 +706,7 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeAr
   // total <= capacity, nb == ceil(total / 4096), block sizes as the format
   // prescribes, block data inside [0, totalCompressedWords).
   bool success = a.out.size(b) >= total;
+  if constexpr (kRanged) success = (uint64_t)rFirst * kBlockSize <= total && rangeWords(total) <= a.out.size(b);
   success = success && header.magicAndVersion == ((kAnsMagic << 16) | kAnsVersion) &&
       (header.options & 0xfu) == (uint32_t)P;
   if (FT) success = success && floatSize == total;
@@ -667,11 +716,17 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeAr
   if (!success) {  // uniform: nothing else of the archive is read
     if (tile == 0 && tid == 0) {
       if (a.outSuccess) a.outSuccess[b] = 0;
-      if (a.outSize) a.outSize[b] = total;
+      if (a.outSize) a.outSize[b] = kRanged ? rangeWords(total) : total;
     }
     return;
   }
-  if (tile * kTileBlocks >= nb && tile != 0) return;
+  // the blocks this workgroup may touch: [.., endBlock), and the first one of its tile
+  uint32_t endBlock = nb, tileFirst = tile * kTileBlocks;
+  if constexpr (kRanged) {
+    endBlock = rEnd < nb ? (uint32_t)rEnd : nb;  // (rFirst <= nb: the range begins inside the element)
+    tileFirst += rFirst;
+  }
+  if (tileFirst >= endBlock && tile != 0) return;
 
   const uint2* blockWords = (const uint2*)(ans + ansBlockWordsOffset(nb));
   // {uncompressed words << 16 | compressed words, start} of block i must be what an
@@ -682,18 +737,18 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeAr
     return (bw.x >> 16) == want && (bw.y & (kBlockAlignWords - 1u)) == 0u &&
         (uint64_t)bw.y + roundUp(words, kBlockAlignWords) <= (uint64_t)totalWords;
   };
-  // tile 0 vouches for the whole element (it alone writes outSuccess); its loads are
+  // tile 0 vouches for the whole element (kRanged: the whole range; it alone writes outSuccess); its loads are
   // issued here and checked after the LUT build
   bool allBlocksOk = true;
   if (tile == 0) {
-    for (uint32_t i = tid; i < nb; i += kDecThreads) allBlocksOk = allBlocksOk && blockOk(i, blockWords[i]);
+    for (uint32_t i = rFirst + tid; i < endBlock; i += kDecThreads) allBlocksOk = allBlocksOk && blockOk(i, blockWords[i]);
   }
 
   // This half-wave's block descriptor and lane states and (wave 0) the pdf table: already on their way (float
   // archives, above), or requested NOW, in the same round trip as tile 0's descriptor checks; as soon as the descriptor
   // is there the block's compressed words and its first non-compressed bytes are requested too (decodePrefetch), and
   // all of it lands while the LUT is being built.
-  bool haveBlock = block < nb;
+  bool haveBlock = inRange && block < endBlock;
   if (!haveBlock) {
     bwMine = make_uint2(0u, 0u);
     state = 0;
@@ -716,7 +771,10 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeAr
   const uint8_t* gwords = ans + ansOverhead(nb) + 2u * (size_t)start;
   RowSink<FT> sink;
   // (a half without a block points at its wave's first block: its prefetches must stay inside the archive)
-  sink.init(a.out.ptr(b), archive, floatSize, (size_t)(haveBlock ? block : (block & ~1u)) * kBlockSize, hl);
+  uint32_t sinkBlock = haveBlock ? block : (block & ~1u);
+  if constexpr (kRanged) sinkBlock = haveBlock ? block : tileFirst + (hw & ~1u);
+  sink.init(a.out.ptr(b), archive, floatSize, (size_t)sinkBlock * kBlockSize, hl);
+  if constexpr (kRanged) sink.out -= (size_t)rFirst * kBlockSize;  // the planes are the element's, the output is the range's
   // LDS address of the dynamic segment (0: this kernel has no static LDS); the
   // rings must be 2 KiB aligned for the and-or addressing in decodeBlock
   const uint32_t ldsBase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem;
@@ -782,9 +840,9 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeAr
     const bool pdfOk = nb == 0u || *sPdfSum == (1u << P);
     if (tile == 0 && tid == 0) {
       if (a.outSuccess) a.outSuccess[b] = (blocksOk && pdfOk) ? 1 : 0;
-      if (a.outSize) a.outSize[b] = total;
+      if (a.outSize) a.outSize[b] = kRanged ? rangeWords(total) : total;
     }
-    if (!pdfOk || tile * kTileBlocks >= nb) return;  // uniform
+    if (!pdfOk || tileFirst >= endBlock) return;  // uniform
     if constexpr (kScanLut) {
       // mark[cdf[s]] = s for every present symbol; sym(x) = the largest mark at or below x (cdfs ascend with
       // the symbol; slot 0 belongs to the first present symbol, so "no mark" = 0 never surfaces)
@@ -914,6 +972,19 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeAr
       decodeBlock<P, FT, false, false, false, kCompact>(xpose, state, n, divUp(maxRows, kGroupRows), gwords, numWords, ringLds, sLut, sink, hl, upper);
     }
   }
+}
+
+// grid = the (element, tile) pairs in the order of DecodeArgs::order
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeArgs a) {
+  decodeTile<P, FT, kTileBlocks, false>(a);
+}
+
+// Ranged form: grid = the listed tiles of the ranges (kDecOrderMap; DecodeArgs::firstBlock / numBlocks / inBytes set).
+// Built for 16- and 4-block tiles.
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_range(DecodeArgs a) {
+  decodeTile<P, FT, kTileBlocks, true>(a);
 }
 
 }  // namespace dgpu

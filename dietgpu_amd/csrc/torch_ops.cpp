@@ -446,6 +446,67 @@ std::vector<at::Tensor> decompress_data_simple(
   return tOuts;
 }
 
+// Ranged decode (no reference op): blocks [first_block[i], first_block[i] + num_blocks[i]) of archive i into ts_out[i],
+// which holds the range (dgpu_ans_decode_batch_pointer_range / dgpu_float_decompress_range).  num_blocks[i] < 0 or
+// >= 2^32 - 1 means "to the end of the element".  No checksum argument: a checksum covers the whole element.
+int64_t decompress_data_range(
+    bool compressAsFloat, const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tOuts,
+    const std::vector<int64_t>& firstBlock, const std::vector<int64_t>& numBlocks, const std::optional<at::Tensor>& tempMem,
+    const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.size() == tOuts.size());
+  TORCH_CHECK(tIns.size() == firstBlock.size() && tIns.size() == numBlocks.size(), "dietgpu: one first_block and num_blocks per tensor");
+  TORCH_CHECK(tIns.front().device().is_cuda());
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tIns.size();
+  std::vector<const void*> inPtrs(n);
+  std::vector<void*> outPtrs(n);
+  std::vector<uint32_t> outCapacity(n), inBytes(n), first(n), count(n);
+  for (size_t i = 0; i < n; ++i) {
+    auto& tIn = tIns[i];
+    auto& tOut = tOuts[i];
+    TORCH_CHECK(tIn.device().is_cuda());
+    TORCH_CHECK(tIn.get_device() == dev);
+    TORCH_CHECK(tIn.is_contiguous());
+    TORCH_CHECK(tOut.device().is_cuda());
+    TORCH_CHECK(tOut.get_device() == dev);
+    TORCH_CHECK(tOut.is_contiguous());
+    TORCH_CHECK(tIn.dtype() == at::kByte);
+    if (compressAsFloat) {
+      floatTypeFromDtype(tOut.scalar_type());
+      TORCH_CHECK(tOut.scalar_type() == tOuts[0].scalar_type());
+    }
+    TORCH_CHECK(firstBlock[i] >= 0 && firstBlock[i] <= (int64_t)std::numeric_limits<uint32_t>::max(), "dietgpu: first_block out of range");
+    first[i] = (uint32_t)firstBlock[i];
+    const bool toEnd = numBlocks[i] < 0 || numBlocks[i] >= (int64_t)std::numeric_limits<uint32_t>::max();
+    count[i] = toEnd ? std::numeric_limits<uint32_t>::max() : (uint32_t)numBlocks[i];
+    inPtrs[i] = tIn.data_ptr();
+    inBytes[i] = (uint32_t)std::min<int64_t>(tIn.numel(), std::numeric_limits<uint32_t>::max());
+    outPtrs[i] = tOut.data_ptr();
+    auto cap = compressAsFloat ? tOut.numel() : tOut.numel() * tOut.element_size();
+    TORCH_CHECK((uint64_t)cap <= std::numeric_limits<uint32_t>::max());
+    outCapacity[i] = (uint32_t)cap;
+  }
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  size_t used = 0;
+  uint8_t* status = outStatus ? (uint8_t*)outStatus->data_ptr() : nullptr;
+  uint32_t* sizes = outSizes ? (uint32_t*)outSizes->data_ptr() : nullptr;
+  if (compressAsFloat) {
+    check(dgpu_float_decompress_range(tmp.ptr, tmp.bytes, &used, floatTypeFromDtype(tOuts[0].scalar_type()), precision(), (uint32_t)n,
+                                      inPtrs.data(), inBytes.data(), first.data(), count.data(), outPtrs.data(),
+                                      outCapacity.data(), status, sizes, streamOf(dev)),
+          "floatDecompressRange", true);
+  } else {
+    check(dgpu_ans_decode_batch_pointer_range(tmp.ptr, tmp.bytes, &used, precision(), (uint32_t)n, inPtrs.data(), inBytes.data(),
+                                              first.data(), count.data(), outPtrs.data(), outCapacity.data(), status, sizes,
+                                              streamOf(dev)),
+          "ansDecodeBatchPointerRange", false);
+  }
+  return (int64_t)used;
+}
+
 void set_precision(int64_t probBits) {
   TORCH_CHECK(probBits == 9 || probBits == 10 || probBits == 11, "probBits must be 9, 10 or 11");
   tPrecision = (int)probBits;
@@ -485,6 +546,9 @@ static bool coreLibraryMatches() { return dgpu_abi_version() == DGPU_ABI_VERSION
 TORCH_LIBRARY(dietgpu_amd, m) {
   if (!coreLibraryMatches()) return;
   m.def("set_precision(int prob_bits) -> ()", &dietgpu_amd::set_precision);
+  m.def(
+      "decompress_data_range(bool compress_as_float, Tensor[] ts_in, Tensor[] ts_out, int[] first_block, int[] num_blocks, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_decompressed_words=None) -> int",
+      &dietgpu_amd::decompress_data_range);
 }
 
 TORCH_LIBRARY(dietgpu, m) {

@@ -34,6 +34,20 @@ def shard_range(num_elements, rank, world):
     return start, start + base + (1 if rank < rem else 0)
 
 
+def decompress_shard(compress_as_float, ts_in, rank, world, dtype=None, temp_mem=None, prob_bits=10):
+    """This rank's `shard_range` of the WORDS of every archive in `ts_in` (a compressed checkpoint every rank holds,
+    each rank wanting its slice of every tensor) -> list of tensors.  Local: ops.decompress_data_slice on the ranges,
+    no collective; only the blocks that cover the shard are read and decoded."""
+    from . import ops
+
+    ops._check(0 <= rank < world, "rank must be in [0, world)")
+    ops._check_slice_args(compress_as_float, ts_in, dtype)
+    sizes, out_dtype = ops._archive_info(compress_as_float, ts_in, dtype)
+    ranges = [shard_range(n, rank, world) for n in sizes]
+    return ops._slice_known(compress_as_float, ts_in, [s for s, _ in ranges], [e - s for s, e in ranges], sizes, out_dtype,
+                            temp_mem, prob_bits)
+
+
 def gather_sizes(local_sizes, num_elements):
     """All-gathers per-element compressed sizes (int32 tensor of this rank's shard,
     on the backend's device) into the full [num_elements] vector on every rank."""

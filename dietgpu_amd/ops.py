@@ -451,3 +451,136 @@ def decompress_data_simple(compress_as_float, ts_in, checksum=False, temp_mem=67
                 outs.append(torch.empty((hs[i],), dtype=torch.uint8, device=device))
     decompress_data(compress_as_float, ts_in, outs, checksum, scratch, None, None, prob_bits=prob_bits)
     return outs
+
+
+# ------------------------------------------------------------- ranged decompress
+# (no reference op: dgpu_ans_decode_batch_pointer_range / dgpu_float_decompress_range, include/dietgpu_amd.h)
+BLOCK_WORDS = 4096  # the format's block: the unit a range is decoded in
+
+
+def block_cover(start, count):
+    """The blocks that hold words [start, start + count) of an element -> (first_block, num_blocks, offset): the range
+    begins `offset` words into block `first_block`.  Pure; a count of 0 covers no block."""
+    _check(start >= 0 and count >= 0, "start and count must not be negative")
+    first = start // BLOCK_WORDS
+    last = (start + count + BLOCK_WORDS - 1) // BLOCK_WORDS if count else first
+    return first, last - first, start - first * BLOCK_WORDS
+
+
+def decompress_data_range(compress_as_float, ts_in, ts_out, first_block, num_blocks, temp_mem=None, out_status=None,
+                          out_decompressed_words=None, prob_bits=K_DEFAULT_PRECISION):
+    """Decodes blocks [first_block[i], first_block[i] + num_blocks[i]) of archive i -- 4096 words each -- into ts_out[i],
+    which holds the range (block first_block + k at word k * 4096), without reading the rest of the archive -> temp bytes
+    used (0).  num_blocks[i] < 0 or 2**32 - 1: to the end of the element; a range that runs past the end is clipped.
+    out_status[i] is 0 when the range begins past the end, does not fit ts_out[i] or the archive is malformed;
+    out_decompressed_words[i] is the size of the clipped range.  There is no `checksum`: a checksum covers the whole
+    element and is ignored here."""
+    _check(len(ts_in) > 0)
+    _check(len(ts_in) == len(ts_out))
+    first_block, num_blocks = list(first_block), list(num_blocks)
+    _check(len(first_block) == len(ts_in) and len(num_blocks) == len(ts_in), "one first_block and num_blocks per tensor")
+    _check(ts_in[0].is_cuda, "tensors must be on the GPU")
+    if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_range"):
+        # (the op makes the per-tensor checks below itself, and raises RuntimeError like them)
+        torch.ops.dietgpu_amd.set_precision(prob_bits)
+        try:
+            return torch.ops.dietgpu_amd.decompress_data_range(compress_as_float, ts_in, ts_out, first_block, num_blocks, temp_mem,
+                                                               out_status, out_decompressed_words)
+        finally:
+            torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+    dev = ts_in[0].get_device()
+    caps = []
+    for f in first_block:
+        _check(0 <= f <= _U32_MAX, "first_block out of range")
+    for ti, to in zip(ts_in, ts_out):
+        _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous())
+        _check(to.is_cuda and to.get_device() == dev and to.is_contiguous())
+        _check(ti.dtype == torch.uint8)
+        if compress_as_float:
+            _float_type(to)
+            _check(to.dtype == ts_out[0].dtype)
+        cap = to.numel() if compress_as_float else to.numel() * to.element_size()
+        _check(cap <= _U32_MAX)
+        caps.append(cap)
+    n = len(ts_in)
+    counts = [_U32_MAX if (c < 0 or c >= _U32_MAX) else c for c in num_blocks]
+    _validate_status(out_status, out_decompressed_words, n, dev)
+    with torch.cuda.device(dev):
+        tp, tb = _temp(temp_mem, dev)
+        used = C.c_size_t(0)
+        if compress_as_float:
+            check(lib().dgpu_float_decompress_range(
+                tp, tb, C.byref(used), _float_type(ts_out[0]), prob_bits, n, _ptr_array(ts_in), _in_bytes(ts_in),
+                _u32_array(first_block), _u32_array(counts), _ptr_array(ts_out), _u32_array(caps), _ptr(out_status),
+                _ptr(out_decompressed_words), _stream()))
+        else:
+            check(lib().dgpu_ans_decode_batch_pointer_range(
+                tp, tb, C.byref(used), prob_bits, n, _ptr_array(ts_in), _in_bytes(ts_in), _u32_array(first_block),
+                _u32_array(counts), _ptr_array(ts_out), _u32_array(caps), _ptr(out_status), _ptr(out_decompressed_words),
+                _stream()))
+    return int(used.value)
+
+
+def _check_slice_args(compress_as_float, ts_in, dtype):
+    _check(len(ts_in) > 0)
+    for t in ts_in:
+        _check(t.is_cuda, "compressed tensors must be on the GPU")
+    if compress_as_float:
+        _check(dtype is None or dtype in _DTYPE_TO_FT, "dtype must be float16, bfloat16 or float32")
+    else:
+        _check(dtype is None or dtype == torch.uint8, "archives of raw bytes decode to uint8")
+
+
+def _archive_info(compress_as_float, ts_in, dtype):
+    """-> (words of every archive, the dtype they decode to), read from the headers (one synchronising copy)"""
+    dev, device, n = ts_in[0].get_device(), ts_in[0].device, len(ts_in)
+    for t in ts_in:
+        _check(t.get_device() == dev and t.is_contiguous() and t.dtype == torch.uint8)
+    with torch.cuda.device(dev):
+        sizes = torch.empty((n,), dtype=torch.int32, device=device)
+        types = torch.zeros((n,), dtype=torch.int32, device=device)
+        if compress_as_float:
+            check(lib().dgpu_float_get_compressed_info(None, 0, _ptr_array(ts_in), n, _ptr(sizes), _ptr(types), None, _stream()))
+        else:
+            check(lib().dgpu_ans_get_compressed_info(None, 0, _ptr_array(ts_in), n, _ptr(sizes), None, _stream()))
+        hs, ht = [v & _U32_MAX for v in sizes.tolist()], types.tolist()
+    if not compress_as_float:
+        return hs, torch.uint8
+    for t in ht:
+        _check(t in _FT_TO_DTYPE and t == ht[0], "the archives must hold one float type")
+    _check(dtype is None or _DTYPE_TO_FT[dtype] == ht[0], "the archives hold another float type than `dtype`")
+    return hs, _FT_TO_DTYPE[ht[0]]
+
+
+def _slice_known(compress_as_float, ts_in, starts, counts, sizes, out_dtype, temp_mem, prob_bits):
+    device = ts_in[0].device
+    covers, bufs = [], []
+    for start, count, size in zip(starts, counts, sizes):
+        _check(start + count <= size, f"words [{start}, {start + count}) are past the end of an element of {size}")
+        first, blocks, offset = block_cover(start, count)
+        covers.append((first, blocks, offset))
+        words = min(size, (first + blocks) * BLOCK_WORDS) - first * BLOCK_WORDS if blocks else 0
+        bufs.append(torch.empty((words,), dtype=out_dtype, device=device))
+    status = torch.empty((len(ts_in),), dtype=torch.uint8, device=device)
+    decompress_data_range(compress_as_float, ts_in, bufs, [c[0] for c in covers], [c[1] for c in covers], temp_mem, status, None,
+                          prob_bits=prob_bits)
+    bad = [i for i, ok in enumerate(status.tolist()) if not ok]
+    _check(not bad, f"ranged decode failed for batch members {bad}: malformed archive")
+    return [buf.narrow(0, c[2] if count else 0, count) for buf, c, count in zip(bufs, covers, counts)]
+
+
+def decompress_data_slice(compress_as_float, ts_in, starts, counts, dtype=None, temp_mem=None, prob_bits=K_DEFAULT_PRECISION):
+    """Words [starts[i], starts[i] + counts[i]) of every archive -> list of tensors (bytes: uint8).
+
+    The range is decoded in the format's blocks of 4096 words: each element's covering block range (`block_cover`) goes
+    into one buffer of its own, the whole batch in ONE ranged decode call, and the result is a view into that buffer --
+    no copy.  The price of keeping sub-block edges out of the kernel: at most 2 x 4095 words per element are decoded
+    (and held by the view's storage) beyond what was asked.  Sizes and, for floats, the dtype are read from the archive
+    headers (`dtype`, if given, must match).  RuntimeError on a range past an element's end or a malformed archive."""
+    starts, counts = [int(v) for v in starts], [int(v) for v in counts]
+    _check(len(starts) == len(ts_in) and len(counts) == len(ts_in), "one start and count per tensor")
+    _check_slice_args(compress_as_float, ts_in, dtype)
+    for s0, c0 in zip(starts, counts):
+        _check(s0 >= 0 and c0 >= 0, "starts and counts must not be negative")
+    sizes, out_dtype = _archive_info(compress_as_float, ts_in, dtype)
+    return _slice_known(compress_as_float, ts_in, starts, counts, sizes, out_dtype, temp_mem, prob_bits)

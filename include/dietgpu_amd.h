@@ -66,7 +66,7 @@ const char* dgpu_version(void);
 /* Bumped whenever an entry point of this header is added, removed or changes its meaning.  Code that is built
  * separately against this header (the tensor-op library of this repository, a cgo / JNI binding) compares the value it was compiled with
  * against the library it finds at run time, so that a stale build fails at load instead of inside a call. */
-#define DGPU_ABI_VERSION 7u
+#define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
  * precondition).  The reference aborts through glog CHECK instead. */
@@ -247,6 +247,37 @@ int dgpu_float_decompress_split_size_bounded(
     void* out_dev, const uint32_t* outSplitSizes,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream, int32_t* errBatch);
 
+/* ---- ranged decode (no upstream equivalent) ----------------------------------------
+ * Decodes blocks [firstBlock[i], firstBlock[i] + numBlocks[i]) of archive i -- a block is the format's 4096 symbols
+ * (bytes / float words) -- without reading or decoding the rest: block firstBlock + k goes to out[i] + k * 4096 words,
+ * so out[i] holds the range, and `outCapacity` (bytes for ans, float words for float) is that buffer's.  Pointer-array
+ * batches that always take `inBytes`, as the *_bounded calls above.  firstBlock / numBlocks are HOST arrays;
+ * numBlocks[i] == UINT32_MAX means "to the end of the element", and a range that runs past the end is clipped to it.
+ *   - outSize_dev[i] = min(total, (firstBlock + numBlocks) * 4096) - firstBlock * 4096 words (bytes).
+ *   - outSuccess_dev[i] = 0 and nothing written when a header check fails (as for a whole decode), firstBlock * 4096 >
+ *     total, the clipped range does not fit outCapacity[i], or a block descriptor OF THE RANGE is malformed.  A range
+ *     that begins exactly at the end is empty and succeeds.  Descriptors outside the range are not looked at.
+ *   - numBlocks[i] == 0: nothing of archive i is read; size 0, success 1.
+ *   - outCapacity[i] must not exceed 0xfffff000 (whole blocks below 4 Gi words): DGPU_ERR_INVALID_ARGUMENT otherwise.
+ *   - There is no useChecksum: a checksum covers the whole element and cannot be verified from a part of it.  Archives
+ *     written with one decode normally; the checksum is ignored.
+ *   - Of the archive only the headers, the probability table and the descriptors, lane states, compressed words and
+ *     non-compressed plane slices of the range's blocks are read.  One kernel geometry per call, from its largest range.
+ *   - No temp memory is used (*tempUsed = 0) and nothing synchronises: capturable into a HIP graph under the same
+ *     conditions as the other pointer-array decode calls (the arrays resident from an earlier identical call). */
+int dgpu_ans_decode_batch_pointer_range(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, int probBits,
+    uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
+    const uint32_t* firstBlock, const uint32_t* numBlocks,
+    void* const* out, const uint32_t* outCapacity,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
+int dgpu_float_decompress_range(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits,
+    uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
+    const uint32_t* firstBlock, const uint32_t* numBlocks,
+    void* const* out, const uint32_t* outCapacity,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
+
 /* ---- float stride batches with capacities (no upstream equivalent) ---------------
  * For exchanging compressed rows at a FIXED width (README.md:68-72,104: compressed collectives): the rows of one
  * tensor are compressed straight into the rows of the send matrix, `outStrideBytes` apart, and nothing is stored
@@ -342,7 +373,8 @@ void dgpu_debug_set_decoder_order(int order);
  * (GpuANSEncode.cuh:692-760, GpuANSDecode.cuh:299-403: maxSize x numInBatch); here the sizes arrive as host arrays, so
  * for a batch in which at least a fifth of that rectangle would be empty the host lists the tiles and histogram parts
  * that exist and the kernels work through the lists.  -1 (default): that policy; 0: always the rectangles; 1: the
- * lists for every pointer-array call whose sizes differ.  Archives and outputs are byte-identical either way. */
+ * lists for every pointer-array call whose sizes differ.  Archives and outputs are byte-identical either way.  The
+ * ranged decode calls are not affected: they have no rectangle and always list the tiles of their ranges. */
 void dgpu_debug_set_work_lists(int mode);
 
 /* Measurement / test hook: SIZE CLASSES inside one batch.  Upstream sizes the one grid of a call for its largest member
