@@ -707,6 +707,7 @@ uint32_t gridX(uint32_t maxBytes, uint32_t bytesPerBlock, uint32_t cap) {
 
 bool validProbBits(int p) { return p == 9 || p == 10 || p == 11; }
 bool validFloatType(uint32_t ft) { return ft == kFloat16 || ft == kBFloat16 || ft == kFloat32; }
+const char* const kMsgFloatType = "floatType must be float16, bfloat16 or float32";
 
 // getMaxCompressedSize, GpuANSEncode.cu:13-25 (block SIZE passed as block COUNT [sic]).  Upstream CHECKs the result
 // against INT32_MAX (GpuANSEncode.cu:22: inputs beyond 419 321 blocks = 1 717 538 816 bytes abort); here such a size
@@ -722,65 +723,136 @@ uint32_t maxCompressedSizeHost(uint32_t bytes) {
 }
 bool encodableSize(uint32_t symbols) { return symbols <= kMaxEncodableBytes; }
 
-// Device batch description assembled by each entry point.
-struct DeviceBatch {
-  BatchView in;
-  BatchView out;
-  uint32_t maxSize = 0;
-};
-
-// Layout of the packed parameter block: [in ptrs][out ptrs][sizes]
-struct HostParams {
+// One call's batch as its entry point describes it: HOST arrays of device pointers and sizes (packed and uploaded as
+// [in ptrs][out ptrs][sizes][inBytes][work], the block the parameter cache hashes) or, when `strided`, two stride views.
+struct Batch {
+  uint32_t n = 0;  // elements
+  bool strided = false;
+  BatchView in, out;  // strided
   std::vector<uint64_t> inPtrs, outPtrs;
-  std::vector<uint32_t> sizes;
+  std::vector<uint32_t> sizes;    // input sizes (encode) or output capacities (decode)
   std::vector<uint32_t> inBytes;  // decode, *_bounded entry points: bytes available per compressed input
+  uint32_t uniformInBytes = 0;    // ... of a strided decode (0 = unknown)
   std::vector<uint32_t> work;     // work lists of a batch whose elements differ widely in size (RaggedPlan)
+  uint32_t maxSize = 0;           // the largest size / capacity
 };
 
-bool streamIsCapturing(hipStream_t stream) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &st) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
+// One side of a batch as an entry point receives it: a HOST array of device pointers, or (ptrs == nullptr) a base and
+// a stride; every address must be a multiple of `align` (the stride from the second element on), `msg` says so.
+struct Side {
+  const void* const* ptrs;
+  const void* base;
+  uint64_t stride;
+  uint32_t align;
+  const char* msg;
+};
+const char* const kMsgCompIn = "compressed input must be 16-byte aligned";
+const char* const kMsgCompOut = "compressed output must be 16-byte aligned";
+const char* const kMsgAnsIn = "ANS input must be 4-byte aligned";
+const char* const kMsgFloatIn = "float input must be float-word aligned";
+
+Side ptrSide(const void* const* ptrs, uint32_t align = 1, const char* msg = "") { return Side{ptrs, nullptr, 0, align, msg}; }
+Side strideSide(const void* base, uint64_t stride, uint32_t align = 1, const char* msg = "") { return Side{nullptr, base, stride, align, msg}; }
+
+int sideAligned(const Side& s, uint32_t B) {
+  DGPU_REQUIRE(s.ptrs || ((uintptr_t)s.base % s.align == 0 && (B <= 1 || s.stride % s.align == 0)), s.msg);
+  return DGPU_OK;
+}
+int sideAddresses(const Side& s, uint32_t B, std::vector<uint64_t>* addr) {
+  if (int rc = sideAligned(s, B)) return rc;
+  addr->resize(B);
+  for (uint32_t i = 0; i < B; ++i) {
+    (*addr)[i] = s.ptrs ? (uint64_t)(uintptr_t)s.ptrs[i] : (uint64_t)(uintptr_t)s.base + i * s.stride;
+    DGPU_REQUIRE(!s.ptrs || (*addr)[i] % s.align == 0, s.msg);
   }
-  return st == hipStreamCaptureStatusActive;
+  return DGPU_OK;
 }
 
-int uploadParams(
-    ParamLease& lease, hipStream_t stream, const HostParams& hp,
-    const uint64_t** inPtrs_dev, const uint64_t** outPtrs_dev, const uint32_t** sizes_dev,
-    const uint32_t** inBytes_dev = nullptr, const uint32_t** work_dev = nullptr) {
-  const size_t nIn = hp.inPtrs.size(), nOut = hp.outPtrs.size(), nSz = hp.sizes.size(), nIb = hp.inBytes.size();
-  const size_t nWk = work_dev ? hp.work.size() : 0;
-  const size_t workAt = (nIn + nOut) * 8 + alignUp(nSz * 4, 8) + alignUp(nIb * 4, 8);
-  const size_t bytes = workAt + alignUp(nWk * 4, 8);
+// The three shapes a batch arrives in.  sizesOnOut: `size` / `sizes` are output capacities (decode) rather than input
+// sizes (encode).
+int strideBatch(Batch* b, uint32_t B, const Side& in, const Side& out, uint32_t size, bool sizesOnOut, uint32_t inBytes = 0) {
+  if (int rc = sideAligned(in, B)) return rc;
+  if (int rc = sideAligned(out, B)) return rc;
+  b->n = B;
+  b->strided = true;
+  b->in = viewStride(in.base, in.stride, sizesOnOut ? 0u : size);
+  b->out = viewStride(out.base, out.stride, sizesOnOut ? size : 0u);
+  b->uniformInBytes = inBytes;
+  b->maxSize = size;
+  return DGPU_OK;
+}
+int pointerBatch(Batch* b, uint32_t B, const Side& in, const Side& out, const uint32_t* sizes, const uint32_t* inBytes = nullptr) {
+  int rc = sideAddresses(in, B, &b->inPtrs);
+  if (!rc) rc = sideAddresses(out, B, &b->outPtrs);
+  if (rc) return rc;
+  b->n = B;
+  b->sizes.assign(sizes, sizes + B);
+  if (inBytes) b->inBytes.assign(inBytes, inBytes + B);
+  for (uint32_t i = 0; i < B; ++i) b->maxSize = std::max(b->maxSize, sizes[i]);
+  return DGPU_OK;
+}
+// `split`: one buffer cut into B elements of splitSizes[i] words of wordBytes, the input (encode) or the output
+// (splitOnOut); interiorAlign != 0: every element but the last must be a multiple of it (alignment rules of
+// GpuANSEncode.cu:132-140)
+int splitBatch(Batch* b, uint32_t B, const Side& split, const uint32_t* splitSizes, uint32_t wordBytes, uint32_t interiorAlign,
+               const Side& other, bool splitOnOut, const uint32_t* inBytes = nullptr) {
+  if (int rc = sideAligned(split, 1)) return rc;
+  for (uint32_t i = 0; i + 1 < B && interiorAlign; ++i) {
+    DGPU_REQUIRE(splitSizes[i] % interiorAlign == 0, "interior split sizes must be multiples of 4 bytes");
+  }
+  int rc = sideAddresses(other, B, splitOnOut ? &b->inPtrs : &b->outPtrs);
+  if (rc) return rc;
+  std::vector<uint64_t>& ptrs = splitOnOut ? b->outPtrs : b->inPtrs;
+  ptrs.resize(B);
+  b->n = B;
+  b->sizes.assign(splitSizes, splitSizes + B);
+  if (inBytes) b->inBytes.assign(inBytes, inBytes + B);
+  uint64_t prefix = 0;
+  for (uint32_t i = 0; i < B; ++i) {
+    ptrs[i] = (uint64_t)(uintptr_t)split.base + prefix * wordBytes;
+    prefix += splitSizes[i];
+    b->maxSize = std::max(b->maxSize, splitSizes[i]);
+  }
+  return DGPU_OK;
+}
+
+// A batch as the kernels see it: device views, the device copies of inBytes and work, and the hold on the parameter
+// block they live in.
+struct DeviceBatch {
+  BatchView in, out;
+  const uint32_t* inBytes = nullptr;
+  const uint32_t* work = nullptr;
+  ParamLease lease;
+};
+
+int uploadParams(const Batch& b, bool sizesOnOut, StreamLease& stream, DeviceBatch* d) {
+  const size_t outAt = b.inPtrs.size() * 8, sizesAt = outAt + b.outPtrs.size() * 8, inBytesAt = sizesAt + alignUp(b.sizes.size() * 4, 8),
+               workAt = inBytesAt + alignUp(b.inBytes.size() * 4, 8), bytes = workAt + alignUp(b.work.size() * 4, 8);
   if (bytes == 0) return DGPU_OK;
   static thread_local std::vector<uint8_t> block;
   block.assign(bytes, 0);
   uint8_t* h = block.data();
-  if (nIn) memcpy(h, hp.inPtrs.data(), nIn * 8);
-  if (nOut) memcpy(h + nIn * 8, hp.outPtrs.data(), nOut * 8);
-  if (nSz) memcpy(h + (nIn + nOut) * 8, hp.sizes.data(), nSz * 4);
-  if (nIb) memcpy(h + (nIn + nOut) * 8 + alignUp(nSz * 4, 8), hp.inBytes.data(), nIb * 4);
-  if (nWk) memcpy(h + workAt, hp.work.data(), nWk * 4);
+  if (outAt) memcpy(h, b.inPtrs.data(), outAt);
+  if (sizesAt > outAt) memcpy(h + outAt, b.outPtrs.data(), sizesAt - outAt);
+  if (!b.sizes.empty()) memcpy(h + sizesAt, b.sizes.data(), b.sizes.size() * 4);
+  if (!b.inBytes.empty()) memcpy(h + inBytesAt, b.inBytes.data(), b.inBytes.size() * 4);
+  if (!b.work.empty()) memcpy(h + workAt, b.work.data(), b.work.size() * 4);
   ParamCache::Entry* entry = nullptr;
   bool miss = false;
-  {
-    const bool capturing = streamIsCapturing(stream);
-    const hipError_t ae = paramCache().acquire(h, bytes, stream, &entry, &miss, capturing);
-    if (ae == hipErrorStreamCaptureUnsupported && capturing && g_captureHint) return fail(DGPU_ERR_HIP, std::string("HIP graph capture: ") + g_captureHint);
-    DGPU_HIP(ae);
-  }
-  lease.bind(entry, miss, stream);
-  uint8_t* dev = (uint8_t*)entry->dev;
-  *inPtrs_dev = nIn ? (const uint64_t*)dev : nullptr;
-  *outPtrs_dev = nOut ? (const uint64_t*)(dev + nIn * 8) : nullptr;
-  *sizes_dev = nSz ? (const uint32_t*)(dev + (nIn + nOut) * 8) : nullptr;
-  if (inBytes_dev) *inBytes_dev = nIb ? (const uint32_t*)(dev + (nIn + nOut) * 8 + alignUp(nSz * 4, 8)) : nullptr;
-  if (work_dev) *work_dev = nWk ? (const uint32_t*)(dev + workAt) : nullptr;
+  const bool capturing = stream.capturing();
+  const hipError_t ae = paramCache().acquire(h, bytes, stream.stream(), &entry, &miss, capturing);
+  if (ae == hipErrorStreamCaptureUnsupported && capturing && g_captureHint) return fail(DGPU_ERR_HIP, std::string("HIP graph capture: ") + g_captureHint);
+  DGPU_HIP(ae);
+  d->lease.bind(entry, miss, stream.stream());
+  const uint8_t* dev = (const uint8_t*)entry->dev;
+  auto at = [dev](size_t offset, bool present) { return present ? dev + offset : nullptr; };
+  const uint32_t* sizes = (const uint32_t*)at(sizesAt, !b.sizes.empty());
+  d->in = viewPointers((const uint64_t*)at(0, outAt != 0), sizesOnOut ? nullptr : sizes, 0);
+  d->out = viewPointers((const uint64_t*)at(outAt, sizesAt > outAt), sizesOnOut ? sizes : nullptr, 0);
+  d->inBytes = (const uint32_t*)at(inBytesAt, !b.inBytes.empty());
+  d->work = (const uint32_t*)at(workAt, !b.work.empty());
   return DGPU_OK;
 }
-
 
 // A pointer batch whose addresses form an arithmetic progression and whose sizes are all equal IS a stride batch
 // (the rows of one tensor, the rows of the output matrix the tensor API allocates, any batch of one): it needs no
@@ -793,17 +865,53 @@ bool progression(const std::vector<uint64_t>& p, uint64_t* stride) {
   }
   return !p.empty();
 }
-bool asStrideViews(const HostParams& hp, bool sizesOnOut, BatchView* in, BatchView* out) {
-  if (!hp.inBytes.empty() || hp.inPtrs.size() != hp.outPtrs.size()) return false;
+// THE RULE: a batch with inBytes is never turned into stride views (a stride view carries one uniformInBytes at most);
+// nor is one whose sides differ in length (the info calls: archive pointers only).
+bool asStrideViews(const Batch& b, bool sizesOnOut, BatchView* in, BatchView* out) {
+  if (!b.inBytes.empty() || b.inPtrs.size() != b.outPtrs.size()) return false;
   uint64_t inStride = 0, outStride = 0;
-  if (!progression(hp.inPtrs, &inStride) || !progression(hp.outPtrs, &outStride)) return false;
-  uint32_t u = hp.sizes.empty() ? 0u : hp.sizes[0];
-  for (uint32_t sz : hp.sizes) {
+  if (!progression(b.inPtrs, &inStride) || !progression(b.outPtrs, &outStride)) return false;
+  uint32_t u = b.sizes.empty() ? 0u : b.sizes[0];
+  for (uint32_t sz : b.sizes) {
     if (sz != u) return false;
   }
-  *in = viewStride((const void*)(uintptr_t)hp.inPtrs[0], inStride, sizesOnOut ? 0u : u);
-  *out = viewStride((const void*)(uintptr_t)hp.outPtrs[0], outStride, sizesOnOut ? u : 0u);
+  *in = viewStride((const void*)(uintptr_t)b.inPtrs[0], inStride, sizesOnOut ? 0u : u);
+  *out = viewStride((const void*)(uintptr_t)b.outPtrs[0], outStride, sizesOnOut ? u : 0u);
   return true;
+}
+
+// How a batch reaches the kernels: the caller's stride views, stride views of a pointer batch that is a progression, or
+// the uploaded block -- then with the work lists `planWork` puts into b.work (only then: a progression has equal sizes).
+// Whatever b.work holds is uploaded and hashed with the block: a planner that does not apply must leave it as it was
+// (every planner here does: they return false before they touch it, or clear it).
+template <typename PlanWork>
+int resolveBatch(Batch& b, bool sizesOnOut, StreamLease& stream, DeviceBatch* d, PlanWork planWork) {
+  if (b.strided) {
+    d->in = b.in;
+    d->out = b.out;
+    return DGPU_OK;
+  }
+  if (asStrideViews(b, sizesOnOut, &d->in, &d->out)) return DGPU_OK;
+  planWork();
+  return uploadParams(b, sizesOnOut, stream, d);
+}
+int resolveBatch(Batch& b, bool sizesOnOut, StreamLease& stream, DeviceBatch* d) {
+  return resolveBatch(b, sizesOnOut, stream, d, [] {});
+}
+
+// What every codec entry point checks before anything else, the reset of its out-parameters and the end of an empty
+// batch: *done says the call is over with the code returned.  ft: 0 = raw bytes; tooLarge (encoders): the refusal of
+// more than the encodable `maxSize` symbols.
+int checkCall(int P, uint32_t B, uint32_t ft, size_t* tempUsed, int32_t* errBatch, bool* done, const char* tooLarge = nullptr, uint32_t maxSize = 0) {
+  *done = true;
+  DGPU_REQUIRE(validProbBits(P), "probBits must be 9, 10 or 11");
+  DGPU_REQUIRE(ft == 0 || validFloatType(ft), kMsgFloatType);
+  DGPU_REQUIRE(B <= 65535u, "numInBatch must be <= 65535");
+  DGPU_REQUIRE(!tooLarge || encodableSize(maxSize), tooLarge);
+  if (tempUsed) *tempUsed = 0;
+  if (errBatch) *errBatch = -1;
+  *done = B == 0;
+  return DGPU_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -875,7 +983,7 @@ bool encoderHardwareDispatch(uint32_t numTickets, uint32_t resident) {
 // exist, spread over the persistent workgroups by a static map that hands the large tensor's tiles to three of them,
 // and two histogram workgroups for its 64 MiB (tools/ragged_probe.py: 5.7 ms per compress call against 56 us + 37 us
 // for the two size classes on their own).  The host knows the sizes (they arrive as host arrays), so for such a batch
-// it lists the work that exists -- HostParams::work, uploaded with the pointers -- and the kernels take their
+// it lists the work that exists -- Batch::work, uploaded with the pointers -- and the kernels take their
 // (element, tile / part) from the list instead of from the rectangle:
 //   * tiles: the encoder's element by element, the large elements first (a tile's predecessor has the ticket before
 //     its own, and descriptors and claim words exist for the listed tiles only); the decoder's, which do not depend on
@@ -889,7 +997,7 @@ inline uint64_t divUp64(uint64_t a, uint64_t b) { return (a + b - 1u) / b; }
 inline uint64_t roundUp64(uint64_t a, uint64_t b) { return divUp64(a, b) * b; }
 struct RaggedPlan {
   bool use = false;
-  // HostParams::work of an encode call: [numTiles] x {element << 16 | tile}, [numHistParts] x {element << 16 | part},
+  // Batch::work of an encode call: [numTiles] x {element << 16 | tile}, [numHistParts] x {element << 16 | part},
   // [B] x {the element's first ticket = index of its first descriptor and claim word}
   uint32_t numTiles = 0;
   uint32_t numHistParts = 0;
@@ -1460,47 +1568,30 @@ int encodeCommon(
 // Shared tail of the encode entry points (ft: 0 for raw bytes): the batch as stride views or uploaded pointers, with
 // the work lists of its size classes or of a ragged batch, then encodeCommon once per class or once for the batch.
 int encodeBatch(
-    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, uint32_t B,
-    const HostParams* hp /*null => stride views below*/, const BatchView* strideIn, const BatchView* strideOut,
-    uint32_t maxSize, const uint32_t* histogram_dev /*may be null*/, uint32_t* outSize_dev, hipStream_t stream) {
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b,
+    const uint32_t* histogram_dev /*may be null*/, uint32_t* outSize_dev, hipStream_t stream,
+    uint32_t outCapacity = 0xffffffffu /* as encodeCommon's */) {
   StreamLease streamLease(stream);
   TempArena arena(temp_dev, tempBytes, streamLease);
-  ParamLease lease;
-  BatchView in, out;
+  DeviceBatch d;
   RaggedPlan plan;
   std::vector<EncodeClass> classes;
-  const uint32_t* work_dev = nullptr;
-  if (hp && asStrideViews(*hp, false, &in, &out)) {
-    // (nothing to upload)
-  } else if (hp) {
-    const uint64_t *inP = nullptr, *outP = nullptr;
-    const uint32_t* sz = nullptr;
-    HostParams listed;
-    const HostParams* up = hp;
-    if ((histogram_dev == nullptr && planEncodeClassesCached(hp->sizes, ft, &classes, &listed.work)) ||
-        planEncode(hp->sizes, ft, maxSize, histogram_dev == nullptr, &plan, &listed.work)) {
-      listed.inPtrs = hp->inPtrs, listed.outPtrs = hp->outPtrs, listed.sizes = hp->sizes;
-      up = &listed;
+  int rc = resolveBatch(b, false, streamLease, &d, [&] {
+    if (histogram_dev || !planEncodeClassesCached(b.sizes, ft, &classes, &b.work)) {
+      planEncode(b.sizes, ft, b.maxSize, histogram_dev == nullptr, &plan, &b.work);
     }
-    int rc = uploadParams(lease, stream, *up, &inP, &outP, &sz, nullptr, &work_dev);
-    if (rc) return rc;
-    in = viewPointers(inP, sz, 0);
-    out = viewPointers(outP, nullptr, 0);
-  } else {
-    in = *strideIn;
-    out = *strideOut;
-  }
+  });
+  if (rc) return rc;
   // (float inputs: no exponent plane in temp memory, the encoder splits the float words itself)
-  int rc = DGPU_OK;
   if (classes.empty()) {
-    rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, B, in, out, ft, maxSize, histogram_dev, outSize_dev, 0xffffffffu, &plan,
-                      work_dev);
+    rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, b.maxSize, histogram_dev, outSize_dev, outCapacity,
+                      &plan, d.work);
   } else {
     // every size class on the kernels of its own geometry, one after the other (EncodeClass)
     EncodeShared shared;
     for (const EncodeClass& c : classes) {
-      rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, B, in, out, ft, c.maxSize, nullptr, outSize_dev, 0xffffffffu, nullptr,
-                        work_dev, &c, &shared);
+      rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, c.maxSize, nullptr, outSize_dev, outCapacity,
+                        nullptr, d.work, &c, &shared);
       if (rc) break;
     }
   }
@@ -1509,29 +1600,24 @@ int encodeBatch(
 }
 
 int ansEncodeImpl(
-    void* temp_dev, size_t tempBytes, size_t* tempUsed, int P, int useChecksum, uint32_t B,
-    const HostParams* hp /*null => stride views below*/, const BatchView* strideIn,
-    const BatchView* strideOut, uint32_t maxSize, const uint32_t* histogram_dev,
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, int P, int useChecksum, Batch& b, const uint32_t* histogram_dev,
     uint32_t* outSize_dev, hipStream_t stream) {
-  DGPU_REQUIRE(validProbBits(P), "probBits must be 9, 10 or 11");
-  DGPU_REQUIRE(B <= 65535u, "numInBatch must be <= 65535");
-  DGPU_REQUIRE(encodableSize(maxSize), "input larger than 1717538816 bytes: its maximum compressed size exceeds INT32_MAX (GpuANSEncode.cu:22)");
-  if (tempUsed) *tempUsed = 0;
-  if (B == 0) return DGPU_OK;
-  return encodeBatch(temp_dev, tempBytes, tempUsed, 0u, P, useChecksum, B, hp, strideIn, strideOut, maxSize, histogram_dev, outSize_dev, stream);
+  bool done;
+  int rc = checkCall(P, b.n, 0u, tempUsed, /*errBatch*/ nullptr, &done,
+                     "input larger than 1717538816 bytes: its maximum compressed size exceeds INT32_MAX (GpuANSEncode.cu:22)", b.maxSize);
+  if (done) return rc;
+  return encodeBatch(temp_dev, tempBytes, tempUsed, 0u, P, useChecksum, b, histogram_dev, outSize_dev, stream);
 }
 
 int floatCompressImpl(
-    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum,
-    uint32_t B, const HostParams& hp, uint32_t maxSize, uint32_t* outSize_dev,
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b, uint32_t* outSize_dev,
     hipStream_t stream) {
-  DGPU_REQUIRE(validProbBits(P), "probBits must be 9, 10 or 11");
-  DGPU_REQUIRE(validFloatType(ft), "floatType must be float16, bfloat16 or float32");
-  DGPU_REQUIRE(B <= 65535u, "numInBatch must be <= 65535");
-  DGPU_REQUIRE(encodableSize(maxSize), "tensor larger than 1717538816 words: the maximum compressed size of its exponent plane exceeds INT32_MAX (GpuANSEncode.cu:22)");
-  if (tempUsed) *tempUsed = 0;
-  if (B == 0) return DGPU_OK;
-  return encodeBatch(temp_dev, tempBytes, tempUsed, ft, P, useChecksum, B, &hp, nullptr, nullptr, maxSize, nullptr, outSize_dev, stream);
+  bool done;
+  int rc = checkCall(P, b.n, ft, tempUsed, /*errBatch*/ nullptr, &done,
+                     "tensor larger than 1717538816 words: the maximum compressed size of its exponent plane exceeds INT32_MAX (GpuANSEncode.cu:22)",
+                     b.maxSize);
+  if (done) return rc;
+  return encodeBatch(temp_dev, tempBytes, tempUsed, ft, P, useChecksum, b, nullptr, outSize_dev, stream);
 }
 
 // Order of k_ans_decode's workgroups (kernels_decode.h: decodeTileOf).  Measured on MI355X, cold round trip
@@ -1559,61 +1645,51 @@ uint32_t decodeOrder(uint32_t B) {
   return B >= 64u ? kDecOrderXcd : kDecOrderElementMajor;
 }
 
+// What every launch of a decode call has in common.
+DecodeArgs decodeArgs(const Batch& b, const DeviceBatch& d, uint32_t ft, uint8_t* outSuccess_dev, uint32_t* outSize_dev) {
+  DecodeArgs a;
+  a.in = d.in;
+  a.out = d.out;
+  a.floatType = ft;
+  a.outSuccess = outSuccess_dev;
+  a.outSize = outSize_dev;
+  a.inBytes = d.inBytes;
+  a.uniformInBytes = b.uniformInBytes;
+  a.numInBatch = b.n;
+  return a;
+}
+
 int decodeImpl(
-    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum,
-    uint32_t B, const HostParams* hp, const BatchView* strideIn, const BatchView* strideOut,
-    uint32_t maxCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream,
-    int32_t* errBatch, uint32_t uniformInBytes = 0 /* stride batches: bytes available per archive (0 = unknown) */) {
-  DGPU_REQUIRE(validProbBits(P), "probBits must be 9, 10 or 11");
-  DGPU_REQUIRE(ft == 0 || validFloatType(ft), "bad floatType");
-  DGPU_REQUIRE(B <= 65535u, "numInBatch must be <= 65535");
-  if (tempUsed) *tempUsed = 0;
-  if (errBatch) *errBatch = -1;
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b, uint8_t* outSuccess_dev,
+    uint32_t* outSize_dev, hipStream_t stream, int32_t* errBatch) {
   g_mismatches.clear();
-  if (B == 0) return DGPU_OK;
-  if (useChecksum && streamIsCapturing(stream)) {
+  bool done;
+  int rc = checkCall(P, b.n, ft, tempUsed, errBatch, &done);
+  if (done) return rc;
+  const uint32_t B = b.n, maxCapacity = b.maxSize;
+  StreamLease streamLease(stream);
+  if (useChecksum && streamLease.capturing()) {
     // the comparison is host work behind a stream synchronise (as upstream, GpuANSDecode.cuh:557-591): it would
     // invalidate the capture, and a replay could never repeat it
     return fail(DGPU_ERR_HIP, "HIP graph capture: checksum verification on decode copies to the host and synchronises the "
                               "stream; it cannot be captured into a HIP graph (decode with useChecksum = 0 under capture)");
   }
 
-  StreamLease streamLease(stream);
   TempArena arena(temp_dev, tempBytes, streamLease);
-  ParamLease lease;
-  BatchView in, out;
-  const uint32_t* inBytes_dev = nullptr;
-  const uint32_t* work_dev = nullptr;
+  DeviceBatch dev;
   uint32_t numListedTiles = 0;
   std::vector<DecodeClass> classes;
-  if (hp && asStrideViews(*hp, true, &in, &out)) {
-    // (nothing to upload)
-  } else if (hp) {
-    const uint64_t *inP = nullptr, *outP = nullptr;
-    const uint32_t* cap = nullptr;
-    // (capacities that differ widely: only the tiles inside each element's capacity are launched, see RaggedPlan)
-    HostParams listed;
-    const HostParams* up = hp;
-    if (planDecodeClassesCached(hp->sizes, &classes, &listed.work)) {
-      listed.inPtrs = hp->inPtrs, listed.outPtrs = hp->outPtrs, listed.sizes = hp->sizes, listed.inBytes = hp->inBytes;
-      up = &listed;
-    } else {
-      const uint32_t blocks = divUp(maxCapacity, kBlockSize);
-      const uint32_t tb = decTileBlocksFor(blocks);
-      if (tb != kDecBlocksPerSingleTile && planTileList(hp->sizes, tb * kBlockSize, std::max(1u, divUp(blocks, tb)), 1u, &listed.work)) {
-        listed.inPtrs = hp->inPtrs, listed.outPtrs = hp->outPtrs, listed.sizes = hp->sizes, listed.inBytes = hp->inBytes;
-        up = &listed;
-        numListedTiles = (uint32_t)listed.work.size();
-      }
+  const uint32_t maxBlocks = divUp(maxCapacity, kBlockSize);
+  const uint32_t tileBlocks = decTileBlocksFor(maxBlocks);
+  const uint32_t maxTiles = std::max(1u, divUp(maxBlocks, tileBlocks));
+  // (capacities that differ widely: only the tiles inside each element's capacity are launched, see RaggedPlan)
+  rc = resolveBatch(b, true, streamLease, &dev, [&] {
+    if (!planDecodeClassesCached(b.sizes, &classes, &b.work) && tileBlocks != kDecBlocksPerSingleTile &&
+        planTileList(b.sizes, tileBlocks * kBlockSize, maxTiles, 1u, &b.work)) {
+      numListedTiles = (uint32_t)b.work.size();
     }
-    int rc = uploadParams(lease, stream, *up, &inP, &outP, &cap, &inBytes_dev, &work_dev);
-    if (rc) return rc;
-    in = viewPointers(inP, nullptr, 0);
-    out = viewPointers(outP, cap, 0);
-  } else {
-    in = *strideIn;
-    out = *strideOut;
-  }
+  });
+  if (rc) return rc;
 
   uint32_t* sizesForChecksum = outSize_dev;
   uint8_t* successForChecksum = outSuccess_dev;
@@ -1628,19 +1704,7 @@ int decodeImpl(
     }
   }
 
-  const uint32_t maxBlocks = divUp(maxCapacity, kBlockSize);
-  const uint32_t tileBlocks = decTileBlocksFor(maxBlocks);
-  const uint32_t maxTiles = std::max(1u, divUp(maxBlocks, tileBlocks));
-  // what every launch of the call has in common
-  DecodeArgs d;
-  d.in = in;
-  d.out = out;
-  d.floatType = ft;
-  d.outSuccess = useChecksum ? successForChecksum : outSuccess_dev;
-  d.outSize = useChecksum ? sizesForChecksum : outSize_dev;
-  d.inBytes = inBytes_dev;
-  d.uniformInBytes = uniformInBytes;
-  d.numInBatch = B;
+  DecodeArgs d = decodeArgs(b, dev, ft, successForChecksum, sizesForChecksum);
   // (k_ans_decode_pair, every capacity <= 4096 symbols: one workgroup per pair of elements)
   auto launch = [&](uint32_t blocks, uint32_t tiles, uint32_t elems) {
     return launchVariant(decoderVariant(P, ft, blocks), dim3(blocks == kDecBlocksPerSingleTile ? (elems + 1u) / 2u : tiles), stream, d);
@@ -1649,9 +1713,9 @@ int decodeImpl(
   for (const DecodeClass& c : classes) {
     d.maxTiles = std::max(1u, divUp(c.maxBlocks, c.tileBlocks));
     d.order = kDecOrderMap;
-    d.workMap = work_dev + (c.tileBlocks == 1u ? c.elemsAt : c.tilesAt);
+    d.workMap = dev.work + (c.tileBlocks == 1u ? c.elemsAt : c.tilesAt);
     d.numListed = c.numElems;
-    int rc = launch(c.tileBlocks, std::max(c.numTiles, 1u), c.numElems);
+    rc = launch(c.tileBlocks, std::max(c.numTiles, 1u), c.numElems);
     if (rc) return rc;
   }
   if (classes.empty()) {
@@ -1660,12 +1724,12 @@ int decodeImpl(
     d.workMap = nullptr;
     d.numListed = 0;
     uint32_t grid = (d.order == kDecOrderXcd ? roundUp(B, 8u) : B) * maxTiles;
-    if (work_dev && numListedTiles) {
+    if (dev.work && numListedTiles) {
       d.order = kDecOrderMap;
-      d.workMap = work_dev;
+      d.workMap = dev.work;
       grid = numListedTiles;
     }
-    int rc = launch(tileBlocks, grid, B);
+    rc = launch(tileBlocks, grid, B);
     if (rc) return rc;
   }
 
@@ -1678,14 +1742,14 @@ int decodeImpl(
     DGPU_ALLOC(sums, uint32_t, arena, 2 * (size_t)B);
     DGPU_HIP(hipMemsetAsync(sums, 0, 2 * (size_t)B * 4, stream));
     dim3 grid(gridX(maxCapacity * (ft ? floatWordBytes(ft) : 1u), 64 * 1024, 64), B);
-    hipLaunchKernelGGL(k_checksum, grid, dim3(256), 0, stream, out, (const uint32_t*)sizesForChecksum,
+    hipLaunchKernelGGL(k_checksum, grid, dim3(256), 0, stream, dev.out, (const uint32_t*)sizesForChecksum,
                        (const uint8_t*)successForChecksum, sums);
     DGPU_HIP(hipGetLastError());
     if (ft) {
-      hipLaunchKernelGGL(k_float_info, dim3(divUp(B, 128)), dim3(128), 0, stream, in, B,
+      hipLaunchKernelGGL(k_float_info, dim3(divUp(B, 128)), dim3(128), 0, stream, dev.in, B,
                          (uint32_t*)nullptr, (uint32_t*)nullptr, sums + B);
     } else {
-      hipLaunchKernelGGL(k_ans_info, dim3(divUp(B, 128)), dim3(128), 0, stream, in, B,
+      hipLaunchKernelGGL(k_ans_info, dim3(divUp(B, 128)), dim3(128), 0, stream, dev.in, B,
                          (uint32_t*)nullptr, sums + B);
     }
     DGPU_HIP(hipGetLastError());
@@ -1724,78 +1788,46 @@ int decodeRangeImpl(
     size_t* tempUsed, uint32_t ft, int P, uint32_t B, const void* const* in, const uint32_t* inBytes,
     const uint32_t* firstBlock, const uint32_t* numBlocks, void* const* out, const uint32_t* outCapacity,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
-  DGPU_REQUIRE(validProbBits(P), "probBits must be 9, 10 or 11");
-  DGPU_REQUIRE(ft == 0 || validFloatType(ft), "floatType must be float16, bfloat16 or float32");
-  DGPU_REQUIRE(B <= 65535u, "numInBatch must be <= 65535");
-  if (tempUsed) *tempUsed = 0;
-  if (B == 0) return DGPU_OK;
+  // (the arrays are read after the checks that do not need them: numInBatch itself may be what is wrong)
+  bool done;
+  int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
+  if (done) return rc;
   DGPU_REQUIRE(in && inBytes && firstBlock && numBlocks && out && outCapacity, "ranged decode: null array with numInBatch > 0");
-  HostParams hp;
-  hp.inPtrs.resize(B);
-  hp.outPtrs.resize(B);
-  hp.sizes.assign(outCapacity, outCapacity + B);
-  hp.inBytes.assign(inBytes, inBytes + B);
+  Batch b;
+  rc = pointerBatch(&b, B, ptrSide(in, 16, kMsgCompIn), ptrSide(out), outCapacity, inBytes);
+  if (rc) return rc;
+  // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
+  DGPU_REQUIRE(b.maxSize <= 0xfffff000u, "ranged decode: outCapacity must not exceed 0xfffff000");
   std::vector<uint32_t> rangeSymbols(B);  // what the tiles of element i have to cover (0: no tile)
   uint32_t maxBlocks = 0;
   for (uint32_t i = 0; i < B; ++i) {
-    DGPU_REQUIRE(((uintptr_t)in[i] % 16) == 0, "compressed input must be 16-byte aligned");
-    // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
-    DGPU_REQUIRE(outCapacity[i] <= 0xfffff000u, "ranged decode: outCapacity must not exceed 0xfffff000");
-    hp.inPtrs[i] = (uint64_t)(uintptr_t)in[i];
-    hp.outPtrs[i] = (uint64_t)(uintptr_t)out[i];
     // (an element that asks for blocks has tile 0, which reports it, even with no capacity at all)
     const uint32_t blocks = numBlocks[i] ? std::max(1u, std::min(numBlocks[i], divUp(outCapacity[i], kBlockSize))) : 0u;
     rangeSymbols[i] = blocks * kBlockSize;
     maxBlocks = std::max(maxBlocks, blocks);
   }
   const uint32_t tileBlocks = maxBlocks <= 2u * kDecBlocksPerSmallTile ? kDecBlocksPerSmallTile : kDecBlocksPerTile;  // as decTileBlocksFor
-  hp.work.assign(firstBlock, firstBlock + B);
-  hp.work.insert(hp.work.end(), numBlocks, numBlocks + B);
+  b.work.assign(firstBlock, firstBlock + B);
+  b.work.insert(b.work.end(), numBlocks, numBlocks + B);
   if (maxBlocks == 0u) {
-    hp.work.push_back(0xffffffffu);  // nothing but empty requests: one workgroup, which reports them
-  } else if (!planTileList(rangeSymbols, tileBlocks * kBlockSize, divUp(maxBlocks, tileBlocks), 0u, &hp.work, nullptr, true)) {
+    b.work.push_back(0xffffffffu);  // nothing but empty requests: one workgroup, which reports them
+  } else if (!planTileList(rangeSymbols, tileBlocks * kBlockSize, divUp(maxBlocks, tileBlocks), 0u, &b.work, nullptr, true)) {
     return fail(DGPU_ERR_INVALID_ARGUMENT, "ranged decode: the ranges have too many tiles for one call");
   }
-  const uint32_t numTiles = (uint32_t)(hp.work.size() - 2u * (size_t)B);
+  const uint32_t numTiles = (uint32_t)(b.work.size() - 2u * (size_t)B);
 
-  ParamLease lease;
-  const uint64_t *inP = nullptr, *outP = nullptr;
-  const uint32_t *cap = nullptr, *inBytes_dev = nullptr, *work_dev = nullptr;
-  int rc = uploadParams(lease, stream, hp, &inP, &outP, &cap, &inBytes_dev, &work_dev);
+  StreamLease streamLease(stream);
+  DeviceBatch dev;
+  rc = resolveBatch(b, true, streamLease, &dev);
   if (rc) return rc;
-  DecodeArgs d;
-  d.in = viewPointers(inP, nullptr, 0);
-  d.out = viewPointers(outP, cap, 0);
-  d.floatType = ft;
-  d.outSuccess = outSuccess_dev;
-  d.outSize = outSize_dev;
-  d.inBytes = inBytes_dev;
-  d.uniformInBytes = 0;
-  d.numInBatch = B;
+  DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
   d.maxTiles = std::max(1u, divUp(maxBlocks, tileBlocks));
   d.order = kDecOrderMap;
-  d.firstBlock = work_dev;
-  d.numBlocks = work_dev + B;
-  d.workMap = work_dev + 2u * (size_t)B;
+  d.firstBlock = dev.work;
+  d.numBlocks = dev.work + B;
+  d.workMap = dev.work + 2u * (size_t)B;
   d.numListed = 0;
   return launchVariant(decoderVariant(P, ft, tileBlocks, true), dim3(numTiles), stream, d);
-}
-
-int splitSizesToPointers(
-    const void* base, const uint32_t* splitSizes, uint32_t B, uint32_t wordBytes,
-    std::vector<uint64_t>* ptrs, std::vector<uint32_t>* sizes, uint32_t* maxSize) {
-  ptrs->resize(B);
-  sizes->resize(B);
-  uint64_t prefix = 0;
-  uint32_t mx = 0;
-  for (uint32_t i = 0; i < B; ++i) {
-    (*ptrs)[i] = (uint64_t)(uintptr_t)base + prefix * wordBytes;
-    (*sizes)[i] = splitSizes[i];
-    prefix += splitSizes[i];
-    mx = std::max(mx, splitSizes[i]);
-  }
-  *maxSize = mx;
-  return DGPU_OK;
 }
 
 }  // namespace
@@ -1944,36 +1976,21 @@ int dgpu_ans_encode_batch_stride(
     uint32_t numInBatch, const void* in_dev, uint32_t inPerBatchSize, uint32_t inPerBatchStride,
     const uint32_t* histogram_dev, void* out_dev, uint32_t outPerBatchStride,
     uint32_t* outSize_dev, void* stream) {
-  DGPU_REQUIRE(((uintptr_t)in_dev % DGPU_ANS_REQUIRED_ALIGNMENT) == 0 &&
-                   (numInBatch <= 1 || inPerBatchStride % DGPU_ANS_REQUIRED_ALIGNMENT == 0),
-               "ANS input must be 4-byte aligned");
-  DGPU_REQUIRE(((uintptr_t)out_dev % 16) == 0 && (numInBatch <= 1 || outPerBatchStride % 16 == 0),
-               "compressed output must be 16-byte aligned");
-  BatchView in = viewStride(in_dev, inPerBatchStride, inPerBatchSize);
-  BatchView out = viewStride(out_dev, outPerBatchStride, 0);
-  return ansEncodeImpl(temp_dev, tempBytes, tempUsed, probBits, useChecksum, numInBatch, nullptr,
-                       &in, &out, inPerBatchSize, histogram_dev, outSize_dev, (hipStream_t)stream);
+  Batch b;
+  int rc = strideBatch(&b, numInBatch, strideSide(in_dev, inPerBatchStride, DGPU_ANS_REQUIRED_ALIGNMENT, kMsgAnsIn),
+                       strideSide(out_dev, outPerBatchStride, 16, kMsgCompOut), inPerBatchSize, false);
+  if (rc) return rc;
+  return ansEncodeImpl(temp_dev, tempBytes, tempUsed, probBits, useChecksum, b, histogram_dev, outSize_dev, (hipStream_t)stream);
 }
 
 int dgpu_ans_encode_batch_pointer(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, int probBits, int useChecksum,
     uint32_t numInBatch, const void* const* in, const uint32_t* inSize,
     const uint32_t* histogram_dev, void* const* out, uint32_t* outSize_dev, void* stream) {
-  HostParams hp;
-  hp.inPtrs.resize(numInBatch);
-  hp.outPtrs.resize(numInBatch);
-  hp.sizes.resize(numInBatch);
-  uint32_t maxSize = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    DGPU_REQUIRE(((uintptr_t)in[i] % DGPU_ANS_REQUIRED_ALIGNMENT) == 0, "ANS input must be 4-byte aligned");
-    DGPU_REQUIRE(((uintptr_t)out[i] % 16) == 0, "compressed output must be 16-byte aligned");
-    hp.inPtrs[i] = (uint64_t)(uintptr_t)in[i];
-    hp.outPtrs[i] = (uint64_t)(uintptr_t)out[i];
-    hp.sizes[i] = inSize[i];
-    maxSize = std::max(maxSize, inSize[i]);
-  }
-  return ansEncodeImpl(temp_dev, tempBytes, tempUsed, probBits, useChecksum, numInBatch, &hp,
-                       nullptr, nullptr, maxSize, histogram_dev, outSize_dev, (hipStream_t)stream);
+  Batch b;
+  int rc = pointerBatch(&b, numInBatch, ptrSide(in, DGPU_ANS_REQUIRED_ALIGNMENT, kMsgAnsIn), ptrSide(out, 16, kMsgCompOut), inSize);
+  if (rc) return rc;
+  return ansEncodeImpl(temp_dev, tempBytes, tempUsed, probBits, useChecksum, b, histogram_dev, outSize_dev, (hipStream_t)stream);
 }
 
 int dgpu_ans_encode_batch_split_size(
@@ -1981,23 +1998,11 @@ int dgpu_ans_encode_batch_split_size(
     uint32_t numInBatch, const void* in_dev, const uint32_t* inSplitSizes,
     const uint32_t* histogram_dev, void* out_dev, uint32_t outStride, uint32_t* outSize_dev,
     void* stream) {
-  // alignment rules of GpuANSEncode.cu:132-140
-  DGPU_REQUIRE(((uintptr_t)in_dev % DGPU_ANS_REQUIRED_ALIGNMENT) == 0, "ANS input must be 4-byte aligned");
-  DGPU_REQUIRE(((uintptr_t)out_dev % 16) == 0 && (numInBatch <= 1 || outStride % 16 == 0),
-               "compressed output must be 16-byte aligned");
-  for (uint32_t i = 0; i + 1 < numInBatch; ++i) {
-    DGPU_REQUIRE(inSplitSizes[i] % DGPU_ANS_REQUIRED_ALIGNMENT == 0,
-                 "interior split sizes must be multiples of 4 bytes");
-  }
-  HostParams hp;
-  uint32_t maxSize = 0;
-  splitSizesToPointers(in_dev, inSplitSizes, numInBatch, 1, &hp.inPtrs, &hp.sizes, &maxSize);
-  hp.outPtrs.resize(numInBatch);
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    hp.outPtrs[i] = (uint64_t)(uintptr_t)out_dev + (uint64_t)i * outStride;
-  }
-  return ansEncodeImpl(temp_dev, tempBytes, tempUsed, probBits, useChecksum, numInBatch, &hp,
-                       nullptr, nullptr, maxSize, histogram_dev, outSize_dev, (hipStream_t)stream);
+  Batch b;
+  int rc = splitBatch(&b, numInBatch, strideSide(in_dev, 0, DGPU_ANS_REQUIRED_ALIGNMENT, kMsgAnsIn), inSplitSizes, 1u,
+                      DGPU_ANS_REQUIRED_ALIGNMENT, strideSide(out_dev, outStride, 16, kMsgCompOut), false);
+  if (rc) return rc;
+  return ansEncodeImpl(temp_dev, tempBytes, tempUsed, probBits, useChecksum, b, histogram_dev, outSize_dev, (hipStream_t)stream);
 }
 
 // ---- decode ----------------------------------------------------------------
@@ -2006,36 +2011,23 @@ int dgpu_ans_decode_batch_stride(
     uint32_t numInBatch, const void* in_dev, uint32_t inPerBatchStride, void* out_dev,
     uint32_t outPerBatchStride, uint32_t outPerBatchCapacity, uint8_t* outSuccess_dev,
     uint32_t* outSize_dev, void* stream, int32_t* errBatch) {
-  DGPU_REQUIRE(((uintptr_t)in_dev % 16) == 0 && (numInBatch <= 1 || inPerBatchStride % 16 == 0),
-               "compressed input must be 16-byte aligned");
-  BatchView in = viewStride(in_dev, inPerBatchStride, 0);
-  BatchView out = viewStride(out_dev, outPerBatchStride, outPerBatchCapacity);
-  return decodeImpl(temp_dev, tempBytes, tempUsed, 0, probBits, useChecksum, numInBatch, nullptr,
-                    &in, &out, outPerBatchCapacity, outSuccess_dev, outSize_dev,
-                    (hipStream_t)stream, errBatch);
+  Batch b;
+  int rc = strideBatch(&b, numInBatch, strideSide(in_dev, inPerBatchStride, 16, kMsgCompIn), strideSide(out_dev, outPerBatchStride),
+                       outPerBatchCapacity, true);
+  if (rc) return rc;
+  return decodeImpl(temp_dev, tempBytes, tempUsed, 0, probBits, useChecksum, b, outSuccess_dev, outSize_dev, (hipStream_t)stream, errBatch);
 }
 
+// (ft: 0 for raw bytes; inBytes: the *_bounded entry points)
 static int decodePointerCommon(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int probBits,
     int useChecksum, uint32_t numInBatch, const void* const* in, void* const* out,
     const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream,
     int32_t* errBatch, const uint32_t* inBytes = nullptr) {
-  HostParams hp;
-  hp.inPtrs.resize(numInBatch);
-  hp.outPtrs.resize(numInBatch);
-  hp.sizes.resize(numInBatch);
-  if (inBytes) hp.inBytes.assign(inBytes, inBytes + numInBatch);
-  uint32_t maxCap = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    DGPU_REQUIRE(((uintptr_t)in[i] % 16) == 0, "compressed input must be 16-byte aligned");
-    hp.inPtrs[i] = (uint64_t)(uintptr_t)in[i];
-    hp.outPtrs[i] = (uint64_t)(uintptr_t)out[i];
-    hp.sizes[i] = outCapacity[i];
-    maxCap = std::max(maxCap, outCapacity[i]);
-  }
-  return decodeImpl(temp_dev, tempBytes, tempUsed, ft, probBits, useChecksum, numInBatch, &hp,
-                    nullptr, nullptr, maxCap, outSuccess_dev, outSize_dev, (hipStream_t)stream,
-                    errBatch);
+  Batch b;
+  int rc = pointerBatch(&b, numInBatch, ptrSide(in, 16, kMsgCompIn), ptrSide(out), outCapacity, inBytes);
+  if (rc) return rc;
+  return decodeImpl(temp_dev, tempBytes, tempUsed, ft, probBits, useChecksum, b, outSuccess_dev, outSize_dev, (hipStream_t)stream, errBatch);
 }
 
 int dgpu_ans_decode_batch_pointer(
@@ -2046,35 +2038,24 @@ int dgpu_ans_decode_batch_pointer(
                              in, out, outCapacity, outSuccess_dev, outSize_dev, stream, errBatch);
 }
 
+// (raw bytes: the output and every interior split 4-byte aligned)
 static int decodeSplitCommon(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int probBits,
     int useChecksum, uint32_t numInBatch, const void* const* in, void* out_dev,
     const uint32_t* outSplitSizes, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream,
     int32_t* errBatch, const uint32_t* inBytes = nullptr) {
-  HostParams hp;
-  if (inBytes) hp.inBytes.assign(inBytes, inBytes + numInBatch);
-  uint32_t maxCap = 0;
-  splitSizesToPointers(out_dev, outSplitSizes, numInBatch, ft ? floatWordBytes(ft) : 1u,
-                       &hp.outPtrs, &hp.sizes, &maxCap);
-  hp.inPtrs.resize(numInBatch);
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    DGPU_REQUIRE(((uintptr_t)in[i] % 16) == 0, "compressed input must be 16-byte aligned");
-    hp.inPtrs[i] = (uint64_t)(uintptr_t)in[i];
-  }
-  return decodeImpl(temp_dev, tempBytes, tempUsed, ft, probBits, useChecksum, numInBatch, &hp,
-                    nullptr, nullptr, maxCap, outSuccess_dev, outSize_dev, (hipStream_t)stream,
-                    errBatch);
+  const Side outSide = ft ? strideSide(out_dev, 0) : strideSide(out_dev, 0, DGPU_ANS_REQUIRED_ALIGNMENT, "output must be 4-byte aligned");
+  Batch b;
+  int rc = splitBatch(&b, numInBatch, outSide, outSplitSizes, ft ? floatWordBytes(ft) : 1u, ft ? 0u : DGPU_ANS_REQUIRED_ALIGNMENT,
+                      ptrSide(in, 16, kMsgCompIn), true, inBytes);
+  if (rc) return rc;
+  return decodeImpl(temp_dev, tempBytes, tempUsed, ft, probBits, useChecksum, b, outSuccess_dev, outSize_dev, (hipStream_t)stream, errBatch);
 }
 
 int dgpu_ans_decode_batch_split_size(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, int probBits, int useChecksum,
     uint32_t numInBatch, const void* const* in, void* out_dev, const uint32_t* outSplitSizes,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream, int32_t* errBatch) {
-  DGPU_REQUIRE(((uintptr_t)out_dev % DGPU_ANS_REQUIRED_ALIGNMENT) == 0, "output must be 4-byte aligned");
-  for (uint32_t i = 0; i + 1 < numInBatch; ++i) {
-    DGPU_REQUIRE(outSplitSizes[i] % DGPU_ANS_REQUIRED_ALIGNMENT == 0,
-                 "interior split sizes must be multiples of 4 bytes");
-  }
   return decodeSplitCommon(temp_dev, tempBytes, tempUsed, 0, probBits, useChecksum, numInBatch, in,
                            out_dev, outSplitSizes, outSuccess_dev, outSize_dev, stream, errBatch);
 }
@@ -2094,10 +2075,6 @@ int dgpu_ans_decode_batch_split_size_bounded(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, int probBits, int useChecksum,
     uint32_t numInBatch, const void* const* in, const uint32_t* inBytes, void* out_dev,
     const uint32_t* outSplitSizes, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream, int32_t* errBatch) {
-  DGPU_REQUIRE(((uintptr_t)out_dev % DGPU_ANS_REQUIRED_ALIGNMENT) == 0, "output must be 4-byte aligned");
-  for (uint32_t i = 0; i + 1 < numInBatch; ++i) {
-    DGPU_REQUIRE(outSplitSizes[i] % DGPU_ANS_REQUIRED_ALIGNMENT == 0, "interior split sizes must be multiples of 4 bytes");
-  }
   return decodeSplitCommon(temp_dev, tempBytes, tempUsed, 0, probBits, useChecksum, numInBatch, in, out_dev,
                            outSplitSizes, outSuccess_dev, outSize_dev, stream, errBatch, inBytes);
 }
@@ -2105,7 +2082,7 @@ int dgpu_float_decompress_bounded(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int useChecksum,
     uint32_t numInBatch, const void* const* in, const uint32_t* inBytes, void* const* out,
     const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream, int32_t* errBatch) {
-  DGPU_REQUIRE(validFloatType(floatType), "floatType must be float16, bfloat16 or float32");
+  DGPU_REQUIRE(validFloatType(floatType), kMsgFloatType);
   return decodePointerCommon(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum, numInBatch, in, out,
                              outCapacity, outSuccess_dev, outSize_dev, stream, errBatch, inBytes);
 }
@@ -2113,7 +2090,7 @@ int dgpu_float_decompress_split_size_bounded(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int useChecksum,
     uint32_t numInBatch, const void* const* in, const uint32_t* inBytes, void* out_dev,
     const uint32_t* outSplitSizes, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream, int32_t* errBatch) {
-  DGPU_REQUIRE(validFloatType(floatType), "floatType must be float16, bfloat16 or float32");
+  DGPU_REQUIRE(validFloatType(floatType), kMsgFloatType);
   return decodeSplitCommon(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum, numInBatch, in, out_dev,
                            outSplitSizes, outSuccess_dev, outSize_dev, stream, errBatch, inBytes);
 }
@@ -2134,7 +2111,7 @@ int dgpu_float_decompress_range(
     void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream) {
   (void)temp_dev;
   (void)tempBytes;
-  DGPU_REQUIRE(validFloatType(floatType), "floatType must be float16, bfloat16 or float32");
+  DGPU_REQUIRE(validFloatType(floatType), kMsgFloatType);
   return decodeRangeImpl(tempUsed, floatType, probBits, numInBatch, in, inBytes, firstBlock, numBlocks, out, outCapacity,
                          outSuccess_dev, outSize_dev, (hipStream_t)stream);
 }
@@ -2144,31 +2121,24 @@ int dgpu_float_compress_stride_capped(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int useChecksum,
     uint32_t numInBatch, const void* in_dev, uint32_t inWords, uint32_t inStrideBytes, void* out_dev,
     uint32_t outStrideBytes, uint32_t outCapacityBytes, uint32_t* outSize_dev, void* stream) {
-  DGPU_REQUIRE(validProbBits(probBits), "probBits must be 9, 10 or 11");
-  DGPU_REQUIRE(validFloatType(floatType), "floatType must be float16, bfloat16 or float32");
-  DGPU_REQUIRE(numInBatch <= 65535u, "numInBatch must be <= 65535");
-  DGPU_REQUIRE(encodableSize(inWords), "tensor larger than 1717538816 words (GpuANSEncode.cu:22)");
-  const uint32_t wb = floatWordBytes(floatType);
-  DGPU_REQUIRE(((uintptr_t)in_dev % wb) == 0 && (numInBatch <= 1 || inStrideBytes % wb == 0), "float input must be float-word aligned");
-  DGPU_REQUIRE(((uintptr_t)out_dev % 16) == 0 && (numInBatch <= 1 || outStrideBytes % 16 == 0) && outCapacityBytes % 16 == 0,
-               "compressed output rows, their stride and their capacity must be 16-byte aligned");
+  DGPU_REQUIRE(validFloatType(floatType), kMsgFloatType);
+  bool done;
+  int rc = checkCall(probBits, numInBatch, floatType, tempUsed, /*errBatch*/ nullptr, &done, "tensor larger than 1717538816 words (GpuANSEncode.cu:22)", inWords);
+  if (rc) return rc;
+  const char* const outMsg = "compressed output rows, their stride and their capacity must be 16-byte aligned";
+  Batch b;
+  rc = strideBatch(&b, numInBatch, strideSide(in_dev, inStrideBytes, floatWordBytes(floatType), kMsgFloatIn),
+                   strideSide(out_dev, outStrideBytes, 16, outMsg), inWords, false);
+  if (rc) return rc;
+  DGPU_REQUIRE(outCapacityBytes % 16 == 0, outMsg);
   DGPU_REQUIRE(numInBatch <= 1 || outCapacityBytes <= outStrideBytes, "outCapacityBytes must not exceed outStrideBytes");
   DGPU_REQUIRE(inWords > kBlockSize, "capped compression needs rows of more than one 4096-word block");
   // everything except the block data is stored unconditionally: it must fit
   const uint32_t nb = divUp(inWords, kBlockSize);
   const uint64_t fixed = (uint64_t)ansOffsetInArchive(floatType, inWords) + ansOverhead(nb);
   DGPU_REQUIRE(fixed <= outCapacityBytes, "outCapacityBytes is smaller than the archive's header, tables and non-compressed planes");
-  if (tempUsed) *tempUsed = 0;
-  if (numInBatch == 0) return DGPU_OK;
-  hipStream_t st = (hipStream_t)stream;
-  StreamLease streamLease(st);
-  TempArena arena(temp_dev, tempBytes, streamLease);
-  const BatchView in = viewStride(in_dev, inStrideBytes, inWords);
-  const BatchView out = viewStride(out_dev, outStrideBytes, 0);
-  int rc = encodeCommon(arena, streamLease, st, probBits, useChecksum != 0, numInBatch, in, out, floatType, inWords, nullptr,
-                        outSize_dev, outCapacityBytes);
-  if (tempUsed) *tempUsed = arena.requested();
-  return rc;
+  if (done) return DGPU_OK;  // (an empty batch, after the checks of its arguments)
+  return encodeBatch(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum, b, nullptr, outSize_dev, (hipStream_t)stream, outCapacityBytes);
 }
 
 int dgpu_float_decompress_stride_bounded(
@@ -2176,16 +2146,14 @@ int dgpu_float_decompress_stride_bounded(
     uint32_t numInBatch, const void* in_dev, uint32_t inStrideBytes, uint32_t inBytes, void* out_dev,
     uint32_t outStrideBytes, uint32_t outCapacityWords, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream,
     int32_t* errBatch) {
-  DGPU_REQUIRE(validFloatType(floatType), "floatType must be float16, bfloat16 or float32");
-  DGPU_REQUIRE(((uintptr_t)in_dev % 16) == 0 && (numInBatch <= 1 || inStrideBytes % 16 == 0),
-               "compressed input must be 16-byte aligned");
-  const uint32_t wb = floatWordBytes(floatType);
-  DGPU_REQUIRE(((uintptr_t)out_dev % wb) == 0 && (numInBatch <= 1 || outStrideBytes % wb == 0), "float output must be float-word aligned");
+  DGPU_REQUIRE(validFloatType(floatType), kMsgFloatType);
+  Batch b;
+  int rc = strideBatch(&b, numInBatch, strideSide(in_dev, inStrideBytes, 16, kMsgCompIn),
+                       strideSide(out_dev, outStrideBytes, floatWordBytes(floatType), "float output must be float-word aligned"),
+                       outCapacityWords, true, inBytes);
+  if (rc) return rc;
   DGPU_REQUIRE(inBytes != 0, "inBytes must be the bytes available per compressed row");
-  BatchView in = viewStride(in_dev, inStrideBytes, 0);
-  BatchView out = viewStride(out_dev, outStrideBytes, outCapacityWords);
-  return decodeImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum, numInBatch, nullptr, &in, &out,
-                    outCapacityWords, outSuccess_dev, outSize_dev, (hipStream_t)stream, errBatch, inBytes);
+  return decodeImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum, b, outSuccess_dev, outSize_dev, (hipStream_t)stream, errBatch);
 }
 
 // ---- info ------------------------------------------------------------------
@@ -2200,22 +2168,25 @@ int dgpu_ans_get_compressed_info_device(
   return DGPU_OK;
 }
 
+// (the *_get_compressed_info entry points: HOST array of archive pointers -> the array on the device)
+static int uploadArchivePointers(const void* const* in, uint32_t numInBatch, hipStream_t stream, DeviceBatch* d) {
+  Batch b;
+  b.inPtrs.resize(numInBatch);
+  for (uint32_t i = 0; i < numInBatch; ++i) b.inPtrs[i] = (uint64_t)(uintptr_t)in[i];
+  StreamLease streamLease(stream);
+  return resolveBatch(b, false, streamLease, d);  // (no out side: never stride views, see asStrideViews)
+}
+
 int dgpu_ans_get_compressed_info(
     void* temp_dev, size_t tempBytes, const void* const* in, uint32_t numInBatch,
     uint32_t* outSizes_dev, uint32_t* outChecksum_dev, void* stream) {
   if (numInBatch == 0 || (!outSizes_dev && !outChecksum_dev)) return DGPU_OK;
   (void)temp_dev;
   (void)tempBytes;
-  ParamLease lease;
-  HostParams hp;
-  hp.inPtrs.resize(numInBatch);
-  for (uint32_t i = 0; i < numInBatch; ++i) hp.inPtrs[i] = (uint64_t)(uintptr_t)in[i];
-  const uint64_t *inP = nullptr, *outP = nullptr;
-  const uint32_t* sz = nullptr;
-  int rc = uploadParams(lease, (hipStream_t)stream, hp, &inP, &outP, &sz);
+  DeviceBatch d;
+  int rc = uploadArchivePointers(in, numInBatch, (hipStream_t)stream, &d);
   if (rc) return rc;
-  return dgpu_ans_get_compressed_info_device((const void* const*)inP, numInBatch, outSizes_dev,
-                                             outChecksum_dev, stream);
+  return dgpu_ans_get_compressed_info_device((const void* const*)d.in.ptrs, numInBatch, outSizes_dev, outChecksum_dev, stream);
 }
 
 int dgpu_float_get_compressed_info_device(
@@ -2235,16 +2206,10 @@ int dgpu_float_get_compressed_info(
   if (numInBatch == 0 || (!outSizes_dev && !outTypes_dev && !outChecksum_dev)) return DGPU_OK;
   (void)temp_dev;
   (void)tempBytes;
-  ParamLease lease;
-  HostParams hp;
-  hp.inPtrs.resize(numInBatch);
-  for (uint32_t i = 0; i < numInBatch; ++i) hp.inPtrs[i] = (uint64_t)(uintptr_t)in[i];
-  const uint64_t *inP = nullptr, *outP = nullptr;
-  const uint32_t* sz = nullptr;
-  int rc = uploadParams(lease, (hipStream_t)stream, hp, &inP, &outP, &sz);
+  DeviceBatch d;
+  int rc = uploadArchivePointers(in, numInBatch, (hipStream_t)stream, &d);
   if (rc) return rc;
-  return dgpu_float_get_compressed_info_device((const void* const*)inP, numInBatch, outSizes_dev,
-                                               outTypes_dev, outChecksum_dev, stream);
+  return dgpu_float_get_compressed_info_device((const void* const*)d.in.ptrs, numInBatch, outSizes_dev, outTypes_dev, outChecksum_dev, stream);
 }
 
 // ---- float codec -------------------------------------------------------------
@@ -2252,42 +2217,23 @@ int dgpu_float_compress(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits,
     int useChecksum, uint32_t numInBatch, const void* const* in, const uint32_t* inSize,
     void* const* out, uint32_t* outSize_dev, void* stream) {
-  DGPU_REQUIRE(validFloatType(floatType), "floatType must be float16, bfloat16 or float32");
-  HostParams hp;
-  hp.inPtrs.resize(numInBatch);
-  hp.outPtrs.resize(numInBatch);
-  hp.sizes.resize(numInBatch);
-  uint32_t maxSize = 0;
-  const uint32_t wb = floatWordBytes(floatType);
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    DGPU_REQUIRE(((uintptr_t)in[i] % wb) == 0, "float input must be float-word aligned");
-    DGPU_REQUIRE(((uintptr_t)out[i] % 16) == 0, "compressed output must be 16-byte aligned");
-    hp.inPtrs[i] = (uint64_t)(uintptr_t)in[i];
-    hp.outPtrs[i] = (uint64_t)(uintptr_t)out[i];
-    hp.sizes[i] = inSize[i];
-    maxSize = std::max(maxSize, inSize[i]);
-  }
-  return floatCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum,
-                           numInBatch, hp, maxSize, outSize_dev, (hipStream_t)stream);
+  DGPU_REQUIRE(validFloatType(floatType), kMsgFloatType);
+  Batch b;
+  int rc = pointerBatch(&b, numInBatch, ptrSide(in, floatWordBytes(floatType), kMsgFloatIn), ptrSide(out, 16, kMsgCompOut), inSize);
+  if (rc) return rc;
+  return floatCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum, b, outSize_dev, (hipStream_t)stream);
 }
 
 int dgpu_float_compress_split_size(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits,
     int useChecksum, uint32_t numInBatch, const void* in_dev, const uint32_t* inSplitSizes,
     void* out_dev, uint32_t outStride, uint32_t* outSize_dev, void* stream) {
-  DGPU_REQUIRE(validFloatType(floatType), "floatType must be float16, bfloat16 or float32");
-  DGPU_REQUIRE(((uintptr_t)out_dev % 16) == 0 && (numInBatch <= 1 || outStride % 16 == 0),
-               "compressed output must be 16-byte aligned");
-  HostParams hp;
-  uint32_t maxSize = 0;
-  splitSizesToPointers(in_dev, inSplitSizes, numInBatch, floatWordBytes(floatType), &hp.inPtrs,
-                       &hp.sizes, &maxSize);
-  hp.outPtrs.resize(numInBatch);
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    hp.outPtrs[i] = (uint64_t)(uintptr_t)out_dev + (uint64_t)i * outStride;
-  }
-  return floatCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum,
-                           numInBatch, hp, maxSize, outSize_dev, (hipStream_t)stream);
+  DGPU_REQUIRE(validFloatType(floatType), kMsgFloatType);
+  Batch b;
+  int rc = splitBatch(&b, numInBatch, strideSide(in_dev, 0), inSplitSizes, floatWordBytes(floatType), 0u,
+                      strideSide(out_dev, outStride, 16, kMsgCompOut), false);
+  if (rc) return rc;
+  return floatCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum, b, outSize_dev, (hipStream_t)stream);
 }
 
 int dgpu_float_decompress(
@@ -2295,7 +2241,7 @@ int dgpu_float_decompress(
     int useChecksum, uint32_t numInBatch, const void* const* in, void* const* out,
     const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream,
     int32_t* errBatch) {
-  DGPU_REQUIRE(validFloatType(floatType), "floatType must be float16, bfloat16 or float32");
+  DGPU_REQUIRE(validFloatType(floatType), kMsgFloatType);
   return decodePointerCommon(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum,
                              numInBatch, in, out, outCapacity, outSuccess_dev, outSize_dev, stream,
                              errBatch);
@@ -2306,7 +2252,7 @@ int dgpu_float_decompress_split_size(
     int useChecksum, uint32_t numInBatch, const void* const* in, void* out_dev,
     const uint32_t* outSplitSizes, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream,
     int32_t* errBatch) {
-  DGPU_REQUIRE(validFloatType(floatType), "floatType must be float16, bfloat16 or float32");
+  DGPU_REQUIRE(validFloatType(floatType), kMsgFloatType);
   return decodeSplitCommon(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum,
                            numInBatch, in, out_dev, outSplitSizes, outSuccess_dev, outSize_dev,
                            stream, errBatch);

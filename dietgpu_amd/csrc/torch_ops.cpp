@@ -145,6 +145,43 @@ void validateStatus(const std::optional<at::Tensor>& outStatus, const std::optio
   }
 }
 
+template <typename T>
+T* ptrOrNull(const std::optional<at::Tensor>& t) { return t ? (T*)t->data_ptr() : nullptr; }
+
+// The tensor pairs of a decode call as the C ABI takes them: the checks of each pair (`extra(i)`: the caller's own, made
+// between them and the marshalling) and the four arrays.
+struct DecodeTensors {
+  std::vector<const void*> inPtrs;
+  std::vector<void*> outPtrs;
+  std::vector<uint32_t> outCapacity;
+  std::vector<uint32_t> inBytes;  // the tensors say how many bytes each archive may occupy
+};
+template <typename Extra>
+DecodeTensors marshalDecode(bool compressAsFloat, const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tOuts, int dev, Extra extra) {
+  const size_t n = tIns.size();
+  DecodeTensors m{std::vector<const void*>(n), std::vector<void*>(n), std::vector<uint32_t>(n), std::vector<uint32_t>(n)};
+  for (size_t i = 0; i < n; ++i) {
+    auto& tIn = tIns[i];
+    auto& tOut = tOuts[i];
+    TORCH_CHECK(tIn.device().is_cuda());
+    TORCH_CHECK(tIn.get_device() == dev);
+    TORCH_CHECK(tIn.is_contiguous());
+    TORCH_CHECK(tOut.device().is_cuda());
+    TORCH_CHECK(tOut.get_device() == dev);
+    TORCH_CHECK(tOut.is_contiguous());
+    TORCH_CHECK(tIn.dtype() == at::kByte);
+    if (compressAsFloat) floatTypeFromDtype(tOut.scalar_type());
+    extra(i);
+    m.inPtrs[i] = tIn.data_ptr();
+    m.inBytes[i] = (uint32_t)std::min<int64_t>(tIn.numel(), std::numeric_limits<uint32_t>::max());
+    m.outPtrs[i] = tOut.data_ptr();
+    auto cap = compressAsFloat ? tOut.numel() : tOut.numel() * tOut.element_size();
+    TORCH_CHECK((uint64_t)cap <= std::numeric_limits<uint32_t>::max());
+    m.outCapacity[i] = (uint32_t)cap;
+  }
+  return m;
+}
+
 }  // namespace
 
 // ---- size queries (DietGpu.cpp:116-143) --------------------------------------
@@ -297,42 +334,19 @@ int64_t decompress_data_impl(
   int dev = tIns.front().get_device();
   c10::hip::HIPGuard guard(dev);
   const size_t n = tIns.size();
-  std::vector<const void*> inPtrs(n);
-  std::vector<void*> outPtrs(n);
-  std::vector<uint32_t> outCapacity(n);
-  std::vector<uint32_t> inBytes(n);  // the tensors say how many bytes each archive may occupy
-  for (size_t i = 0; i < n; ++i) {
-    auto& tIn = tIns[i];
-    auto& tOut = tOuts[i];
-    TORCH_CHECK(tIn.device().is_cuda());
-    TORCH_CHECK(tIn.get_device() == dev);
-    TORCH_CHECK(tIn.is_contiguous());
-    TORCH_CHECK(tOut.device().is_cuda());
-    TORCH_CHECK(tOut.get_device() == dev);
-    TORCH_CHECK(tOut.is_contiguous());
-    TORCH_CHECK(tIn.dtype() == at::kByte);
-    if (compressAsFloat) floatTypeFromDtype(tOut.scalar_type());
-    inPtrs[i] = tIn.data_ptr();
-    inBytes[i] = (uint32_t)std::min<int64_t>(tIn.numel(), std::numeric_limits<uint32_t>::max());
-    outPtrs[i] = tOut.data_ptr();
-    auto cap = compressAsFloat ? tOut.numel() : tOut.numel() * tOut.element_size();
-    TORCH_CHECK((uint64_t)cap <= std::numeric_limits<uint32_t>::max());
-    outCapacity[i] = (uint32_t)cap;
-  }
+  DecodeTensors m = marshalDecode(compressAsFloat, tIns, tOuts, dev, [](size_t) {});
   validateStatus(outStatus, outSizes, (int64_t)n, dev);
   size_t used = 0;
   int32_t err = -1;
   if (compressAsFloat) {
     check(dgpu_float_decompress_bounded(tmp.ptr, tmp.bytes, &used, floatTypeFromDtype(tOuts[0].scalar_type()), precision(),
-                                checksum, (uint32_t)n, inPtrs.data(), inBytes.data(), outPtrs.data(), outCapacity.data(),
-                                outStatus ? (uint8_t*)outStatus->data_ptr() : nullptr,
-                                outSizes ? (uint32_t*)outSizes->data_ptr() : nullptr, streamOf(dev), &err),
+                                checksum, (uint32_t)n, m.inPtrs.data(), m.inBytes.data(), m.outPtrs.data(), m.outCapacity.data(),
+                                ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev), &err),
           "floatDecompress", true);
   } else {
     check(dgpu_ans_decode_batch_pointer_bounded(tmp.ptr, tmp.bytes, &used, precision(), checksum, (uint32_t)n,
-                                        inPtrs.data(), inBytes.data(), outPtrs.data(), outCapacity.data(),
-                                        outStatus ? (uint8_t*)outStatus->data_ptr() : nullptr,
-                                        outSizes ? (uint32_t*)outSizes->data_ptr() : nullptr, streamOf(dev), &err),
+                                        m.inPtrs.data(), m.inBytes.data(), m.outPtrs.data(), m.outCapacity.data(),
+                                        ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev), &err),
           "ansDecodeBatchPointer", false);
   }
   return (int64_t)used;
@@ -386,14 +400,12 @@ int64_t decompress_data_split_size(
     check(dgpu_float_decompress_split_size_bounded(tmp.ptr, tmp.bytes, &used, floatTypeFromDtype(tOut.scalar_type()),
                                            precision(), checksum, (uint32_t)numInBatch, inPtrs.data(), inBytes.data(),
                                            tOut.data_ptr(), splitSizes.data(),
-                                           outStatus ? (uint8_t*)outStatus->data_ptr() : nullptr,
-                                           outSizes ? (uint32_t*)outSizes->data_ptr() : nullptr, streamOf(dev), &err),
+                                           ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev), &err),
           "floatDecompressSplitSize", true);
   } else {
     check(dgpu_ans_decode_batch_split_size_bounded(tmp.ptr, tmp.bytes, &used, precision(), checksum, (uint32_t)numInBatch,
                                            inPtrs.data(), inBytes.data(), tOut.data_ptr(), splitSizes.data(),
-                                           outStatus ? (uint8_t*)outStatus->data_ptr() : nullptr,
-                                           outSizes ? (uint32_t*)outSizes->data_ptr() : nullptr, streamOf(dev), &err),
+                                           ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev), &err),
           "ansDecodeBatchSplitSize", false);
   }
   return (int64_t)used;
@@ -461,46 +473,26 @@ int64_t decompress_data_range(
   c10::hip::HIPGuard guard(dev);
   Temp tmp = tempOf(tempMem, dev);
   const size_t n = tIns.size();
-  std::vector<const void*> inPtrs(n);
-  std::vector<void*> outPtrs(n);
-  std::vector<uint32_t> outCapacity(n), inBytes(n), first(n), count(n);
-  for (size_t i = 0; i < n; ++i) {
-    auto& tIn = tIns[i];
-    auto& tOut = tOuts[i];
-    TORCH_CHECK(tIn.device().is_cuda());
-    TORCH_CHECK(tIn.get_device() == dev);
-    TORCH_CHECK(tIn.is_contiguous());
-    TORCH_CHECK(tOut.device().is_cuda());
-    TORCH_CHECK(tOut.get_device() == dev);
-    TORCH_CHECK(tOut.is_contiguous());
-    TORCH_CHECK(tIn.dtype() == at::kByte);
-    if (compressAsFloat) {
-      floatTypeFromDtype(tOut.scalar_type());
-      TORCH_CHECK(tOut.scalar_type() == tOuts[0].scalar_type());
-    }
+  std::vector<uint32_t> first(n), count(n);
+  DecodeTensors m = marshalDecode(compressAsFloat, tIns, tOuts, dev, [&](size_t i) {
+    if (compressAsFloat) TORCH_CHECK(tOuts[i].scalar_type() == tOuts[0].scalar_type());
     TORCH_CHECK(firstBlock[i] >= 0 && firstBlock[i] <= (int64_t)std::numeric_limits<uint32_t>::max(), "dietgpu: first_block out of range");
     first[i] = (uint32_t)firstBlock[i];
     const bool toEnd = numBlocks[i] < 0 || numBlocks[i] >= (int64_t)std::numeric_limits<uint32_t>::max();
     count[i] = toEnd ? std::numeric_limits<uint32_t>::max() : (uint32_t)numBlocks[i];
-    inPtrs[i] = tIn.data_ptr();
-    inBytes[i] = (uint32_t)std::min<int64_t>(tIn.numel(), std::numeric_limits<uint32_t>::max());
-    outPtrs[i] = tOut.data_ptr();
-    auto cap = compressAsFloat ? tOut.numel() : tOut.numel() * tOut.element_size();
-    TORCH_CHECK((uint64_t)cap <= std::numeric_limits<uint32_t>::max());
-    outCapacity[i] = (uint32_t)cap;
-  }
+  });
   validateStatus(outStatus, outSizes, (int64_t)n, dev);
   size_t used = 0;
-  uint8_t* status = outStatus ? (uint8_t*)outStatus->data_ptr() : nullptr;
-  uint32_t* sizes = outSizes ? (uint32_t*)outSizes->data_ptr() : nullptr;
+  uint8_t* status = ptrOrNull<uint8_t>(outStatus);
+  uint32_t* sizes = ptrOrNull<uint32_t>(outSizes);
   if (compressAsFloat) {
     check(dgpu_float_decompress_range(tmp.ptr, tmp.bytes, &used, floatTypeFromDtype(tOuts[0].scalar_type()), precision(), (uint32_t)n,
-                                      inPtrs.data(), inBytes.data(), first.data(), count.data(), outPtrs.data(),
-                                      outCapacity.data(), status, sizes, streamOf(dev)),
+                                      m.inPtrs.data(), m.inBytes.data(), first.data(), count.data(), m.outPtrs.data(),
+                                      m.outCapacity.data(), status, sizes, streamOf(dev)),
           "floatDecompressRange", true);
   } else {
-    check(dgpu_ans_decode_batch_pointer_range(tmp.ptr, tmp.bytes, &used, precision(), (uint32_t)n, inPtrs.data(), inBytes.data(),
-                                              first.data(), count.data(), outPtrs.data(), outCapacity.data(), status, sizes,
+    check(dgpu_ans_decode_batch_pointer_range(tmp.ptr, tmp.bytes, &used, precision(), (uint32_t)n, m.inPtrs.data(), m.inBytes.data(),
+                                              first.data(), count.data(), m.outPtrs.data(), m.outCapacity.data(), status, sizes,
                                               streamOf(dev)),
           "ansDecodeBatchPointerRange", false);
   }

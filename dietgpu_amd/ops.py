@@ -337,6 +337,34 @@ def _raise_checksum(rc, is_float):
     check(rc)
 
 
+def _decode_capacities(compress_as_float, ts_in, ts_out, dev, same_dtype=False):
+    """The per-tensor checks of a decode call -> the capacity of every output (words of floats, else bytes)."""
+    caps = []
+    for ti, to in zip(ts_in, ts_out):
+        _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous())
+        _check(to.is_cuda and to.get_device() == dev and to.is_contiguous())
+        _check(ti.dtype == torch.uint8)
+        if compress_as_float:
+            _float_type(to)
+            _check(not same_dtype or to.dtype == ts_out[0].dtype)
+        cap = to.numel() if compress_as_float else to.numel() * to.element_size()
+        _check(cap <= _U32_MAX)
+        caps.append(cap)
+    return caps
+
+
+def _header_info(compress_as_float, ts_in, tp, tb):
+    """-> (sizes, float types) of the archives as host lists, read from their headers (one synchronising copy)"""
+    n, device = len(ts_in), ts_in[0].device
+    sizes = torch.empty((n,), dtype=torch.int32, device=device)
+    types = torch.zeros((n,), dtype=torch.int32, device=device)
+    if compress_as_float:
+        check(lib().dgpu_float_get_compressed_info(tp, tb, _ptr_array(ts_in), n, _ptr(sizes), _ptr(types), None, _stream()))
+    else:
+        check(lib().dgpu_ans_get_compressed_info(tp, tb, _ptr_array(ts_in), n, _ptr(sizes), None, _stream()))
+    return sizes.tolist(), types.tolist()
+
+
 def decompress_data(compress_as_float, ts_in, ts_out, checksum=False, temp_mem=None,
                     out_status=None, out_decompressed_words=None, prob_bits=K_DEFAULT_PRECISION):
     """DietGpu.cpp:530-677 -> temp bytes used."""
@@ -346,16 +374,7 @@ def decompress_data(compress_as_float, ts_in, ts_out, checksum=False, temp_mem=N
     _check(len(ts_in) > 0)
     _check(len(ts_in) == len(ts_out))
     dev = ts_in[0].get_device()
-    caps = []
-    for ti, to in zip(ts_in, ts_out):
-        _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous())
-        _check(to.is_cuda and to.get_device() == dev and to.is_contiguous())
-        _check(ti.dtype == torch.uint8)
-        if compress_as_float:
-            _float_type(to)
-        cap = to.numel() if compress_as_float else to.numel() * to.element_size()
-        _check(cap <= _U32_MAX)
-        caps.append(cap)
+    caps = _decode_capacities(compress_as_float, ts_in, ts_out, dev)
     n = len(ts_in)
     _validate_status(out_status, out_decompressed_words, n, dev)
     with torch.cuda.device(dev):
@@ -432,16 +451,7 @@ def decompress_data_simple(compress_as_float, ts_in, checksum=False, temp_mem=67
         scratch = None
         if temp_mem is not None and temp_mem >= 256:  # kSDMAlignment, DietGpu.cpp:831-834
             scratch = torch.empty((temp_mem,), dtype=torch.uint8, device=device)
-        tp, tb = _temp(scratch, dev)
-        sizes = torch.empty((n,), dtype=torch.int32, device=device)
-        types = torch.zeros((n,), dtype=torch.int32, device=device)
-        if compress_as_float:
-            check(lib().dgpu_float_get_compressed_info(
-                tp, tb, _ptr_array(ts_in), n, _ptr(sizes), _ptr(types), None, _stream()))
-        else:
-            check(lib().dgpu_ans_get_compressed_info(
-                tp, tb, _ptr_array(ts_in), n, _ptr(sizes), None, _stream()))
-        hs, ht = sizes.tolist(), types.tolist()
+        hs, ht = _header_info(compress_as_float, ts_in, *_temp(scratch, dev))
         outs = []
         for i in range(n):
             if compress_as_float:
@@ -489,19 +499,9 @@ def decompress_data_range(compress_as_float, ts_in, ts_out, first_block, num_blo
         finally:
             torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
     dev = ts_in[0].get_device()
-    caps = []
     for f in first_block:
         _check(0 <= f <= _U32_MAX, "first_block out of range")
-    for ti, to in zip(ts_in, ts_out):
-        _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous())
-        _check(to.is_cuda and to.get_device() == dev and to.is_contiguous())
-        _check(ti.dtype == torch.uint8)
-        if compress_as_float:
-            _float_type(to)
-            _check(to.dtype == ts_out[0].dtype)
-        cap = to.numel() if compress_as_float else to.numel() * to.element_size()
-        _check(cap <= _U32_MAX)
-        caps.append(cap)
+    caps = _decode_capacities(compress_as_float, ts_in, ts_out, dev, same_dtype=True)
     n = len(ts_in)
     counts = [_U32_MAX if (c < 0 or c >= _U32_MAX) else c for c in num_blocks]
     _validate_status(out_status, out_decompressed_words, n, dev)
@@ -533,17 +533,12 @@ def _check_slice_args(compress_as_float, ts_in, dtype):
 
 def _archive_info(compress_as_float, ts_in, dtype):
     """-> (words of every archive, the dtype they decode to), read from the headers (one synchronising copy)"""
-    dev, device, n = ts_in[0].get_device(), ts_in[0].device, len(ts_in)
+    dev = ts_in[0].get_device()
     for t in ts_in:
         _check(t.get_device() == dev and t.is_contiguous() and t.dtype == torch.uint8)
     with torch.cuda.device(dev):
-        sizes = torch.empty((n,), dtype=torch.int32, device=device)
-        types = torch.zeros((n,), dtype=torch.int32, device=device)
-        if compress_as_float:
-            check(lib().dgpu_float_get_compressed_info(None, 0, _ptr_array(ts_in), n, _ptr(sizes), _ptr(types), None, _stream()))
-        else:
-            check(lib().dgpu_ans_get_compressed_info(None, 0, _ptr_array(ts_in), n, _ptr(sizes), None, _stream()))
-        hs, ht = [v & _U32_MAX for v in sizes.tolist()], types.tolist()
+        hs, ht = _header_info(compress_as_float, ts_in, None, 0)
+    hs = [v & _U32_MAX for v in hs]
     if not compress_as_float:
         return hs, torch.uint8
     for t in ht:
