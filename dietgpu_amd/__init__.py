@@ -14,6 +14,7 @@ from .ops import (  # noqa: F401
     compress_data_split_size,
     block_cover,
     decompress_data,
+    decompress_data_accumulate,
     decompress_data_range,
     decompress_data_simple,
     decompress_data_slice,

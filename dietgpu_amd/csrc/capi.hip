@@ -1827,7 +1827,51 @@ int decodeRangeImpl(
   d.numBlocks = dev.work + B;
   d.workMap = dev.work + 2u * (size_t)B;
   d.numListed = 0;
-  return launchVariant(decoderVariant(P, ft, tileBlocks, true), dim3(numTiles), stream, d);
+  return launchVariant(decoderVariant(P, ft, tileBlocks, DecodeForm::kRanged), dim3(numTiles), stream, d);
+}
+
+// Decode-accumulate (k_ans_decode_accum): every archive widened to float32 and stored to (accumulate == 0) or added into
+// (1) its float32 accumulator.  One geometry per call, from the largest capacity (16-block tiles, 4-block tiles for
+// capacities of up to 8 blocks); the grid is the rectangle of a whole decode, or the tile list when the capacities
+// differ widely.  No temp memory, no host synchronisation.
+int decodeAccumulateImpl(
+    size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, const void* const* in, const uint32_t* inBytes,
+    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+  DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
+  DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "decode-accumulate: accumulate must be 0 or 1");
+  bool done;
+  int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
+  if (done) return rc;
+  DGPU_REQUIRE(in && inBytes && out && outCapacity, "decode-accumulate: null array with numInBatch > 0");
+  Batch b;
+  rc = pointerBatch(&b, B, ptrSide(in, 16, kMsgCompIn), ptrSide(out, 4, "decode-accumulate: accumulators must be 4-byte aligned"), outCapacity,
+                    inBytes);
+  if (rc) return rc;
+  // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
+  DGPU_REQUIRE(b.maxSize <= 0xfffff000u, "decode-accumulate: outCapacity must not exceed 0xfffff000");
+  const uint32_t maxBlocks = divUp(b.maxSize, kBlockSize);
+  const uint32_t tileBlocks = maxBlocks <= 2u * kDecBlocksPerSmallTile ? kDecBlocksPerSmallTile : kDecBlocksPerTile;  // as decTileBlocksFor
+  const uint32_t maxTiles = std::max(1u, divUp(maxBlocks, tileBlocks));
+  StreamLease streamLease(stream);
+  DeviceBatch dev;
+  uint32_t numListedTiles = 0;
+  rc = resolveBatch(b, true, streamLease, &dev, [&] {
+    if (planTileList(b.sizes, tileBlocks * kBlockSize, maxTiles, 1u, &b.work)) numListedTiles = (uint32_t)b.work.size();
+  });
+  if (rc) return rc;
+  DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
+  d.accumulate = (uint32_t)accumulate;
+  d.maxTiles = maxTiles;
+  d.order = decodeOrder(B);
+  d.workMap = nullptr;
+  d.numListed = 0;
+  uint32_t grid = (d.order == kDecOrderXcd ? roundUp(B, 8u) : B) * maxTiles;
+  if (dev.work && numListedTiles) {
+    d.order = kDecOrderMap;
+    d.workMap = dev.work;
+    grid = numListedTiles;
+  }
+  return launchVariant(decoderVariant(P, ft, tileBlocks, DecodeForm::kAccum), dim3(grid), stream, d);
 }
 
 }  // namespace
@@ -2114,6 +2158,17 @@ int dgpu_float_decompress_range(
   DGPU_REQUIRE(validFloatType(floatType), kMsgFloatType);
   return decodeRangeImpl(tempUsed, floatType, probBits, numInBatch, in, inBytes, firstBlock, numBlocks, out, outCapacity,
                          outSuccess_dev, outSize_dev, (hipStream_t)stream);
+}
+
+// ---- decode-accumulate (no upstream equivalent) ----------------------------------
+int dgpu_float_decode_accumulate(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, const void* const* in, const uint32_t* inBytes, void* const* out, const uint32_t* outCapacity,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream) {
+  (void)temp_dev;
+  (void)tempBytes;
+  return decodeAccumulateImpl(tempUsed, floatType, probBits, accumulate, numInBatch, in, inBytes, out, outCapacity,
+                              outSuccess_dev, outSize_dev, (hipStream_t)stream);
 }
 
 // ---- float stride batches with capacities on both sides (the compressed collectives) --------------------

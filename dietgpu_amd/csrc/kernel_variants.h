@@ -112,13 +112,23 @@ inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, boo
 
 // The decoder of tiles of `tileBlocks` blocks; batches whose every capacity is one block go to k_ans_decode_pair (two
 // elements per wavefront, kernels_pairs.h).
-//   * ranged: k_ans_decode_range, which decodes a block range of every element; it exists for 16- and 4-block tiles
-//     (a range of one or two blocks takes the 4-block form).
-inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, bool ranged = false) {
+//   * DecodeForm::kRanged: k_ans_decode_range, which decodes a block range of every element; it exists for 16- and
+//     4-block tiles (a range of one or two blocks takes the 4-block form);
+//   * DecodeForm::kAccum: k_ans_decode_accum, which widens to float32 and stores to / adds into float32 accumulators;
+//     float types only (raw bytes: the float32 form), 16- and 4-block tiles.
+inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, DecodeForm form = DecodeForm::kWhole) {
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> DecodeVariant {
     constexpr int kP = decltype(p)::value;
     constexpr uint32_t kFT = decltype(f)::value;
-    if (ranged) {
+    if (form == DecodeForm::kAccum) {
+      auto tiled = [](auto tb) -> DecodeVariant {
+        constexpr uint32_t kTB = decltype(tb)::value;
+        constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
+        return {k_ans_decode_accum<kP, kAccFT, kTB>, decThreads(kTB), decLdsBytes(kP, kAccFT, kTB), "k_ans_decode_accum"};
+      };
+      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
+    }
+    if (form == DecodeForm::kRanged) {
       auto tiled = [](auto tb) -> DecodeVariant {
         constexpr uint32_t kTB = decltype(tb)::value;
         return {k_ans_decode_range<kP, kFT, kTB>, decThreads(kTB), decLdsBytes(kP, kFT, kTB), "k_ans_decode_range"};

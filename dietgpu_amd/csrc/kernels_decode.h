@@ -64,6 +64,8 @@ struct DecodeArgs {
   // k_ans_decode_range only (see decodeTile): blocks [firstBlock[b], firstBlock[b] + numBlocks[b]) of element b
   const uint32_t* firstBlock = nullptr;  // [B]
   const uint32_t* numBlocks = nullptr;   // [B]; 0xffffffff = to the end of the element
+  // k_ans_decode_accum only: out holds float32 accumulators; 0: acc = decoded (the accumulator is not read), 1: acc += decoded
+  uint32_t accumulate = 0;
 };
 __device__ __forceinline__ uint64_t decodeInBytes(const DecodeArgs& a, uint32_t b) {
   return a.inBytes ? (uint64_t)a.inBytes[b] : (a.uniformInBytes ? (uint64_t)a.uniformInBytes : ~0ull);
@@ -144,6 +146,7 @@ struct RowSink<0> {  // raw bytes (BatchWriter, BatchProvider.cuh:16-37)
     out = outBase + first + hl;
   }
   typedef uint32_t Pre;
+  typedef uint2 GroupPre;
   __device__ __forceinline__ uint32_t prefetch(uint32_t) const { return 0; }
   __device__ __forceinline__ void store(uint32_t row, uint32_t e0, uint32_t) const {
     out[row * 32u] = (uint8_t)(e0 >> 24);  // 32-byte row pieces: left to the L2 to merge
@@ -174,9 +177,12 @@ struct RowSink<kFloat16> {  // word = comp << 8 | nonComp
     nc = archive + 16u + first + hl;
   }
   typedef uint32_t Pre;
+  typedef uint2 GroupPre;
   __device__ __forceinline__ uint32_t prefetch(uint32_t row) const { return nc[row * 32u]; }
+  // the joined word in the TOP half
+  static __device__ __forceinline__ uint32_t joinWord(uint32_t e0, uint32_t r) { return joinBytes(e0, r); }  // [sym][nc][0000 pdf]
   __device__ __forceinline__ void store(uint32_t row, uint32_t e0, uint32_t r) const {
-    const uint32_t v = joinBytes(e0, r);  // [sym][nc][0000 pdf]
+    const uint32_t v = joinWord(e0, r);
     streamStore<kNtDecStores>(&out[row * 32u], (uint16_t)(v >> 16));
   }
   // wide variant (see decodeBlock): rows stage {sym, 0}; a lane joins its 8 consecutive words with the 8
@@ -186,13 +192,18 @@ struct RowSink<kFloat16> {  // word = comp << 8 | nonComp
   __device__ __forceinline__ void stageRow(uint32_t xpose, uint32_t j, uint32_t hl, uint32_t e0) const {
     *(LdsU16w*)(uintptr_t)(xpose + (j * 32u + hl) * 2u) = (uint16_t)(e0 >> 16);
   }
-  __device__ __forceinline__ void flushGroup(uint32_t xpose, uint32_t g, uint32_t hl, uint2 ncb) const {
+  // the lane's 8 consecutive words of the group, two per dword
+  static __device__ __forceinline__ u32x4w joinGroup(uint32_t xpose, uint32_t hl, uint2 ncb) {
     const u32x4w v = *(const LdsU4w*)(uintptr_t)(xpose + hl * 16u);
     u32x4w o;
     o.x = __builtin_amdgcn_perm(v.x, ncb.x, 0x07010500u);  // {nc0, sym0, nc1, sym1}
     o.y = __builtin_amdgcn_perm(v.y, ncb.x, 0x07030502u);
     o.z = __builtin_amdgcn_perm(v.z, ncb.y, 0x07010500u);
     o.w = __builtin_amdgcn_perm(v.w, ncb.y, 0x07030502u);
+    return o;
+  }
+  __device__ __forceinline__ void flushGroup(uint32_t xpose, uint32_t g, uint32_t hl, uint2 ncb) const {
+    const u32x4w o = joinGroup(xpose, hl, ncb);
     u32x4w* dst = (u32x4w*)(out - hl + g * 256u + hl * 8u);
     if (kNtDecStores) __builtin_nontemporal_store(o, dst);
     else *dst = o;
@@ -208,10 +219,15 @@ struct RowSink<kBFloat16> {  // word = (comp << 8 | nonComp) >> 1 | (nonComp & 1
     nc = archive + 16u + first + hl;
   }
   typedef uint32_t Pre;
+  typedef uint2 GroupPre;
   __device__ __forceinline__ uint32_t prefetch(uint32_t row) const { return nc[row * 32u]; }
-  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, uint32_t r) const {
+  // the joined word in the TOP half
+  static __device__ __forceinline__ uint32_t joinWord(uint32_t e0, uint32_t r) {
     const uint32_t lo = joinBytes(e0, r);                                 // [sym][nc][0000 pdf]
-    const uint32_t v = __builtin_amdgcn_alignbit(r, lo, 1);     // (lo >> 1) | (r << 31)
+    return __builtin_amdgcn_alignbit(r, lo, 1);                 // (lo >> 1) | (r << 31)
+  }
+  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, uint32_t r) const {
+    const uint32_t v = joinWord(e0, r);
     streamStore<kNtDecStores>(&out[row * 32u], (uint16_t)(v >> 16));                    // [sign][exp][mant7]
   }
   // wide variant: as fp16, then every 16-bit half {exp, nc} rotated right by one (sign to the top):
@@ -229,13 +245,18 @@ struct RowSink<kBFloat16> {  // word = (comp << 8 | nonComp) >> 1 | (nonComp & 1
     asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(0x80008000u), "v"(shifted));
     return r;
   }
-  __device__ __forceinline__ void flushGroup(uint32_t xpose, uint32_t g, uint32_t hl, uint2 ncb) const {
+  // the lane's 8 consecutive words of the group, two per dword
+  static __device__ __forceinline__ u32x4w joinGroup(uint32_t xpose, uint32_t hl, uint2 ncb) {
     const u32x4w v = *(const LdsU4w*)(uintptr_t)(xpose + hl * 16u);
     u32x4w o;
     o.x = rotrHalves(__builtin_amdgcn_perm(v.x, ncb.x, 0x07010500u));
     o.y = rotrHalves(__builtin_amdgcn_perm(v.y, ncb.x, 0x07030502u));
     o.z = rotrHalves(__builtin_amdgcn_perm(v.z, ncb.y, 0x07010500u));
     o.w = rotrHalves(__builtin_amdgcn_perm(v.w, ncb.y, 0x07030502u));
+    return o;
+  }
+  __device__ __forceinline__ void flushGroup(uint32_t xpose, uint32_t g, uint32_t hl, uint2 ncb) const {
+    const u32x4w o = joinGroup(xpose, hl, ncb);
     u32x4w* dst = (u32x4w*)(out - hl + g * 256u + hl * 8u);
     if (kNtDecStores) __builtin_nontemporal_store(o, dst);
     else *dst = o;
@@ -253,6 +274,7 @@ struct RowSink<kFloat32> {  // rotr32(comp << 24 | nonComp24, 1)
     nc1 = archive + 16u + 2u * (size_t)roundUp(floatSize, 8u) + first + hl;
   }
   typedef uint32_t Pre;
+  typedef uint2 GroupPre;
   __device__ __forceinline__ uint32_t prefetch(uint32_t row) const {
     return ((uint32_t)nc1[row * 32u] << 16) | nc2[row * 32u];
   }
@@ -260,7 +282,134 @@ struct RowSink<kFloat32> {  // rotr32(comp << 24 | nonComp24, 1)
     const uint32_t v = (e0 & 0xff000000u) | r;
     streamStore<kNtDecStores>(&out[row * 32u], (uint32_t)__builtin_amdgcn_alignbit(v, v, 1));
   }
+  // the same word for AccumSink (store() keeps its own text: routing it through here reorders its row loop's schedule)
+  static __device__ __forceinline__ uint32_t joinWord(uint32_t e0, uint32_t r) {
+    const uint32_t v = (e0 & 0xff000000u) | r;
+    return (uint32_t)__builtin_amdgcn_alignbit(v, v, 1);
+  }
   static constexpr uint32_t kXposeBytes = 0;  // 128-byte row pieces already: no transposition
+  __device__ __forceinline__ uint2 prefetchGroup(uint32_t, uint32_t) const { return make_uint2(0, 0); }
+  __device__ __forceinline__ void stageRow(uint32_t, uint32_t, uint32_t, uint32_t) const {}
+  __device__ __forceinline__ void flushGroup(uint32_t, uint32_t, uint32_t, uint2) const {}
+};
+
+// ---------------------------------------------------------------------------
+// Accumulating sinks (k_ans_decode_accum): the interface of RowSink<FT>, but the joined word is widened to float32 and
+// goes to a float32 accumulator: acc = widened (accumulate == 0: the accumulator is not read) or acc += widened -- one
+// IEEE float32 add, round to nearest even, denormals kept, nothing to contract it with.  Widening is exact: fp16 ->
+// v_cvt_f32_f16 (fp16 denormals become float32 normals), bf16 -> word << 16, fp32 as it is.  `accumulate` is uniform
+// over the launch.  The accumulator words a lane adds to are requested where RowSink requests the non-compressed bytes
+// of the same rows -- two 8-row groups ahead on the wide path, one otherwise -- and travel with them (GroupPre / Pre),
+// so the row loop does not wait for them.  Wide path (16-bit types): a lane's 8 consecutive words leave as 32
+// contiguous bytes (two 16-byte stores) where RowSink leaves 16.
+template <uint32_t FT>
+__device__ __forceinline__ float accWiden16(uint32_t h);  // h: the 16-bit word in the LOW half
+template <>
+__device__ __forceinline__ float accWiden16<kFloat16>(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }
+template <>
+__device__ __forceinline__ float accWiden16<kBFloat16>(uint32_t h) { return __builtin_bit_cast(float, h << 16); }
+// (__fadd_rn: never fused, whatever the contraction mode of the translation unit)
+__device__ __forceinline__ uint32_t accAdd(uint32_t acc, float v) { return __builtin_bit_cast(uint32_t, __fadd_rn(__builtin_bit_cast(float, acc), v)); }
+typedef u32x4w u32x4w4 __attribute__((aligned(4)));  // accumulators are float-aligned only
+
+struct AccumPre {  // one row: the non-compressed byte(s) and the accumulator word
+  uint32_t r, acc;
+  __device__ __forceinline__ AccumPre() = default;
+  __device__ __forceinline__ AccumPre(uint32_t) : r(0), acc(0) {}
+};
+struct AccumGroupPre {  // one 8-row group of a lane: 8 non-compressed bytes and 8 accumulator words
+  uint2 nc;
+  u32x4w a0, a1;
+};
+
+template <uint32_t FT>
+struct AccumSink {  // kFloat16 / kBFloat16
+  static_assert(FT == kFloat16 || FT == kBFloat16, "");
+  float* out;
+  const uint8_t* nc;
+  uint32_t accumulate;
+  __device__ __forceinline__ void init(uint8_t* outBase, const uint8_t* archive, uint32_t, size_t first, uint32_t hl) {
+    out = (float*)outBase + first + hl;
+    nc = archive + 16u + first + hl;
+  }
+  typedef AccumPre Pre;
+  typedef AccumGroupPre GroupPre;
+  __device__ __forceinline__ AccumPre prefetch(uint32_t row) const {
+    AccumPre p(0);
+    p.r = nc[row * 32u];
+    if (accumulate) p.acc = *(const uint32_t*)&out[row * 32u];
+    return p;
+  }
+  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, const AccumPre& p) const {
+    const float v = accWiden16<FT>(RowSink<FT>::joinWord(e0, p.r) >> 16);
+    const uint32_t o = accumulate ? accAdd(p.acc, v) : __builtin_bit_cast(uint32_t, v);
+    streamStore<kNtDecStores>((uint32_t*)&out[row * 32u], o);
+  }
+  static constexpr uint32_t kXposeBytes = 512;
+  __device__ __forceinline__ AccumGroupPre prefetchGroup(uint32_t g, uint32_t hl) const {
+    AccumGroupPre p;
+    p.nc = decLoad8(nc - hl + g * 256u + hl * 8u);
+    p.a0 = p.a1 = u32x4w{0u, 0u, 0u, 0u};
+    if (accumulate) {
+      const u32x4w4* src = (const u32x4w4*)(out - hl + g * 256u + hl * 8u);
+      p.a0 = src[0];
+      p.a1 = src[1];
+    }
+    return p;
+  }
+  __device__ __forceinline__ void stageRow(uint32_t xpose, uint32_t j, uint32_t hl, uint32_t e0) const {
+    *(LdsU16w*)(uintptr_t)(xpose + (j * 32u + hl) * 2u) = (uint16_t)(e0 >> 16);
+  }
+  __device__ __forceinline__ void flushGroup(uint32_t xpose, uint32_t g, uint32_t hl, const AccumGroupPre& p) const {
+    const u32x4w w = RowSink<FT>::joinGroup(xpose, hl, p.nc);
+    float v[8];
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+      v[2u * k] = accWiden16<FT>(w[k] & 0xffffu);
+      v[2u * k + 1u] = accWiden16<FT>(w[k] >> 16);
+    }
+    u32x4w o0, o1;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+      o0[k] = accumulate ? accAdd(p.a0[k], v[k]) : __builtin_bit_cast(uint32_t, v[k]);
+      o1[k] = accumulate ? accAdd(p.a1[k], v[4u + k]) : __builtin_bit_cast(uint32_t, v[4u + k]);
+    }
+    u32x4w4* dst = (u32x4w4*)(out - hl + g * 256u + hl * 8u);
+    if (kNtDecStores) {
+      __builtin_nontemporal_store(o0, &dst[0]);
+      __builtin_nontemporal_store(o1, &dst[1]);
+    } else {
+      dst[0] = o0;
+      dst[1] = o1;
+    }
+  }
+};
+
+template <>
+struct AccumSink<kFloat32> {  // row-wise, as RowSink<kFloat32>: 128-byte pieces already
+  float* out;
+  const uint16_t* nc2;
+  const uint8_t* nc1;
+  uint32_t accumulate;
+  __device__ __forceinline__ void init(uint8_t* outBase, const uint8_t* archive, uint32_t floatSize, size_t first, uint32_t hl) {
+    out = (float*)outBase + first + hl;
+    nc2 = (const uint16_t*)(archive + 16u) + first + hl;
+    nc1 = archive + 16u + 2u * (size_t)roundUp(floatSize, 8u) + first + hl;
+  }
+  typedef AccumPre Pre;
+  typedef uint2 GroupPre;
+  __device__ __forceinline__ AccumPre prefetch(uint32_t row) const {
+    AccumPre p(0);
+    p.r = ((uint32_t)nc1[row * 32u] << 16) | nc2[row * 32u];
+    if (accumulate) p.acc = *(const uint32_t*)&out[row * 32u];
+    return p;
+  }
+  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, const AccumPre& p) const {
+    const uint32_t w = RowSink<kFloat32>::joinWord(e0, p.r);
+    const uint32_t o = accumulate ? accAdd(p.acc, __builtin_bit_cast(float, w)) : w;
+    streamStore<kNtDecStores>((uint32_t*)&out[row * 32u], o);
+  }
+  static constexpr uint32_t kXposeBytes = 0;
   __device__ __forceinline__ uint2 prefetchGroup(uint32_t, uint32_t) const { return make_uint2(0, 0); }
   __device__ __forceinline__ void stageRow(uint32_t, uint32_t, uint32_t, uint32_t) const {}
   __device__ __forceinline__ void flushGroup(uint32_t, uint32_t, uint32_t, uint2) const {}
@@ -338,13 +487,15 @@ __host__ __device__ constexpr uint32_t decLdsBytes(int P, uint32_t ft, uint32_t 
 // of following it (k_ans_decode: header -> {pdf, block descriptor, lane states} -> {compressed words, first
 // non-compressed bytes} was a chain of four dependent round trips at the start of every workgroup; on cold buffers
 // that is 10-15 % of a workgroup's life).  Held in registers across the build; valid for whole-block staging only.
-struct DecodePre {
-  uint4 words[4];  // the block's compressed words, 16 bytes per lane and k (kNoRing)
-  uint2 nc[2];     // non-compressed bytes of the last two groups (join at the flush)
+template <typename GroupPre>
+struct DecodePreOf {
+  uint4 words[4];   // the block's compressed words, 16 bytes per lane and k (kNoRing)
+  GroupPre nc[2];   // non-compressed bytes of the last two groups (join at the flush); AccumSink: with their accumulator words
 };
-template <uint32_t FT>
-__device__ __forceinline__ void decodePrefetch(DecodePre& pre, const uint8_t* __restrict__ gwords, uint32_t numWords,
-                                               const RowSink<FT>& sink, uint32_t hl, bool wide) {
+typedef DecodePreOf<uint2> DecodePre;
+template <uint32_t FT, typename Sink>
+__device__ __forceinline__ void decodePrefetch(DecodePreOf<typename Sink::GroupPre>& pre, const uint8_t* __restrict__ gwords, uint32_t numWords,
+                                               const Sink& sink, uint32_t hl, bool wide) {
   const uint32_t paddedBytes = roundUp(numWords, kBlockAlignWords) * 2u;
 #pragma unroll
   for (uint32_t k = 0; k < 4u; ++k) {
@@ -352,7 +503,7 @@ __device__ __forceinline__ void decodePrefetch(DecodePre& pre, const uint8_t* __
     pre.words[k] = make_uint4(0, 0, 0, 0);
     if (off < paddedBytes) pre.words[k] = decLoad16(gwords + off);
   }
-  pre.nc[0] = pre.nc[1] = make_uint2(0, 0);
+  pre.nc[0] = pre.nc[1] = typename Sink::GroupPre();
   if (wide) {
     pre.nc[0] = sink.prefetchGroup(kRowsPerBlock / 8u - 1u, hl);
     pre.nc[1] = sink.prefetchGroup(kRowsPerBlock / 8u - 2u, hl);
@@ -366,7 +517,7 @@ __device__ __forceinline__ void decodePrefetch(DecodePre& pre, const uint8_t* __
 // them in which every lane of a half that has a block holds a symbol: those run the straight-line step with the wide
 // stores.  `n` = symbols of this half's block (0 with kIdleUpper: the upper half has none).
 template <int P, uint32_t FT, bool kFull, bool kWide = false, bool kIdleUpper = false, bool kCompact = false, bool kNoRing = false,
-          bool kPre = false, bool kTail = false>
+          bool kPre = false, bool kTail = false, typename Sink = RowSink<FT>>
 __device__ __forceinline__ void decodeBlock(
     uint32_t xpose,                // kWide: LDS address of this half's transposition buffer
     uint32_t state,
@@ -376,10 +527,10 @@ __device__ __forceinline__ void decodeBlock(
     uint32_t numWords,
     uint32_t ringBase,             // LDS address of this half's 2 KiB ring (multiple of 2048)
     const void* __restrict__ lutRaw, // LDS: uint2 entries, or uint32 entries (kCompact)
-    const RowSink<FT>& sink,
+    const Sink& sink,              // RowSink<FT>, or AccumSink<FT>
     uint32_t hl,
     bool upper,
-    const DecodePre* pre = nullptr,  // kPre: the staging loads were issued by the caller (decodePrefetch)
+    const DecodePreOf<typename Sink::GroupPre>* pre = nullptr,  // kPre: the staging loads were issued by the caller (decodePrefetch)
     uint32_t topRows = 0) {          // kTail: rows above the `groups` whole groups (wave-uniform)
   static_assert(!kPre || (kNoRing && kFull), "");
   static_assert(!kTail || (kFull && !kPre), "");
@@ -456,7 +607,8 @@ __device__ __forceinline__ void decodeBlock(
   // lanes that need to renormalise keep it.
   // wave-uniform positions (SGPRs): unread words of the lower / upper half's block; kNoRing: plus the LDS word
   // address of the block's staging area, so that (position + rank) << 1 IS the LDS address
-  typedef typename RowSink<FT>::Pre Pre;
+  typedef typename Sink::Pre Pre;
+  typedef typename Sink::GroupPre GroupPre;
   uint32_t sLo = 0, sHi = 0;
   // an idle upper half follows the lower half's addresses (in bounds; its words are never used)
   int upperSel = (upper && !kIdleUpper) ? 1 : 0;
@@ -495,7 +647,7 @@ __device__ __forceinline__ void decodeBlock(
     constexpr bool F = decltype(fullTag)::value;
     constexpr bool kJoinAtFlush = F && kWide;
     Pre preCur[kGroupRows], preNext[kGroupRows];
-    uint2 ncCur = make_uint2(0, 0), ncNext = make_uint2(0, 0), ncNext2 = make_uint2(0, 0);
+    GroupPre ncCur = GroupPre(), ncNext = GroupPre(), ncNext2 = GroupPre();
     if (kJoinAtFlush) {
       if (kPre) {
         ncCur = pre->nc[0];
@@ -585,7 +737,7 @@ __device__ __forceinline__ void decodeBlock(
 }
 
 // One workgroup of the tiled decoder: 32 threads per block of the tile (512 or 128), LDS = word rings + 64-bit LUT.
-// The body of k_ans_decode (kRanged = false) and of k_ans_decode_range (kRanged = true), below.
+// The body of k_ans_decode (DecodeForm::kWhole), k_ans_decode_range (kRanged) and k_ans_decode_accum (kAccum), below.
 //
 // kRanged: blocks [firstBlock[b], firstBlock[b] + numBlocks[b]) of element b, clipped to the element's end, and block
 // firstBlock + k goes to out + k * 4096 words: the output buffer holds the range, not the element.
@@ -603,8 +755,18 @@ __device__ __forceinline__ void decodeBlock(
 //     blocks and their slices of the non-compressed plane(s).  A checksum in the archive is ignored.
 //   * An element with numBlocks == 0 has no tile; workgroup 0 of the grid reports it (size 0, success) without reading
 //     its archive.  A call of nothing but such elements lists one entry whose element index is not below numInBatch.
-template <int P, uint32_t FT, uint32_t kTileBlocks, bool kRanged>
+//
+// kAccum: a whole bounded decode whose words are widened to float32 and stored to / added into the float32 accumulator
+// a.out.ptr(b) (AccumSink; capacities in float words; float types only).  Row loop, ring, LUT build, checks, success and
+// outSize are those of the whole decode, with one difference: EVERY tile makes tile 0's check of all the element's block
+// descriptors (8 bytes per block, from the L2, in the round trip of the tile's own descriptor), and no tile of an element
+// with a malformed descriptor stores -- a failing element leaves its accumulator as it was.
+enum class DecodeForm { kWhole, kRanged, kAccum };
+template <int P, uint32_t FT, uint32_t kTileBlocks, DecodeForm kForm>
 __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
+  constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccum = kForm == DecodeForm::kAccum;
+  static_assert(!kAccum || FT != 0u, "accumulating decode: float archives only");
+  using Sink = std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32>, RowSink<FT>>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks);
   // the LUT-build scratch (cdf, pdf: 2 KiB, read while the LUT is stored) sits in the ring area
   static_assert(kTileBlocks * kRingBytes >= 2048u, "");
@@ -740,7 +902,10 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   // tile 0 vouches for the whole element (kRanged: the whole range; it alone writes outSuccess); its loads are
   // issued here and checked after the LUT build
   bool allBlocksOk = true;
-  if (tile == 0) {
+  if constexpr (kAccum) {
+    // every tile vouches for the whole element (see above); the loads do not wait for each other
+    for (uint32_t i = tid; i < endBlock; i += kDecThreads) allBlocksOk = blockOk(i, blockWords[i]) & allBlocksOk;
+  } else if (tile == 0) {
     for (uint32_t i = rFirst + tid; i < endBlock; i += kDecThreads) allBlocksOk = allBlocksOk && blockOk(i, blockWords[i]);
   }
 
@@ -769,8 +934,10 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
     }
   }
   const uint8_t* gwords = ans + ansOverhead(nb) + 2u * (size_t)start;
-  RowSink<FT> sink;
-  // (a half without a block points at its wave's first block: its prefetches must stay inside the archive)
+  Sink sink;
+  if constexpr (kAccum) sink.accumulate = a.accumulate;
+  // (a half without a block points at its wave's first block: its prefetches must stay inside the archive -- kAccum:
+  // and inside the accumulator)
   uint32_t sinkBlock = haveBlock ? block : (block & ~1u);
   if constexpr (kRanged) sinkBlock = haveBlock ? block : tileFirst + (hw & ~1u);
   sink.init(a.out.ptr(b), archive, floatSize, (size_t)sinkBlock * kBlockSize, hl);
@@ -785,11 +952,12 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   const uint32_t wSecond = __shfl(numWords, 32, 64);
   const bool noRing = wFirst <= kRingBytes / 2u && wSecond <= kRingBytes / 2u;
   // (the wide stores cover whole 8-row groups of words that exist; they take any word-aligned output element)
-  const bool wide = decXposeBytes(P, FT, kTileBlocks) != 0 && (((uintptr_t)a.out.ptr(b)) & (decOutWordBytes(FT) - 1u)) == 0;
+  // (kAccum: accumulators are float-aligned, the host checks it)
+  const bool wide = decXposeBytes(P, FT, kTileBlocks) != 0 && (kAccum || (((uintptr_t)a.out.ptr(b)) & (decOutWordBytes(FT) - 1u)) == 0);
   const bool fullPair = nFirst == kBlockSize && nSecond == kBlockSize;
   // one full block in the wave (odd block counts): fast path with an idle upper half
   const bool fullSingle = nFirst == kBlockSize && nSecond == 0u;
-  DecodePre pre;
+  DecodePreOf<typename Sink::GroupPre> pre;
   if ((fullPair || fullSingle) && noRing) decodePrefetch<FT>(pre, gwords, numWords, sink, hl, wide);
 
   // Decode LUT, built by the workgroup itself from the archive's pdf table (no
@@ -843,6 +1011,9 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
       if (a.outSize) a.outSize[b] = kRanged ? rangeWords(total) : total;
     }
     if (!pdfOk || tileFirst >= endBlock) return;  // uniform
+    if constexpr (kAccum) {
+      if (!blocksOk) return;  // uniform
+    }
     if constexpr (kScanLut) {
       // mark[cdf[s]] = s for every present symbol; sym(x) = the largest mark at or below x (cdfs ascend with
       // the symbol; slot 0 belongs to the first present symbol, so "no mark" = 0 never surfaces)
@@ -977,14 +1148,21 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
 // grid = the (element, tile) pairs in the order of DecodeArgs::order
 template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeArgs a) {
-  decodeTile<P, FT, kTileBlocks, false>(a);
+  decodeTile<P, FT, kTileBlocks, DecodeForm::kWhole>(a);
 }
 
 // Ranged form: grid = the listed tiles of the ranges (kDecOrderMap; DecodeArgs::firstBlock / numBlocks / inBytes set).
 // Built for 16- and 4-block tiles.
 template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_range(DecodeArgs a) {
-  decodeTile<P, FT, kTileBlocks, true>(a);
+  decodeTile<P, FT, kTileBlocks, DecodeForm::kRanged>(a);
+}
+
+// Accumulating form: grid and order as k_ans_decode; DecodeArgs::out holds float32 accumulators, DecodeArgs::accumulate
+// says whether they are added to or overwritten.  Built for the float types, 16- and 4-block tiles.
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_accum(DecodeArgs a) {
+  decodeTile<P, FT, kTileBlocks, DecodeForm::kAccum>(a);
 }
 
 }  // namespace dgpu

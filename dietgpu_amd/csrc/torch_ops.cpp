@@ -499,6 +499,31 @@ int64_t decompress_data_range(
   return (int64_t)used;
 }
 
+// Decode-accumulate (no reference op): archive i widened to float32 and stored to (accumulate = false) or added into
+// ts_acc[i], a float32 tensor (dgpu_float_decode_accumulate).  float_type: what the archives hold (1 / 2 / 3).
+int64_t decompress_data_accumulate(
+    const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tAccs, int64_t floatType, bool accumulate,
+    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.size() == tAccs.size());
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType >= (int64_t)DGPU_FLOAT16 && floatType <= (int64_t)DGPU_FLOAT32, "dietgpu: float_type must be 1, 2 or 3");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tIns.size();
+  DecodeTensors m = marshalDecode(true, tIns, tAccs, dev, [&](size_t i) {
+    TORCH_CHECK(tAccs[i].scalar_type() == at::ScalarType::Float, "dietgpu: accumulators must be float32");
+  });
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  size_t used = 0;
+  check(dgpu_float_decode_accumulate(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
+                                         m.inPtrs.data(), m.inBytes.data(), m.outPtrs.data(), m.outCapacity.data(),
+                                         ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
+        "floatDecompressAccumulate", true);
+  return (int64_t)used;
+}
+
 void set_precision(int64_t probBits) {
   TORCH_CHECK(probBits == 9 || probBits == 10 || probBits == 11, "probBits must be 9, 10 or 11");
   tPrecision = (int)probBits;
@@ -541,6 +566,9 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "decompress_data_range(bool compress_as_float, Tensor[] ts_in, Tensor[] ts_out, int[] first_block, int[] num_blocks, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_decompressed_words=None) -> int",
       &dietgpu_amd::decompress_data_range);
+  m.def(
+      "decompress_data_accumulate(Tensor[] ts_in, Tensor[] ts_acc, int float_type, bool accumulate=True, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
+      &dietgpu_amd::decompress_data_accumulate);
 }
 
 TORCH_LIBRARY(dietgpu, m) {

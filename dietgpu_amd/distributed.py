@@ -98,14 +98,24 @@ class GpuFloatCodec:
 
         self.ops = load_torch_ops()
         self.temp_mem = temp_mem
+        self.dtype = None
 
     def compress(self, tensors):
         comp, sizes, _ = self.ops.compress_data(True, tensors, False, self.temp_mem)
+        self.dtype = tensors[0].dtype  # (what decompress_accumulate's rows hold: the collectives exchange one dtype)
         return comp, sizes
 
     def decompress(self, rows, outs):
         status = torch.zeros((len(rows),), dtype=torch.uint8, device=outs[0].device)
         self.ops.decompress_data(True, rows, outs, False, self.temp_mem, status, None)
+        return status
+
+    def decompress_accumulate(self, rows, accs, accumulate):
+        """rows widened to float32 and stored to (accumulate false) or added into the float32 tensors `accs` -> status"""
+        from . import ops
+
+        status = torch.zeros((len(rows),), dtype=torch.uint8, device=accs[0].device)
+        ops.decompress_data_accumulate(rows, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype)
         return status
 
 
@@ -151,6 +161,53 @@ def compressed_all_gather(tensors, codec=None):
         "payload_bytes": int(all_sizes[dist.get_rank()].sum().item()),
     }
     return gathered, stats
+
+
+def compressed_reduce_scatter(tensor, codec=None):
+    """Reduce-scatter (sum) of a flat float tensor, moving compressed bytes and summing in float32.
+
+    `tensor`: this rank's flat fp16 / bf16 / fp32 tensor; its length is a multiple of the world size and the same on
+    every rank.  Shard j of every rank goes to rank j, compressed; rank j decodes the `world` rows it received straight
+    into ONE float32 shard -- no 16-bit scratch tensor, no separate add: rank 0's row is stored (accumulate off, so the
+    shard needs no memset), then one decode-accumulate call per further source rank, in ascending rank order on the
+    current stream.  The result is therefore, by construction, the sequential float32 sum in rank order,
+    ((x_0 + x_1) + x_2) + ..., of the exactly widened inputs: bit-identical on every run and to the same sum computed
+    uncompressed.  Returns (shard_fp32, stats), stats as `compressed_all_gather`.  RuntimeError if a row fails to decode.
+    `codec` needs compress(list) -> (uint8 [n, cap], int32 [n]) and decompress_accumulate(rows, accs, accumulate) ->
+    uint8 status [n]."""
+    codec = codec or GpuFloatCodec()
+    world = dist.get_world_size()
+    if tensor.dim() != 1 or tensor.numel() % world != 0:
+        raise RuntimeError("compressed_reduce_scatter: the tensor must be flat, its length a multiple of the world size")
+    shard_words = tensor.numel() // world
+    comp, sizes = codec.compress(list(tensor.view(world, shard_words).unbind(0)))  # all shards in one call
+    sizes = sizes.to(torch.int32)
+
+    # phase 1: sizes (every rank learns every row's size: the width is the widest row anywhere)
+    all_sizes = [torch.empty_like(sizes) for _ in range(world)]
+    dist.all_gather(all_sizes, sizes)
+    all_sizes = torch.stack(all_sizes)  # [source rank, destination rank]
+    width = (int(all_sizes.max().item()) + 15) // 16 * 16
+
+    # phase 2: row j of this rank to rank j, trimmed to the widest row
+    send = comp[:, :width].contiguous()
+    recv = torch.empty_like(send)
+    work = _all_to_all_flat(recv.view(-1), send.view(-1), world)
+    if work is not None:
+        work.wait()
+
+    me = dist.get_rank()
+    shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
+    for r in range(world):
+        status = codec.decompress_accumulate([recv[r, : int(all_sizes[r, me])]], [shard], r != 0)
+        if not bool(status.all().item()):
+            raise RuntimeError(f"decode-accumulate of rank {r}'s row failed")
+    stats = {
+        "raw_bytes": tensor.numel() * tensor.element_size(),
+        "wire_bytes": world * width,
+        "payload_bytes": int(all_sizes[me].sum().item()),
+    }
+    return shard, stats
 
 
 # ---------------------------------------------------------------------------

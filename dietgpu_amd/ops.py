@@ -521,6 +521,52 @@ def decompress_data_range(compress_as_float, ts_in, ts_out, first_block, num_blo
     return int(used.value)
 
 
+# ------------------------------------------------------------- decode-accumulate
+# (no reference op: dgpu_float_decode_accumulate, include/dietgpu_amd.h)
+def decompress_data_accumulate(ts_in, ts_acc, accumulate=True, temp_mem=None, out_status=None, out_sizes=None,
+                               prob_bits=K_DEFAULT_PRECISION, dtype=None):
+    """Decodes float archive ts_in[i], widens every word to float32 and adds it into ts_acc[i] (accumulate=True: one IEEE
+    float32 add per word) or stores it there (accumulate=False: the accumulator is not read -- a 16-bit archive straight
+    into float32, and the first source of a sum) -> temp bytes used (0).  ts_acc: float32 CUDA tensors that do not overlap.
+
+    One call decodes one float type: `dtype` if given (no host synchronisation: what a caller that knows its archives,
+    or captures the call into a graph, passes), else the type in the header of ts_in[0], read with one synchronising
+    copy (`_header_info`).  out_status[i] is 0, and ts_acc[i] untouched, for an archive of another type, a malformed or
+    truncated one, or one that does not fit ts_acc[i]; out_sizes[i] is the size its header states.  There is no
+    `checksum`: a checksum covers the 16-bit words, which never reach memory here, and is ignored."""
+    _check(len(ts_in) > 0)
+    _check(len(ts_in) == len(ts_acc))
+    _check(ts_in[0].is_cuda, "tensors must be on the GPU")
+    dev = ts_in[0].get_device()
+    for ti, ta in zip(ts_in, ts_acc):
+        _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous() and ti.dtype == torch.uint8)
+        _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
+        _check(ta.dtype == torch.float32, "accumulators must be float32")
+        _check(ta.numel() <= _U32_MAX)
+    n = len(ts_in)
+    _validate_status(out_status, out_sizes, n, dev)
+    with torch.cuda.device(dev):
+        tp, tb = _temp(temp_mem, dev)
+        if dtype is not None:
+            _check(dtype in _DTYPE_TO_FT, "dtype must be float16, bfloat16 or float32")
+            ft = _DTYPE_TO_FT[dtype]
+        else:
+            ft = _header_info(True, ts_in[:1], tp, tb)[1][0]
+            _check(ft in _FT_TO_DTYPE, "ts_in[0] is not a float archive")
+        if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_accumulate"):
+            torch.ops.dietgpu_amd.set_precision(prob_bits)
+            try:
+                return torch.ops.dietgpu_amd.decompress_data_accumulate(ts_in, ts_acc, ft, bool(accumulate), temp_mem, out_status,
+                                                                        out_sizes)
+            finally:
+                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+        used = C.c_size_t(0)
+        check(lib().dgpu_float_decode_accumulate(
+            tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, _ptr_array(ts_in), _in_bytes(ts_in),
+            _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), _ptr(out_status), _ptr(out_sizes), _stream()))
+    return int(used.value)
+
+
 def _check_slice_args(compress_as_float, ts_in, dtype):
     _check(len(ts_in) > 0)
     for t in ts_in:

@@ -63,9 +63,12 @@ extern "C" {
 #define DGPU_ANS_DEFAULT_PROB_BITS 10
 
 const char* dgpu_version(void);
-/* Bumped whenever an entry point of this header is added, removed or changes its meaning.  Code that is built
- * separately against this header (the tensor-op library of this repository, a cgo / JNI binding) compares the value it was compiled with
- * against the library it finds at run time, so that a stale build fails at load instead of inside a call. */
+/* Bumped whenever an entry point of this header is removed or changes its meaning.  Code that is built separately
+ * against this header (the tensor-op library of this repository, a cgo / JNI binding) compares the value it was compiled
+ * with against the library it finds at run time, so that a stale build fails at load instead of inside a call.  An entry
+ * point that is only ADDED leaves every existing one as it was and does not move the version: a library without the new
+ * symbol fails at load too, by symbol resolution, in anything that links it (dgpu_float_decode_accumulate was added
+ * at version 8). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -276,6 +279,31 @@ int dgpu_float_decompress_range(
     uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
     const uint32_t* firstBlock, const uint32_t* numBlocks,
     void* const* out, const uint32_t* outCapacity,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
+
+/* ---- decode-accumulate (no upstream equivalent) --------------------------------------
+ * Decodes float archive i, widens every word to float32 and stores it to (accumulate == 0) or adds it into
+ * (accumulate == 1) the float32 accumulator out[i] -- the reduction of compressed 16-bit gradients in float32 without a
+ * 16-bit scratch tensor, and (accumulate == 0) the decompression of a 16-bit archive straight into float32.
+ * Pointer-array batch that always takes `inBytes`, as the *_bounded calls above; `outCapacity` is in float words.
+ *   - Widening is exact: float16 converts (denormals included), bfloat16 is word << 16, float32 passes through.  The
+ *     sum is ONE IEEE float32 add per word, round to nearest even, denormals kept, not contracted with anything; with
+ *     accumulate == 0 the accumulator is not read (no memset is needed before the first source of a sum) and the bits
+ *     of the widened word are stored as they are.
+ *   - floatType must be DGPU_FLOAT16, DGPU_BFLOAT16 or DGPU_FLOAT32 (there is no raw-byte form), accumulate 0 or 1,
+ *     in[i] 16-byte aligned, out[i] 4-byte aligned, outCapacity[i] <= 0xfffff000: DGPU_ERR_INVALID_ARGUMENT otherwise,
+ *     before anything is enqueued.  The accumulators of the members of one call MUST NOT overlap.
+ *   - outSize_dev[i], outSuccess_dev[i] and every header and descriptor check are those of a whole bounded decode.  A
+ *     member that fails (outSuccess_dev[i] = 0) leaves its accumulator untouched and does not disturb the others.
+ *   - There is no useChecksum: a checksum covers the 16-bit (32-bit) words of the element, which never reach memory
+ *     here.  Archives written with one decode normally; the checksum is ignored.
+ *   - One kernel geometry per call, from its largest capacity.
+ *   - No temp memory is used (*tempUsed = 0) and nothing synchronises: capturable into a HIP graph under the same
+ *     conditions as the other pointer-array decode calls (the arrays resident from an earlier identical call). */
+int dgpu_float_decode_accumulate(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
+    void* const* out /* float32 */, const uint32_t* outCapacity /* float words */,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
 
 /* ---- float stride batches with capacities (no upstream equivalent) ---------------

@@ -1,0 +1,25 @@
+// Decode-accumulate in the style of the dietgpu:: mirror (no reference equivalent): float archive i is decoded, every
+// word widened to float32 and stored to (accumulate = false) or added into (true) the float32 accumulator out[i] -- the
+// float32 reduction of compressed 16-bit gradients without a 16-bit scratch tensor.  Inline on top of
+// dgpu_float_decode_accumulate of ../dietgpu_amd.h, where the contract is spelled out.  `inBytes`: the bytes
+// available at in[i]; `outCapacity`: float words; the accumulators of one call must not overlap.  The config's
+// useChecksum is ignored: a checksum covers the 16-bit words, which never reach memory here.  Uses no temp memory.
+#pragma once
+
+#include "GpuFloatCodec.h"
+
+namespace dietgpu {
+
+inline void floatDecompressAccumulate(
+    StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, const void** in,
+    const uint32_t* inBytes, float** out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev,
+    hipStream_t stream) {
+  (void)res;
+  size_t used = 0;
+  detail::checkRc(dgpu_float_decode_accumulate(nullptr, 0, &used, (uint32_t)config.floatType, config.ansConfig.probBits,
+                                                   accumulate ? 1 : 0, numInBatch, in, inBytes, (void* const*)out,
+                                                   outCapacity, outSuccess_dev, outSize_dev, stream),
+                  "floatDecompressAccumulate");
+}
+
+}  // namespace dietgpu
