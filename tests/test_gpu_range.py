@@ -232,6 +232,27 @@ def test_ranges_of_oracle_archives(dg, ft):
                 run_and_check(dg, route, ft, p, archs, xs, fulls, [kind(nb, t) for nb, t in zip(nbs, sizes)], 4)
 
 
+@pytest.mark.parametrize("ft", [O.FLOAT16, O.BFLOAT16, O.FLOAT32])
+def test_ranges_of_floats_on_both_staging_modes(dg, ft):
+    """make_words gives every float type one staging mode (N(0, 1): fp16 blocks always take the word ring, bf16 and fp32
+    blocks never).  The elements of tests/accum_cases.py hold, for every type, waves staged whole, ring waves, waves that
+    mix the two, and 24 blocks at the 1024-word limit (tests/test_accumulate_cases_host.py asserts it on these archives)."""
+    import accum_cases as AC
+
+    case = AC.staging(ft, 0)
+    members = [AC.STAGING_MIXED, AC.STAGING_BOUNDARY]
+    ws = [case.words[i] for i in members]
+    sizes = [w.size for w in ws]
+    xs = [to_tensor(ft, w) for w in ws]
+    archs = [torch.from_numpy(case.archives(10)[i].copy()).to(DEV) for i in members]
+    fulls = full_decode(dg, ft, archs, xs, 10)
+    nbs = [(t + BLK - 1) // BLK for t in sizes]
+    for kind in KINDS.values():
+        for route in ROUTES:
+            for shift in (0, 4):
+                run_and_check(dg, route, ft, 10, archs, xs, fulls, [kind(nb, t) for nb, t in zip(nbs, sizes)], shift)
+
+
 @pytest.mark.parametrize("ft", TYPES)
 def test_a_range_that_does_not_fit_its_buffer_is_reported(dg, ft):
     total = BLK * 9 + 1234
