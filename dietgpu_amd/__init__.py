@@ -10,6 +10,7 @@ from . import ops  # noqa: F401
 from ._lib import DietGpuError, EXPORTED_SYMBOLS, lib  # noqa: F401
 from .ops import (  # noqa: F401
     compress_data,
+    compress_data_cast,
     compress_data_simple,
     compress_data_split_size,
     block_cover,

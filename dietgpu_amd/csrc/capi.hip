@@ -945,15 +945,18 @@ uint32_t residentWorkgroups(const KernelVariant<Args...>& v, uint32_t workgroups
 // in-order commit (kernels_encode.h, kSpillStageWordsWide; profiles/r06_ab_encoder_five_per_cu_*.txt).
 constexpr uint32_t kWideStageMaxTiles = 32;
 
-// blocks per encoder tile for a batch whose largest element has `maxSize` symbols
-uint32_t encTileBlocksFor(uint32_t maxSize) {
+// blocks per encoder tile for a batch whose largest element has `maxSize` symbols; ft: what is encoded (0: raw bytes; a
+// float type, with kCastSource for a cast call, which has no single-block kernels: its single-block elements run on
+// 2-block tiles)
+uint32_t encTileBlocksFor(uint32_t maxSize, uint32_t ft = 0) {
   const uint32_t blocks = divUp(maxSize, kBlockSize);
+  if (encIsCast(ft) && blocks <= kBlocksPerTinyTile) return kBlocksPerTinyTile;
   return blocks <= kBlocksPerSingleTile ? kBlocksPerSingleTile
       : blocks <= kBlocksPerTinyTile    ? kBlocksPerTinyTile
       : blocks <= kBlocksPerSmallTile   ? kBlocksPerSmallTile
                                         : kBlocksPerTile;
 }
-uint32_t tilesFor(uint32_t maxSize) { return divUp(divUp(maxSize, kBlockSize), encTileBlocksFor(maxSize)); }
+uint32_t tilesFor(uint32_t maxSize, uint32_t ft = 0) { return divUp(divUp(maxSize, kBlockSize), encTileBlocksFor(maxSize, ft)); }
 
 uint32_t absentWorkgroupModulo();  // test hook, defined with the C ABI below
 
@@ -1061,13 +1064,13 @@ void planHistList(const std::vector<uint32_t>& sizes, uint32_t wordBytes, bool r
 }
 // Work lists of an encode call: false = the rectangles.
 bool planEncode(const std::vector<uint32_t>& sizes, uint32_t floatType, uint32_t maxSize, bool needHist, RaggedPlan* plan, std::vector<uint32_t>* work) {
-  const uint32_t tileBlocks = encTileBlocksFor(maxSize);
+  const uint32_t tileBlocks = encTileBlocksFor(maxSize, floatType);
   if (tileBlocks == kBlocksPerSingleTile) return false;  // single-block batches: one wavefront per element, nothing to list
   std::vector<uint32_t> tileBase;
-  if (!planTileList(sizes, tileBlocks * kBlockSize, tilesFor(maxSize), 0u, work, &tileBase)) return false;
+  if (!planTileList(sizes, tileBlocks * kBlockSize, tilesFor(maxSize, floatType), 0u, work, &tileBase)) return false;
   plan->use = true;
   plan->numTiles = (uint32_t)work->size();
-  if (needHist) planHistList(sizes, floatType ? floatWordBytes(floatType) : 1u, floatType == 0, plan, work);
+  if (needHist) planHistList(sizes, floatType ? floatWordBytes(encArchiveType(floatType)) : 1u, floatType == 0, plan, work);
   work->insert(work->end(), tileBase.begin(), tileBase.end());
   return true;
 }
@@ -1139,9 +1142,9 @@ bool classifyBySize(const std::vector<uint32_t>& sizes, ClassOf classOf, bool pa
 }
 bool planEncodeClasses(const std::vector<uint32_t>& sizes, uint32_t floatType, std::vector<EncodeClass>* classes, std::vector<uint32_t>* work) {
   std::vector<uint32_t> classOfElem, order;
-  if (!classifyBySize(sizes, [](uint32_t sz) { return encTileBlocksFor(sz); }, floatType != kFloat32, &classOfElem, &order)) return false;
+  if (!classifyBySize(sizes, [](uint32_t sz) { return encTileBlocksFor(sz); }, floatType != kFloat32 && !encIsCast(floatType), &classOfElem, &order)) return false;
   const size_t B = sizes.size();
-  const uint32_t wordBytes = floatType ? floatWordBytes(floatType) : 1u;
+  const uint32_t wordBytes = floatType ? floatWordBytes(encArchiveType(floatType)) : 1u;  // (a cast call's parts go by the archive's words)
   classes->clear();
   for (uint32_t c : order) {
     EncodeClass k;
@@ -1348,7 +1351,10 @@ bool histogramLoadsNonTemporal(uint32_t ft) {
 // Shared tail of every encode entry point: [checksum] -> histogram (+ fused
 // normalisation) -> encode.  `in` holds raw bytes (floatType == 0: the ANS
 // archive is the whole output) or float words (floatType != 0: the encoder
-// splits them on the fly, the archive is a float archive).  No memset is needed
+// splits them on the fly, the archive is a float archive).  `sourceType` is floatType, or floatType | kCastSource for
+// a cast call: `in` then holds float32 words, which histogram and encoder round to floatType in registers.  Only the
+// choice of the kernels depends on it -- grids, lists and temp memory are those of the plain call of floatType (no
+// single-block kernels, though: such elements run on 2-block tiles).  No memset is needed
 // on the common path: histogram workgroups store partial histograms, the last
 // one of each element sums and normalises them and clears the tile descriptors +
 // ticket for the encode kernel.
@@ -1365,15 +1371,16 @@ struct EncodeShared {
 };
 int encodeCommon(
     TempArena& arena, StreamLease& lease, hipStream_t stream, int P, bool useChecksum, uint32_t B,
-    const BatchView& in, const BatchView& archives, uint32_t floatType, uint32_t maxSize,
+    const BatchView& in, const BatchView& archives, uint32_t sourceType, uint32_t maxSize,
     const uint32_t* hist_dev /*may be null*/, uint32_t* outSize_dev,
     uint32_t outCapacity = 0xffffffffu /* bytes at every archive pointer; block data beyond it is dropped */,
     const RaggedPlan* plan = nullptr, const uint32_t* work_dev = nullptr /* the plan's lists on the device */,
     const EncodeClass* cls = nullptr /* one size class of the batch (its lists in work_dev); maxSize is the class's */,
     EncodeShared* shared = nullptr /* what the classes of one call share */) {
+  const uint32_t floatType = encArchiveType(sourceType);
   const uint32_t wordBytes = floatType ? floatWordBytes(floatType) : 1u;
-  const uint32_t tileBlocks = cls ? cls->tileBlocks : encTileBlocksFor(maxSize);
-  const uint32_t maxTiles = cls ? std::max(1u, divUp(divUp(maxSize, kBlockSize), tileBlocks)) : tilesFor(maxSize);
+  const uint32_t tileBlocks = cls ? cls->tileBlocks : encTileBlocksFor(maxSize, sourceType);
+  const uint32_t maxTiles = cls ? std::max(1u, divUp(divUp(maxSize, kBlockSize), tileBlocks)) : tilesFor(maxSize, sourceType);
 
   uint32_t* checksumTemp = shared ? shared->checksumTemp : nullptr;
   if (useChecksum && !checksumTemp) {
@@ -1431,8 +1438,8 @@ int encodeCommon(
   const uint32_t numTickets = lists ? numListedTiles : (elemMap ? numElems : B * maxTiles);
   const uint32_t numWorkgroups = pairs ? (numTickets + 1u) / 2u : numTickets;  // (one per pair of elements / per tile)
   const bool wideStage = maxTiles <= kWideStageMaxTiles;
-  const EncodeVariant persistent = encoderVariant(P, floatType, tileBlocks, false, wideStage);
-  const EncodeVariant hardware = encoderVariant(P, floatType, tileBlocks, true, wideStage);
+  const EncodeVariant persistent = encoderVariant(P, sourceType, tileBlocks, false, wideStage);
+  const EncodeVariant hardware = encoderVariant(P, sourceType, tileBlocks, true, wideStage);
   const bool bothForms = hardware.fn != persistent.fn;
   // The persistent grid is the persistent variant's own occupancy.  The spill pool must cover whichever form is
   // launched and the policy is decided before the form is: where both forms exist the larger occupancy counts there
@@ -1525,7 +1532,7 @@ int encodeCommon(
     fuse.norm = n;
     // bins with 32 lane slots unless a workgroup sees too little data to pay for zeroing / folding them
     const bool smallBins = histList ? listedHistPartBytes <= 64u * 1024u : (uint64_t)maxSize * wordBytes / grid.x <= 64u * 1024u;
-    rc = launchVariant(histogramVariant(floatType, smallBins, histogramLoadsNonTemporal(floatType)), grid, stream, in, histTemp, 1u, fuse);
+    rc = launchVariant(histogramVariant(sourceType, smallBins, histogramLoadsNonTemporal(floatType)), grid, stream, in, histTemp, 1u, fuse);
     if (rc) return rc;
   } else {
     // caller-supplied histogram: stand-alone normalisation
@@ -1609,15 +1616,16 @@ int ansEncodeImpl(
   return encodeBatch(temp_dev, tempBytes, tempUsed, 0u, P, useChecksum, b, histogram_dev, outSize_dev, stream);
 }
 
+// (cast: the batch holds float32 words and ft is the archive's 16-bit type)
 int floatCompressImpl(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b, uint32_t* outSize_dev,
-    hipStream_t stream) {
+    hipStream_t stream, bool cast = false) {
   bool done;
   int rc = checkCall(P, b.n, ft, tempUsed, /*errBatch*/ nullptr, &done,
                      "tensor larger than 1717538816 words: the maximum compressed size of its exponent plane exceeds INT32_MAX (GpuANSEncode.cu:22)",
                      b.maxSize);
   if (done) return rc;
-  return encodeBatch(temp_dev, tempBytes, tempUsed, ft, P, useChecksum, b, nullptr, outSize_dev, stream);
+  return encodeBatch(temp_dev, tempBytes, tempUsed, cast ? (ft | kCastSource) : ft, P, useChecksum, b, nullptr, outSize_dev, stream);
 }
 
 // Order of k_ans_decode's workgroups (kernels_decode.h: decodeTileOf).  Measured on MI355X, cold round trip
@@ -2277,6 +2285,20 @@ int dgpu_float_compress(
   int rc = pointerBatch(&b, numInBatch, ptrSide(in, floatWordBytes(floatType), kMsgFloatIn), ptrSide(out, 16, kMsgCompOut), inSize);
   if (rc) return rc;
   return floatCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, useChecksum, b, outSize_dev, (hipStream_t)stream);
+}
+
+// ---- cast-compress (no upstream equivalent) ------------------------------------------
+// float32 words in, ordinary float16 / bfloat16 archives out: the rounding is fused into the histogram and the encoder
+// (kernels_encode.h, ChunkSourceCast).  No checksum: it covers the 16-bit words, which never reach memory.
+int dgpu_float_cast_compress(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits,
+    uint32_t numInBatch, const void* const* in, const uint32_t* inSize,
+    void* const* out, uint32_t* outSize_dev, void* stream) {
+  DGPU_REQUIRE(floatType == kFloat16 || floatType == kBFloat16, "floatType of a cast archive must be float16 or bfloat16");
+  Batch b;
+  int rc = pointerBatch(&b, numInBatch, ptrSide(in, 4, "float32 input must be 4-byte aligned"), ptrSide(out, 16, kMsgCompOut), inSize);
+  if (rc) return rc;
+  return floatCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, 0, b, outSize_dev, (hipStream_t)stream, true);
 }
 
 int dgpu_float_compress_split_size(

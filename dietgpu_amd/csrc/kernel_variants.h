@@ -72,13 +72,38 @@ auto withProbBitsAndFloatType(int P, uint32_t ft, F&& f) {
 // CU; kernels_encode.h).
 constexpr bool encodeSpills(uint32_t ft) { return ft != 0; }
 
-// The encoder of tiles of `tileBlocks` blocks.
+// Cast sources (kCastSource: float32 words in, the archive of a 16-bit type out) exist as tiled encoders of 2, 4 and 8
+// blocks in the dispatch forms of the plain 16-bit call -- 2- and 4-block tiles persistent and hardware-dispatched,
+// 8-block tiles persistent -- without the wide stage, and as every histogram form.  There is no cast form of the
+// single-block kernels (k_ans_encode_pair, k_stats_single): single-block members of a cast call run on 2-block tiles.
+inline EncodeVariant encoderVariantCast(int P, uint32_t archiveType, uint32_t tileBlocks, bool hwDispatch) {
+  auto of = [&](auto p, auto f) -> EncodeVariant {
+    constexpr int kP = decltype(p)::value;
+    constexpr uint32_t kFT = decltype(f)::value | kCastSource;
+    auto tiled = [](auto tb, auto persistent) -> EncodeVariant {
+      constexpr uint32_t kTB = decltype(tb)::value;
+      constexpr bool kPersistent = decltype(persistent)::value;
+      return {k_ans_encode<kP, kFT, true, kTB, kPersistent, false>, encThreads(kTB), encLdsBytes(kP, true, kFT, kTB), "k_ans_encode_cast"};
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (tileBlocks <= kBlocksPerTinyTile) return hwDispatch ? tiled(UintC<kBlocksPerTinyTile>{}, no) : tiled(UintC<kBlocksPerTinyTile>{}, yes);
+    if (tileBlocks == kBlocksPerSmallTile) return hwDispatch ? tiled(UintC<kBlocksPerSmallTile>{}, no) : tiled(UintC<kBlocksPerSmallTile>{}, yes);
+    return tiled(UintC<kBlocksPerTile>{}, yes);
+  };
+  return withProbBits(P, [&](auto p) {
+    return archiveType == kFloat16 ? of(p, UintC<kFloat16>{}) : of(p, UintC<kBFloat16>{});
+  });
+}
+
+// The encoder of tiles of `tileBlocks` blocks; ft: the archive's float type, with kCastSource for a cast source.
 //   * single-block tiles go to k_ans_encode_pair: two ELEMENTS per wavefront, always one workgroup per pair;
 //   * hwDispatch: one workgroup per tile, dispatched by the hardware in ticket order, instead of persistent workgroups
 //     that walk the tickets.  8-block float tiles exist in the persistent form only (hardware dispatch measured no
 //     gain there);
 //   * wide: the wide stage (kSpillStageWordsWide) exists for persistent 8-block bf16 / fp32 tiles only.
 inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, bool hwDispatch, bool wide) {
+  if (encIsCast(ft)) return encoderVariantCast(P, encArchiveType(ft), tileBlocks, hwDispatch);
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> EncodeVariant {
     constexpr int kP = decltype(p)::value;
     constexpr uint32_t kFT = decltype(f)::value;
@@ -147,8 +172,9 @@ inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, Dec
 }
 
 // The histogram pass: bins with kHistSlotsSmall or kHistSlotsLarge lane slots, non-temporal or ordinary input loads.
+// (ft with kCastSource: the cast form, which bins the exponent byte of the rounded word)
 inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTemporal) {
-  return withFloatType(ft, [&](auto f) -> HistogramVariant {
+  auto pick = [&](auto f) -> HistogramVariant {
     constexpr uint32_t kFT = decltype(f)::value;
     auto of = [](auto slots, auto nt) -> HistogramVariant {
       constexpr uint32_t kS = decltype(slots)::value;
@@ -156,14 +182,16 @@ inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTe
       if constexpr (kFT == 0) {
         return {k_histogram<kS, kNt>, 256u, 0u, "k_histogram"};
       } else {
-        return {k_float_histogram<kFT, kS, kNt>, 256u, 0u, "k_float_histogram"};
+        return {k_float_histogram<kFT, kS, kNt>, 256u, 0u, encIsCast(kFT) ? "k_float_histogram_cast" : "k_float_histogram"};
       }
     };
     constexpr UintC<kHistSlotsSmall> small{};
     constexpr UintC<kHistSlotsLarge> large{};
     if (nonTemporal) return smallBins ? of(small, std::true_type{}) : of(large, std::true_type{});
     return smallBins ? of(small, std::false_type{}) : of(large, std::false_type{});
-  });
+  };
+  if (encIsCast(ft)) return encArchiveType(ft) == kFloat16 ? pick(UintC<kFloat16 | kCastSource>{}) : pick(UintC<kBFloat16 | kCastSource>{});
+  return withFloatType(ft, pick);
 }
 
 // One wavefront counts and normalises a single-block element (kernels_pairs.h).  Not built for float32, whose batches

@@ -84,8 +84,16 @@ __host__ __device__ constexpr uint32_t encSpillSlotWords(int P) { return roundUp
 
 // (Raw bytes keep the worst-case stage: a 1664-word stage with spill slots -- 4 workgroups per CU -- measured -2 %
 // for 43 MiB more temp memory, and nothing once the row stored under the ballot; docs/HISTORY.md section 5, "Config 2".)
+// SOURCE of an encoder / histogram instantiation: the template parameter FT is the archive's float type, or -- cast
+// sources, which read float32 words and round them to the archive's 16-bit type in registers -- that type with
+// kCastSource set.  Everything about the ARCHIVE (layout, header, stage size) goes by encArchiveType(FT).
+constexpr uint32_t kCastSource = 0x100u;
+__host__ __device__ constexpr bool encIsCast(uint32_t ft) { return (ft & kCastSource) != 0u; }
+__host__ __device__ constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~kCastSource; }
+__host__ __device__ constexpr uint32_t encSourceWordBytes(uint32_t ft) { return ft == 0u ? 1u : ((ft == kFloat32 || encIsCast(ft)) ? 4u : 2u); }
+
 __host__ __device__ constexpr uint32_t encStageCap(int P, bool spill, uint32_t ft, bool wide = false) {
-  return spill ? (ft == kFloat16 ? kSpillStageWordsFp16 : (wide ? kSpillStageWordsWide : kSpillStageWords)) : encStageWords(P);
+  return spill ? (encArchiveType(ft) == kFloat16 ? kSpillStageWordsFp16 : (wide ? kSpillStageWordsWide : kSpillStageWords)) : encStageWords(P);
 }
 // Blocks per tile = per workgroup: 8 (256 threads), or 4 (128 threads) for batches whose elements have
 // at most 4 blocks -- an 8-block tile would leave half of its waves without a block there.
@@ -189,7 +197,7 @@ struct ChunkSource;
 // mask them.
 template <uint32_t FT>
 __device__ __forceinline__ bool encVectorLoadsOk(const uint8_t* in, uint32_t size) {
-  constexpr uint32_t kWordBytes = FT == 0u ? 1u : (FT == kFloat32 ? 4u : 2u);
+  constexpr uint32_t kWordBytes = encSourceWordBytes(FT);
   const uint32_t a = (uint32_t)(uintptr_t)in;
   return (a & 15u) == 0 || ((a & (kWordBytes - 1u)) == 0 && (uint64_t)size * kWordBytes >= 16u);
 }
@@ -447,6 +455,144 @@ struct ChunkSource<kFloat32> {  // 4-byte words: comp byte + 24 non-comp bits (u
   }
 };
 
+// float32 -> 16-bit float, round to nearest even, for the cast sources and the cast histogram (one helper, so that the
+// two cannot disagree).  `x` are the float32 bits; NaN becomes the canonical quiet NaN of the target with the sign kept
+// (a payload in the low 16 bits alone must not round to infinity).
+//   * bfloat16: integer rounding on the bits, (x + 0x7fff + lsb) >> 16: float32 denormals are not flushed, overflow
+//     carries into infinity.  castRoundHigh leaves the result in the HIGH half (the low half is of no use).
+//   * float16: v_cvt_f16_f32 under the kernel's default mode (round to nearest even, float16 denormals produced; every
+//     float32 denormal is below half the smallest float16 denormal and becomes a zero whether or not it is flushed).
+template <uint32_t AT>
+__device__ __forceinline__ uint32_t castRoundHigh(uint32_t x) {
+  static_assert(AT == kBFloat16, "");
+  const bool nan = (x & 0x7fffffffu) > 0x7f800000u;
+  const uint32_t s = x + 0x7fffu + ((x >> 16) & 1u);
+  return nan ? ((x & 0x80000000u) | 0x7fc00000u) : s;
+}
+template <uint32_t AT>
+__device__ __forceinline__ uint32_t castRound(uint32_t x) {
+  if (AT == kBFloat16) {
+    return castRoundHigh<kBFloat16>(x) >> 16;
+  } else {
+    const bool nan = (x & 0x7fffffffu) > 0x7f800000u;
+    const uint32_t h = (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)__builtin_bit_cast(float, x));
+    return nan ? (((x >> 16) & 0x8000u) | 0x7e00u) : h;
+  }
+}
+// two words -> one dword of two 16-bit words (x0's in the low half)
+template <uint32_t AT>
+__device__ __forceinline__ uint32_t castRoundPair(uint32_t x0, uint32_t x1) {
+  if (AT == kBFloat16) return __builtin_amdgcn_perm(castRoundHigh<kBFloat16>(x1), castRoundHigh<kBFloat16>(x0), 0x07060302u);
+  return __builtin_amdgcn_perm(castRound<AT>(x1), castRound<AT>(x0), 0x05040100u);
+}
+
+// ChunkSource16's split of packed pairs of 16-bit words for any number of dwords: the compressed (exponent) bytes and
+// the non-compressed bytes, four to a dword each, in word order.  (ChunkSource16::splitStore keeps its own copy: called
+// through this function its kernels come out of the compiler scheduled differently, and they are the measured ones.)
+template <uint32_t FT, int kDwords>
+__device__ __forceinline__ void splitPacked16(const uint32_t (&x)[kDwords], uint32_t (&comp)[kDwords / 2], uint32_t (&rest)[kDwords / 2]) {
+  if (FT == kFloat16) {
+    // comp = w >> 8 (bytes 1, 3 of each dword), nonComp = w & 0xff (bytes 0, 2)
+#pragma unroll
+    for (int j = 0; j < kDwords / 2; ++j) {
+      comp[j] = packBytes13(x[2 * j + 1], x[2 * j]);
+      rest[j] = packBytes02(x[2 * j + 1], x[2 * j]);
+    }
+  } else {
+    // bf16: comp = bits 14..7; nonComp = mantissa7 << 1 | sign, i.e. each
+    // 16-bit half rotated left by one, low byte
+    uint32_t t[kDwords], q[kDwords];
+#pragma unroll
+    for (int j = 0; j < kDwords; ++j) {
+      t[j] = x[j] >> 7;                                         // comp in bytes 0 and 2
+      // each half rotated left by one = w * 2 + (w >> 15) on packed u16 (v_pk_lshrrev_b16 + v_pk_mad_u16)
+      // (the compiler expands the multiply into a shift and an add; the asm keeps it to two ops)
+      const u16x2e w = __builtin_bit_cast(u16x2e, x[j]);
+      const uint32_t signs = __builtin_bit_cast(uint32_t, (u16x2e)(w >> 15));
+      asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(q[j]) : "v"(x[j]), "s"(0x00020002u), "v"(signs));
+    }
+#pragma unroll
+    for (int j = 0; j < kDwords / 2; ++j) {
+      comp[j] = packBytes02(t[2 * j + 1], t[2 * j]);
+      rest[j] = packBytes02(q[2 * j + 1], q[2 * j]);
+    }
+  }
+}
+
+// Cast source: float32 words in, the archive of the 16-bit type AT out.  The chunk has ChunkSource<kFloat32>'s shape --
+// 8 rows, two 16-byte loads per lane -- because 16 rows of float32 in flight are 16 registers; the lane rounds its 8
+// words to 4 packed dwords (castRoundPair) and from there it is ChunkSource16's split: one 8-byte store into the
+// non-compressed plane, 8 exponent bytes for the ring.  The 16-bit words never exist in memory.
+template <uint32_t AT>
+struct ChunkSourceCast {
+  static constexpr uint32_t kRows = 8;
+  struct Raw { uint4 v[2]; };
+  const uint32_t* in;  // this half's block (4096 float32 words)
+  uint8_t* nc;         // this half's block of the non-comp plane
+  __device__ __forceinline__ void init(const uint8_t* elemIn, uint8_t* archive, uint32_t, uint32_t block) {
+    in = (const uint32_t*)elemIn + (size_t)block * kBlockSize;
+    nc = archive + 16u + (size_t)block * kBlockSize;
+  }
+  __device__ __forceinline__ Raw load(uint32_t c, uint32_t hl) const {
+    const uint4* p = (const uint4*)(in + c * 256u + hl * 8u);
+    Raw r;
+    r.v[0] = streamLoad<kNtEncLoads>(&p[0]);
+    r.v[1] = streamLoad<kNtEncLoads>(&p[1]);
+    return r;
+  }
+  static constexpr uint32_t kCompRegs = 2;
+  __device__ __forceinline__ void consume(const Raw& r, uint32_t c, uint32_t hl, uint8_t* ring) const {
+    uint32_t comp[2];
+    splitStore(r, c, hl, comp);
+    *(uint2*)(ring + hl * 8u) = make_uint2(comp[0], comp[1]);
+  }
+  // Tail forms: see ChunkSource<kFloat32> (8 float32 words per lane and chunk, bounded by loadSliceBounded: no byte
+  // beyond the element is read).  Words at or beyond n are set to zero BEFORE they are rounded, so their non-compressed
+  // bytes -- in the plane's zero padding -- are zero.
+  __device__ __forceinline__ Raw loadTail(uint32_t c, uint32_t hl, uint32_t n) const {
+    const uint32_t first = c * 256u + hl * 8u;
+    Raw r;
+    loadSliceBounded<2>((const uint8_t*)in, first * 4u, n * 4u, r.v);
+    return r;
+  }
+  __device__ __forceinline__ void consumeTail(const Raw& r, uint32_t c, uint32_t hl, uint8_t* ring, uint32_t n) const {
+    const uint32_t first = c * 256u + hl * 8u;
+    const uint32_t valid = n > first ? (n - first < 8u ? n - first : 8u) : 0u;
+    auto keep = [&](uint32_t x, uint32_t j) -> uint32_t { return valid > j ? x : 0u; };
+    Raw m;
+    m.v[0] = make_uint4(keep(r.v[0].x, 0), keep(r.v[0].y, 1), keep(r.v[0].z, 2), keep(r.v[0].w, 3));
+    m.v[1] = make_uint4(keep(r.v[1].x, 4), keep(r.v[1].y, 5), keep(r.v[1].z, 6), keep(r.v[1].w, 7));
+    uint32_t comp[2];
+    splitStore(m, c, hl, comp, valid != 0u);
+    *(uint2*)(ring + hl * 8u) = make_uint2(comp[0], comp[1]);
+  }
+  __device__ __forceinline__ void splitStore(const Raw& r, uint32_t c, uint32_t hl, uint32_t (&comp)[kCompRegs], bool store = true) const {
+    const uint32_t x[4] = {castRoundPair<AT>(r.v[0].x, r.v[0].y), castRoundPair<AT>(r.v[0].z, r.v[0].w),
+                           castRoundPair<AT>(r.v[1].x, r.v[1].y), castRoundPair<AT>(r.v[1].z, r.v[1].w)};
+    uint32_t rest[2];
+    splitPacked16<AT, 4>(x, comp, rest);
+    if (store) *(uint2*)(nc + c * 256u + hl * 8u) = make_uint2(rest[0], rest[1]);
+  }
+  // scalar path: the rounded 16-bit word (the load is of the element's own 4 bytes)
+  __device__ __forceinline__ uint32_t wordAt(uint32_t i) const { return castRound<AT>(in[i]); }
+  __device__ __forceinline__ uint32_t splitAt(uint32_t i, uint32_t w, bool valid) const {
+    uint32_t c, r;
+    if (AT == kFloat16) {
+      c = w >> 8;
+      r = w & 0xffu;
+    } else {
+      c = (w >> 7) & 0xffu;
+      r = ((w << 1) & 0xfeu) | (w >> 15);
+    }
+    if (valid) nc[i] = (uint8_t)r;
+    return c;
+  }
+};
+template <>
+struct ChunkSource<kFloat16 | kCastSource> : ChunkSourceCast<kFloat16> {};
+template <>
+struct ChunkSource<kBFloat16 | kCastSource> : ChunkSourceCast<kBFloat16> {};
+
 // ---------------------------------------------------------------------------
 // The emitting lanes of a full-block row store their word under the row's ballot as execution mask -- two scalar
 // instructions instead of the v_cndmask that would park the idle lanes' store on a scratch slot -- and, for raw
@@ -457,7 +603,7 @@ struct ChunkSource<kFloat32> {  // 4-byte words: comp byte + 24 non-comp bits (u
 // positions in SGPRs (-2 VALU, +7 SALU: +8 %), a packed 8-byte table entry (half the LDS bytes, +3 VALU: +8 %),
 // table entries 4 rows ahead instead of 2 (+8 %), a hand-scheduled SDWA select (+5 %).
 template <uint32_t FT>
-constexpr bool encShiftUnderBallot() { return FT == 0u || FT == kBFloat16; }
+constexpr bool encShiftUnderBallot() { return FT == 0u || encArchiveType(FT) == kBFloat16; }
 // The incoming execution mask is saved and restored (s_and_saveexec), so a caller with inactive lanes keeps them
 // inactive; every caller in this library runs the full-block step with all 64 lanes active.
 __device__ __forceinline__ void stageWriteUnder(uint64_t vote, uint32_t addr, uint32_t state) {
@@ -855,7 +1001,8 @@ __device__ __forceinline__ uint32_t lookBackTwoLevel(const uint64_t* desc, uint6
 template <int P, uint32_t FT, bool kSpill, uint32_t kTB, bool kPersistent, bool kWide = false>
 __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_ans_encode(EncodeArgs a) {
   static_assert(kTB >= 2u, "single-block elements are k_ans_encode_pair's");
-  static_assert(!kWide || (kSpill && FT != kFloat16 && kTB == kBlocksPerTile && kPersistent), "the wide stage exists for persistent 8-block bf16 / fp32 tiles");
+  static_assert(!kWide || (kSpill && encArchiveType(FT) != kFloat16 && kTB == kBlocksPerTile && kPersistent), "the wide stage exists for persistent 8-block bf16 / fp32 tiles");
+  constexpr uint32_t AT = encArchiveType(FT);  // the archive's float type (FT: the source's, see kCastSource)
   constexpr uint32_t kThreads = encThreads(kTB);
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr uint32_t kCap = encStageCap(P, kSpill, FT, kWide);
@@ -958,7 +1105,7 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
 
       const uint8_t* in = a.in.ptr(b);
       uint8_t* archive = a.out.ptr(b);
-      uint8_t* ans = archive + ansOffsetInArchive(FT, size);
+      uint8_t* ans = archive + ansOffsetInArchive(AT, size);
 
       if (FT != 0 && tile == 0) {
         // GpuFloatHeader (GpuFloatCompress.cuh:325-337) and the zero padding of the
@@ -967,11 +1114,11 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
           FloatHeader h;
           h.magicAndVersion = (kFloatMagic << 16) | kFloatVersion;
           h.size = size;
-          h.options = FT | (a.useChecksum ? 0x10u : 0u);
+          h.options = AT | (a.useChecksum ? 0x10u : 0u);
           h.checksum = (a.useChecksum && a.checksum) ? a.checksum[b] : 0u;
           *(FloatHeader*)archive = h;
         }
-        if (FT == kFloat32) {
+        if (AT == kFloat32) {
           uint16_t* nc2 = (uint16_t*)(archive + 16u);
           uint8_t* nc1 = archive + 16u + 2u * (size_t)roundUp(size, 8u);
           if (size + tid < roundUp(size, 8u)) nc2[size + tid] = 0;
@@ -1105,7 +1252,7 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
             // complete the header (GpuANSEncode.cuh:533-566)
             ((AnsHeader*)ans)->totalCompressedWords = failed ? 0u : inclusive;
             if (failed) ((AnsHeader*)ans)->magicAndVersion = 0u;  // no decoder will follow this archive
-            if (a.outSize) a.outSize[b] = failed ? 0u : ansOffsetInArchive(FT, size) + ansOverhead(nb) + 2u * inclusive;
+            if (a.outSize) a.outSize[b] = failed ? 0u : ansOffsetInArchive(AT, size) + ansOverhead(nb) + 2u * inclusive;
           }
         }
         // per-block word counts and start offsets (GpuANSEncode.cuh:595-608)
@@ -1125,7 +1272,7 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
       ldsBarrier();
 
       if (haveBlock) {
-        const uint64_t dataOff = (uint64_t)ansOffsetInArchive(FT, size) + ansOverhead(nb) + 2ull * (sh->tileBase + sh->localOff[hw]);
+        const uint64_t dataOff = (uint64_t)ansOffsetInArchive(AT, size) + ansOverhead(nb) + 2ull * (sh->tileBase + sh->localOff[hw]);
         uint4* dst = (uint4*)(archive + dataOff);
         // 16-byte vectors of this block that still fit the caller's capacity (all of them under the reference's contract)
         const uint64_t room = (uint64_t)a.outCapacity > dataOff ? ((uint64_t)a.outCapacity - dataOff) / 16u : 0u;
@@ -1159,11 +1306,16 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
 // (the histogram the reference fuses into splitFloat,
 // GpuFloatCompress.cuh:144, 352-364).  grid = (xBlocks, B), 256 threads;
 // hist must be zeroed first.
+// Cast form (FT = archive type | kCastSource): the element is float32 words and the bin is the exponent byte of the
+// word ROUNDED to the archive's type (castRound, as the encoder's cast source: a carry out of the mantissa changes it).
+// Its parts are laid out by the bytes of the ARCHIVE's words, as the plain call's are: same grids, same temp memory.
 template <uint32_t FT, uint32_t S, bool kNt = true>
 __global__ __launch_bounds__(256) void k_float_histogram(BatchView in, uint32_t* __restrict__ hist, uint32_t partial, HistFuse fuse) {
   __shared__ uint32_t bins[kNumSymbols * S];
   const uint32_t tid = threadIdx.x;
-  const HistWork w = histWorkOf(fuse, in, FT == kFloat32 ? 4u : 2u);
+  constexpr bool kCast = encIsCast(FT);
+  constexpr uint32_t AT = encArchiveType(FT);
+  const HistWork w = histWorkOf(fuse, in, AT == kFloat32 ? 4u : 2u);
   const uint32_t b = w.b;
   histZero<S>(bins, tid);
   __syncthreads();
@@ -1173,7 +1325,7 @@ __global__ __launch_bounds__(256) void k_float_histogram(BatchView in, uint32_t*
   const uint8_t* inBytes = in.ptr(b);
   // words before the first 16-byte boundary (elements of a split tensor and rows of a matrix start anywhere; a count
   // does not care about order, so the vectors simply start at the boundary)
-  constexpr uint32_t kWordBytes = FT == kFloat32 ? 4u : 2u;
+  constexpr uint32_t kWordBytes = encSourceWordBytes(FT);
   constexpr uint32_t kWordsPerVec = 16u / kWordBytes;
   const bool wordAligned = (((uintptr_t)inBytes) & (kWordBytes - 1u)) == 0;
   uint32_t head = wordAligned ? (uint32_t)((16u - ((uintptr_t)inBytes & 15u)) & 15u) / kWordBytes : n;
@@ -1182,8 +1334,13 @@ __global__ __launch_bounds__(256) void k_float_histogram(BatchView in, uint32_t*
   const uint32_t stride = w.parts * 256u;
   const uint4* pv = (const uint4*)(inBytes + (size_t)head * kWordBytes);
 
+  constexpr uint32_t kShift16 = AT == kFloat16 ? 8u : 7u;  // exponent byte of a 16-bit word
   auto addVec = [&](const uint4& x) {
-    if (FT == kFloat32) {
+    if (kCast) {
+      const uint32_t xw[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) histAdd<S>(myBins, (castRound<kCast ? AT : kBFloat16>(xw[j]) >> kShift16) & 0xffu);
+    } else if (FT == kFloat32) {
       histAdd<S>(myBins, (x.x >> 23) & 0xffu);
       histAdd<S>(myBins, (x.y >> 23) & 0xffu);
       histAdd<S>(myBins, (x.z >> 23) & 0xffu);
@@ -1221,7 +1378,8 @@ __global__ __launch_bounds__(256) void k_float_histogram(BatchView in, uint32_t*
   for (uint32_t j = w.part * 256u + tid; j < loose; j += stride) {
     const uint32_t i = j < head ? j : numVec * kWordsPerVec + j;
     uint32_t c;
-    if (FT == kFloat32) c = (((const uint32_t*)inBytes)[i] >> 23) & 0xffu;
+    if (kCast) c = (castRound<kCast ? AT : kBFloat16>(((const uint32_t*)inBytes)[i]) >> kShift16) & 0xffu;
+    else if (FT == kFloat32) c = (((const uint32_t*)inBytes)[i] >> 23) & 0xffu;
     else c = ((uint32_t)((const uint16_t*)inBytes)[i] >> (FT == kFloat16 ? 8u : 7u)) & 0xffu;
     histAdd<S>(myBins, c);
   }

@@ -524,6 +524,44 @@ int64_t decompress_data_accumulate(
   return (int64_t)used;
 }
 
+// Cast-compress (no reference op): float32 tensor i rounded to float_type (1 = float16, 2 = bfloat16) in registers and
+// compressed into an ordinary archive of that type (dgpu_float_cast_compress).  Output conventions of compress_data.
+std::tuple<at::Tensor, at::Tensor, int64_t> compress_data_cast(
+    const std::vector<at::Tensor>& tIns, int64_t floatType, const std::optional<at::Tensor>& tempMem,
+    const std::optional<at::Tensor>& outCompressed, const std::optional<at::Tensor>& outCompressedSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tIns.size();
+  int64_t maxWords = 0;
+  for (auto& t : tIns) {
+    TORCH_CHECK(t.device().is_cuda());
+    TORCH_CHECK(t.is_contiguous());
+    TORCH_CHECK(t.get_device() == dev);
+    TORCH_CHECK(t.scalar_type() == at::ScalarType::Float, "dietgpu: the inputs of a cast call must be float32");
+    maxWords = std::max<int64_t>(maxWords, t.numel());
+  }
+  at::Tensor comp, sizes;
+  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)maxWords), dev,
+                  tIns[0].device(), comp, sizes);
+  std::vector<const void*> inPtrs(n);
+  std::vector<uint32_t> inSize(n);
+  std::vector<void*> compPtrs(n);
+  for (size_t i = 0; i < n; ++i) {
+    inPtrs[i] = tIns[i].data_ptr();
+    inSize[i] = (uint32_t)tIns[i].numel();
+    compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
+  }
+  size_t used = 0;
+  check(dgpu_float_cast_compress(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), (uint32_t)n, inPtrs.data(), inSize.data(),
+                                 compPtrs.data(), (uint32_t*)sizes.data_ptr(), streamOf(dev)),
+        "floatCompressCast", true);
+  return {std::move(comp), std::move(sizes), (int64_t)used};
+}
+
 void set_precision(int64_t probBits) {
   TORCH_CHECK(probBits == 9 || probBits == 10 || probBits == 11, "probBits must be 9, 10 or 11");
   tPrecision = (int)probBits;
@@ -569,6 +607,9 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "decompress_data_accumulate(Tensor[] ts_in, Tensor[] ts_acc, int float_type, bool accumulate=True, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
       &dietgpu_amd::decompress_data_accumulate);
+  m.def(
+      "compress_data_cast(Tensor[] ts_in, int float_type, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
+      &dietgpu_amd::compress_data_cast);
 }
 
 TORCH_LIBRARY(dietgpu, m) {

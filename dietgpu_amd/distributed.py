@@ -105,6 +105,14 @@ class GpuFloatCodec:
         self.dtype = tensors[0].dtype  # (what decompress_accumulate's rows hold: the collectives exchange one dtype)
         return comp, sizes
 
+    def compress_cast(self, tensors, dtype):
+        """float32 tensors -> archives of `dtype` (float16 / bfloat16), rounded in registers: no 16-bit scratch tensor"""
+        from . import ops
+
+        comp, sizes, _ = ops.compress_data_cast(tensors, dtype, self.temp_mem)
+        self.dtype = dtype
+        return comp, sizes
+
     def decompress(self, rows, outs):
         status = torch.zeros((len(rows),), dtype=torch.uint8, device=outs[0].device)
         self.ops.decompress_data(True, rows, outs, False, self.temp_mem, status, None)
@@ -128,10 +136,16 @@ def compressed_all_gather(tensors, codec=None):
     `codec` needs compress(list) -> (uint8 [n, cap], int32 [n]) and
     decompress(list of uint8 rows, list of outputs) -> uint8 status [n]."""
     codec = codec or GpuFloatCodec()
-    world = dist.get_world_size()
-    n = len(tensors)
-    dev = tensors[0].device
     comp, sizes = codec.compress(tensors)
+    raw = sum(t.numel() * t.element_size() for t in tensors)
+    return _all_gather_archives(comp, sizes, lambda r: [torch.empty_like(t) for t in tensors], raw, codec)
+
+
+def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec):
+    """The exchange of compressed_all_gather for rows that are compressed already: `comp` [n, cap] / `sizes` [n] as a
+    codec's compress returns them; `outs_of(r)` -> the n tensors rank r's rows are decompressed into."""
+    world = dist.get_world_size()
+    n = comp.shape[0]
     sizes = sizes.to(torch.int32)
 
     # phase 1: sizes
@@ -149,14 +163,13 @@ def compressed_all_gather(tensors, codec=None):
     gathered = []
     for r in range(world):
         rows = [gathered_payload[r][i, : int(all_sizes[r, i])] for i in range(n)]
-        outs = [torch.empty_like(t) for t in tensors]
+        outs = outs_of(r)
         status = codec.decompress(rows, outs)
         if not bool(status.all().item()):
             raise RuntimeError(f"decompression of rank {r}'s rows failed")
         gathered.append(outs)
-    raw = sum(t.numel() * t.element_size() for t in tensors)
     stats = {
-        "raw_bytes": raw,
+        "raw_bytes": raw_bytes,
         "wire_bytes": n * width,
         "payload_bytes": int(all_sizes[dist.get_rank()].sum().item()),
     }
@@ -208,6 +221,28 @@ def compressed_reduce_scatter(tensor, codec=None):
         "payload_bytes": int(all_sizes[me].sum().item()),
     }
     return shard, stats
+
+
+def compressed_all_reduce(tensor, codec=None):
+    """All-reduce (sum) of a flat fp16 / bf16 tensor, moving compressed bytes both ways and summing in float32.
+
+    Three steps: `compressed_reduce_scatter` (this rank's float32 shard of the sum), the codec's `compress_cast` of that
+    shard back to the input dtype -- the rounding happens inside the compressor, the 16-bit shard never exists -- and the
+    compressed all-gather of the shards.  The result is the sequential float32 sum in rank order of the exactly widened
+    inputs, rounded ONCE to the input dtype (round to nearest even), bit-identical on every rank.  Returns (summed
+    tensor in the input dtype, stats): the stats of the two exchanges added up.  `codec` needs what
+    compressed_reduce_scatter and compressed_all_gather need, and compress_cast(list of float32, dtype) -> (uint8
+    [n, cap], int32 [n])."""
+    if tensor.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("compressed_all_reduce: the tensor must be float16 or bfloat16")
+    codec = codec or GpuFloatCodec()
+    world = dist.get_world_size()
+    shard, rs = compressed_reduce_scatter(tensor, codec)
+    comp, sizes = codec.compress_cast([shard], tensor.dtype)
+    out = torch.empty_like(tensor)
+    rows = out.view(world, shard.numel())
+    _, ag = _all_gather_archives(comp, sizes, lambda r: [rows[r]], shard.numel() * tensor.element_size(), codec)
+    return out, {k: rs[k] + ag[k] for k in rs}
 
 
 # ---------------------------------------------------------------------------

@@ -318,6 +318,43 @@ def compress_data_simple(compress_as_float, ts_in, checksum=False, temp_mem=6710
     return [comp[i, : host[i]].clone() for i in range(len(ts_in))]
 
 
+# ---------------------------------------------------------------- cast-compress
+# (no reference op: dgpu_float_cast_compress, include/dietgpu_amd.h)
+def compress_data_cast(ts_in, dtype, temp_mem=None, out_compressed=None, out_compressed_sizes=None,
+                       prob_bits=K_DEFAULT_PRECISION):
+    """Compresses float32 tensors into ordinary float16 / bfloat16 archives (`dtype`: of the archives): every word is
+    rounded to `dtype` in registers -- round to nearest even, NaN to the canonical quiet NaN with its sign -- and the
+    archive is byte for byte what `compress_data(True, [t.to(dtype)])` writes for the rounded tensor, without the
+    16-bit scratch tensor -> (comp [B, maxSize] u8, sizes [B] i32, temp bytes used), as compress_data.  ts_in is not
+    modified.  There is no `checksum`: a checksum covers the 16-bit words, which never reach memory here."""
+    _check(len(ts_in) > 0)
+    _check(dtype in (torch.float16, torch.bfloat16), "dtype (of the archives) must be float16 or bfloat16")
+    _check(ts_in[0].is_cuda, "tensors must be on the GPU")
+    ft = _DTYPE_TO_FT[dtype]
+    dev = ts_in[0].get_device()
+    for t in ts_in:
+        _check(t.is_cuda and t.is_contiguous() and t.get_device() == dev)
+        _check(t.dtype == torch.float32, "the inputs of a cast call must be float32")
+    if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "compress_data_cast"):
+        torch.ops.dietgpu_amd.set_precision(prob_bits)
+        try:
+            return torch.ops.dietgpu_amd.compress_data_cast(ts_in, ft, temp_mem, out_compressed, out_compressed_sizes)
+        finally:
+            torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+    _, mx = _total_and_max(ts_in)
+    rows, cols = len(ts_in), _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
+    with torch.cuda.device(dev):
+        comp, sizes = _validate_out(out_compressed, out_compressed_sizes, rows, cols, dev, ts_in[0].device)
+        tp, tb = _temp(temp_mem, dev)
+        row = comp.size(1)
+        out_ptrs = (C.c_void_p * rows)(*[comp.data_ptr() + i * row for i in range(rows)])
+        used = C.c_size_t(0)
+        check(lib().dgpu_float_cast_compress(
+            tp, tb, C.byref(used), ft, prob_bits, rows, _ptr_array(ts_in), _u32_array([t.numel() for t in ts_in]),
+            out_ptrs, _ptr(sizes), _stream()))
+    return comp, sizes, int(used.value)
+
+
 # ------------------------------------------------------------------ decompress
 def _validate_status(out_status, out_sizes, n, dev):
     if out_status is not None:

@@ -67,8 +67,8 @@ const char* dgpu_version(void);
  * against this header (the tensor-op library of this repository, a cgo / JNI binding) compares the value it was compiled
  * with against the library it finds at run time, so that a stale build fails at load instead of inside a call.  An entry
  * point that is only ADDED leaves every existing one as it was and does not move the version: a library without the new
- * symbol fails at load too, by symbol resolution, in anything that links it (dgpu_float_decode_accumulate was added
- * at version 8). */
+ * symbol fails at load too, by symbol resolution, in anything that links it (dgpu_float_decode_accumulate and
+ * dgpu_float_cast_compress were added at version 8). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -305,6 +305,30 @@ int dgpu_float_decode_accumulate(
     uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
     void* const* out /* float32 */, const uint32_t* outCapacity /* float words */,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
+
+/* ---- cast-compress (no upstream equivalent) -------------------------------------------
+ * Compresses float32 element i into an ordinary float16 / bfloat16 archive: every word is rounded to `floatType` in
+ * registers, by the histogram pass and by the encoder alike, and the archive is byte for byte what dgpu_float_compress
+ * (useChecksum = 0) writes for the already-rounded tensor -- every decoder of this header reads it.  The sending side
+ * of a compressed exchange whose values are float32 (master weights, gradient accumulators, the float32 sums of
+ * dgpu_float_decode_accumulate) without a 16-bit scratch tensor and the cast kernel that fills it.
+ *   - The rounding, on the float32 bits x: bfloat16 is (x + 0x7fff + ((x >> 16) & 1)) >> 16 -- round to nearest even,
+ *     float32 denormals are not flushed, overflow goes to infinity; float16 is the IEEE conversion, round to nearest
+ *     even, float16 denormals produced, |v| >= 65520 -> infinity, the sign of zero kept.  A NaN of either sign and any
+ *     payload becomes the canonical quiet NaN with the sign kept (sign | 0x7fc0, sign | 0x7e00): never an infinity.
+ *   - floatType is the type of the ARCHIVE: DGPU_FLOAT16 or DGPU_BFLOAT16 (float32 -> float32 is dgpu_float_compress);
+ *     in[i] 4-byte aligned, out[i] 16-byte aligned with room for dgpu_float_max_compressed_size(floatType, inSize[i]),
+ *     probBits 9 / 10 / 11, numInBatch <= 65535, inSize[i] (words) within the size guard of dgpu_float_compress:
+ *     DGPU_ERR_INVALID_ARGUMENT otherwise, before anything is enqueued.  An empty batch returns 0, *tempUsed = 0.
+ *   - There is no useChecksum: a checksum covers the 16-bit words, which never reach memory here.
+ *   - Temp memory: dgpu_float_compress_temp_bytes(floatType, numInBatch, max inSize).  Stride detection, parameter
+ *     cache, work lists, size classes and graph capture are those of dgpu_float_compress; elements of a single block
+ *     run on the 2-block tiles (there is no cast form of the single-block kernels). */
+int dgpu_float_cast_compress(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed,
+    uint32_t floatType /* of the ARCHIVE: DGPU_FLOAT16 or DGPU_BFLOAT16 */, int probBits,
+    uint32_t numInBatch, const void* const* in /* float32 */, const uint32_t* inSize /* words */,
+    void* const* out, uint32_t* outSize_dev, void* stream);
 
 /* ---- float stride batches with capacities (no upstream equivalent) ---------------
  * For exchanging compressed rows at a FIXED width (README.md:68-72,104: compressed collectives): the rows of one
