@@ -21,6 +21,7 @@
 
 #include "format.h"
 #include "kernel_variants.h"
+#include "work_plan.h"
 
 using namespace dgpu;
 
@@ -733,7 +734,7 @@ struct Batch {
   std::vector<uint32_t> sizes;    // input sizes (encode) or output capacities (decode)
   std::vector<uint32_t> inBytes;  // decode, *_bounded entry points: bytes available per compressed input
   uint32_t uniformInBytes = 0;    // ... of a strided decode (0 = unknown)
-  std::vector<uint32_t> work;     // work lists of a batch whose elements differ widely in size (RaggedPlan)
+  std::vector<uint32_t> work;     // work lists of a batch whose elements differ widely in size (work_plan.h)
   uint32_t maxSize = 0;           // the largest size / capacity
 };
 
@@ -945,20 +946,13 @@ uint32_t residentWorkgroups(const KernelVariant<Args...>& v, uint32_t workgroups
 // in-order commit (kernels_encode.h, kSpillStageWordsWide; profiles/r06_ab_encoder_five_per_cu_*.txt).
 constexpr uint32_t kWideStageMaxTiles = 32;
 
-// blocks per encoder tile for a batch whose largest element has `maxSize` symbols; ft: what is encoded (0: raw bytes; a
-// float type, with kCastSource for a cast call, which has no single-block kernels: its single-block elements run on
-// 2-block tiles)
-uint32_t encTileBlocksFor(uint32_t maxSize, uint32_t ft = 0) {
-  const uint32_t blocks = divUp(maxSize, kBlockSize);
-  if (encIsCast(ft) && blocks <= kBlocksPerTinyTile) return kBlocksPerTinyTile;
-  return blocks <= kBlocksPerSingleTile ? kBlocksPerSingleTile
-      : blocks <= kBlocksPerTinyTile    ? kBlocksPerTinyTile
-      : blocks <= kBlocksPerSmallTile   ? kBlocksPerSmallTile
-                                        : kBlocksPerTile;
-}
-uint32_t tilesFor(uint32_t maxSize, uint32_t ft = 0) { return divUp(divUp(maxSize, kBlockSize), encTileBlocksFor(maxSize, ft)); }
-
 uint32_t absentWorkgroupModulo();  // test hook, defined with the C ABI below
+
+// start value of a test / A-B hook: the environment variable, or `otherwise`
+int envInt(const char* name, int otherwise) {
+  const char* e = getenv(name);
+  return e && *e ? atoi(e) : otherwise;
+}
 
 // How the workgroups of the tiled encoder come to their tiles: persistent workgroups with a static ticket map, or one
 // workgroup per tile, dispatched by the hardware in ticket order.  Measured on MI355X
@@ -970,335 +964,19 @@ uint32_t absentWorkgroupModulo();  // test hook, defined with the C ABI below
 //   * k_ans_encode_pair (single-block elements) always runs one workgroup per pair: 133.7 -> 96.8 us.
 // -1 = this policy; dgpu_debug_set_encoder_dispatch / DGPU_ENC_DISPATCH force 0 (persistent) or 1 (hardware) where the
 // kernel exists in both forms (tests, A/B runs).
-std::atomic<int> g_encDispatch{[] {
-  const char* e = getenv("DGPU_ENC_DISPATCH");
-  return e && *e ? atoi(e) : -1;
-}()};
+std::atomic<int> g_encDispatch{envInt("DGPU_ENC_DISPATCH", -1)};
 bool encoderHardwareDispatch(uint32_t numTickets, uint32_t resident) {
   const int m = g_encDispatch.load();
   if (m >= 0) return m != 0;
   return numTickets > resident;  // more tiles than slots: let the hardware balance them
 }
 
-// Batches whose elements differ widely in size -- the tensors of a model in one call: a few matrices, many vectors.
-// The grids of the histogram, the encoder and the decoder are rectangles laid out for the LARGEST element (as
-// upstream's are); with one 32 Mi-word tensor next to 255 small ones that is 262 144 encoder tickets of which 1 279
-// exist, spread over the persistent workgroups by a static map that hands the large tensor's tiles to three of them,
-// and two histogram workgroups for its 64 MiB (tools/ragged_probe.py: 5.7 ms per compress call against 56 us + 37 us
-// for the two size classes on their own).  The host knows the sizes (they arrive as host arrays), so for such a batch
-// it lists the work that exists -- Batch::work, uploaded with the pointers -- and the kernels take their
-// (element, tile / part) from the list instead of from the rectangle:
-//   * tiles: the encoder's element by element, the large elements first (a tile's predecessor has the ticket before
-//     its own, and descriptors and claim words exist for the listed tiles only); the decoder's, which do not depend on
-//     one another, tile-major;
-//   * histogram parts: every element cut into parts of histPartBytes (chosen for the usual number of workgroups over
-//     the WHOLE batch), element-major, so that an element's partial histograms are consecutive.
-// Used when at least a fifth of the rectangle's tiles do not exist (256 bf16 tensors of 0.06 .. 1 Mi words: compress
-// 228 -> 181 us; of 0.5 .. 1 Mi: 247 -> 229; of 0.85 .. 1 Mi the rectangle is 3 % faster: profiles/r05_ab_work_lists.txt);
-// dgpu_debug_set_work_lists forces it on (1: whenever the batch has a size array) or off (0) for tests.
-inline uint64_t divUp64(uint64_t a, uint64_t b) { return (a + b - 1u) / b; }
-inline uint64_t roundUp64(uint64_t a, uint64_t b) { return divUp64(a, b) * b; }
-struct RaggedPlan {
-  bool use = false;
-  // Batch::work of an encode call: [numTiles] x {element << 16 | tile}, [numHistParts] x {element << 16 | part},
-  // [B] x {the element's first ticket = index of its first descriptor and claim word}
-  uint32_t numTiles = 0;
-  uint32_t numHistParts = 0;
-  uint32_t histPartBytes = 0;
-};
-std::atomic<int> g_workLists{[] {
-  const char* e = getenv("DGPU_WORK_LISTS");
-  return e && *e ? atoi(e) : -1;
-}()};
-// tiles of `tileSymbols` symbols; minTiles: 1 where an element without symbols still needs its first tile (decode)
-// elementMajor (encoder): an element's tiles are consecutive -- descriptors and claim words are then indexed by the
-// ticket -- elements in descending size (the large ones start first, the small ones fill the end); *tileBase receives
-// each element's first ticket.  Otherwise (decoder: no dependence between tiles) tile-major.
-// always (ranged decode, which has no rectangle to fall back to): list whatever the policy and the test hook say.
-bool planTileList(const std::vector<uint32_t>& sizes, uint32_t tileSymbols, uint32_t maxTiles, uint32_t minTiles, std::vector<uint32_t>* work,
-                  std::vector<uint32_t>* tileBase = nullptr, bool always = false) {
-  const int mode = always ? 1 : g_workLists.load();
-  const size_t B = sizes.size();
-  if (mode == 0 || B == 0 || B > 65535u || maxTiles > 65536u || tileSymbols == 0) return false;
-  std::vector<uint32_t> tiles(B);
-  uint64_t total = 0;
-  for (size_t b = 0; b < B; ++b) {
-    tiles[b] = std::max(divUp(sizes[b], tileSymbols), minTiles);
-    total += tiles[b];
-  }
-  if (mode != 1 && (B < 2 || maxTiles < 2 || total * 5u > (uint64_t)B * maxTiles * 4u)) return false;
-  if (total > 0x7fffffffull) return false;
-  std::vector<uint32_t> order(B);
-  for (size_t b = 0; b < B; ++b) order[b] = (uint32_t)b;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return tiles[x] > tiles[y]; });
-  const size_t first = work->size();
-  work->reserve(first + (size_t)total);
-  if (tileBase) {
-    tileBase->assign(B, 0u);
-    for (size_t i = 0; i < B; ++i) {
-      const uint32_t b = order[i];
-      (*tileBase)[b] = (uint32_t)(work->size() - first);
-      for (uint32_t r = 0; r < tiles[b]; ++r) work->push_back((b << 16) | r);
-    }
-  } else {
-    for (uint32_t r = 0; r < maxTiles; ++r) {
-      for (size_t i = 0; i < B && tiles[order[i]] > r; ++i) work->push_back((order[i] << 16) | r);
-    }
-  }
-  return true;
-}
-constexpr uint32_t kHistTargetWgsForLists = 512, kHistTargetWgsForListsRaw = 768;
-void planHistList(const std::vector<uint32_t>& sizes, uint32_t wordBytes, bool raw, RaggedPlan* plan, std::vector<uint32_t>* work) {
-  uint64_t totalBytes = 0;
-  for (uint32_t sz : sizes) totalBytes += (uint64_t)sz * wordBytes;
-  const uint64_t target = raw ? kHistTargetWgsForListsRaw : kHistTargetWgsForLists;
-  const uint64_t partBytes = std::max<uint64_t>(32u * 1024u, roundUp64(divUp64(totalBytes, target), 16u * 1024u));
-  plan->histPartBytes = (uint32_t)std::min<uint64_t>(partBytes, 0x40000000ull);
-  const size_t before = work->size();
-  for (size_t b = 0; b < sizes.size(); ++b) {
-    const uint64_t bytes = (uint64_t)sizes[b] * wordBytes;
-    const uint32_t parts = (uint32_t)std::max<uint64_t>(1u, divUp64(bytes, plan->histPartBytes));
-    for (uint32_t p = 0; p < parts; ++p) work->push_back(((uint32_t)b << 16) | p);
-  }
-  plan->numHistParts = (uint32_t)(work->size() - before);
-}
-// Work lists of an encode call: false = the rectangles.
-bool planEncode(const std::vector<uint32_t>& sizes, uint32_t floatType, uint32_t maxSize, bool needHist, RaggedPlan* plan, std::vector<uint32_t>* work) {
-  const uint32_t tileBlocks = encTileBlocksFor(maxSize, floatType);
-  if (tileBlocks == kBlocksPerSingleTile) return false;  // single-block batches: one wavefront per element, nothing to list
-  std::vector<uint32_t> tileBase;
-  if (!planTileList(sizes, tileBlocks * kBlockSize, tilesFor(maxSize, floatType), 0u, work, &tileBase)) return false;
-  plan->use = true;
-  plan->numTiles = (uint32_t)work->size();
-  if (needHist) planHistList(sizes, floatType ? floatWordBytes(encArchiveType(floatType)) : 1u, floatType == 0, plan, work);
-  work->insert(work->end(), tileBase.begin(), tileBase.end());
-  return true;
-}
-
-// SIZE CLASSES inside one batch.  The tile geometry of a call -- pairs of single-block elements per wavefront, tiles of 2,
-// 4 or 8 blocks -- used to be chosen once, from the largest element (encTileBlocksFor(maxSize); upstream does the same:
-// one grid laid out for maxSize, GpuANSEncode.cuh:753-771).  One large tensor next to thousands of small ones then ran
-// every small element on an 8-block tile -- seven of its eight half-waves idle, where the pair kernels are 1.4-2 x faster
-// on such elements.  The host already lists the work of such a batch; it now lists it PER CLASS and launches each class
-// on the kernels of its own geometry, the classes one after the other on the caller's stream (large elements first).
-// All kernels index the batch's arrays by the element's own index, so a class is nothing but its lists: tiles and
-// histogram parts (EncodeArgs::workMap, HistFuse::workMap) or, for the single-block class, the elements to pair up.
-// A class of fewer than kMinClassElements elements joins the next larger one (a launch costs more than their idle
-// lanes), and a batch whose smaller classes together hold fewer than kMinSplitElements elements is not split at all:
-// in ONE launch its few small elements run beside the large ones' tiles (1 x 32 Mi + 255 x 2 Ki bf16: 71 us together
-// against 56 + 38 one after the other, profiles/r05_ab_work_lists.txt).
-constexpr uint32_t kMinClassElements = 32, kMinSplitElements = 256;
-struct EncodeClass {
-  uint32_t tileBlocks = 0;
-  uint32_t maxSize = 0;                                       // of the class's elements
-  uint32_t tilesAt = 0, numTiles = 0;                         // tiles of >= 2 blocks: [numTiles] element << 16 | tile, element by element
-  uint32_t histAt = 0, numHistParts = 0, histPartBytes = 0;   // ... [numHistParts] element << 16 | part
-  uint32_t tileBaseAt = 0;                                    // ... [B] first ticket of each of the class's elements
-  uint32_t elemsAt = 0, numElems = 0;                         // single-block class: [numElems] the elements
-};
-std::atomic<int> g_sizeClasses{[] {
-  const char* e = getenv("DGPU_SIZE_CLASSES");
-  return e && *e ? atoi(e) : -1;
-}()};
-// Splits the batch into size classes (false: one geometry for the call, as before).  `classOf(size)` -> blocks per tile /
-// workgroup of an element of that size; `pairsOk`: the single-block class has kernels of its own (not float32 encode).
-template <typename ClassOf>
-bool classifyBySize(const std::vector<uint32_t>& sizes, ClassOf classOf, bool pairsOk, std::vector<uint32_t>* classOfElem,
-                    std::vector<uint32_t>* classesOut) {
-  const int mode = g_sizeClasses.load();
-  const size_t B = sizes.size();
-  if (mode == 0 || g_workLists.load() == 0 || B < 2 || B > 65535u) return false;
-  std::map<uint32_t, uint32_t> count;
-  classOfElem->resize(B);
-  for (size_t b = 0; b < B; ++b) {
-    uint32_t c = classOf(sizes[b]);
-    if (c == 1u && !pairsOk) c = 2u;
-    (*classOfElem)[b] = c;
-    count[c]++;
-  }
-  if (count.size() < 2) return false;
-  // small classes join the next larger one that exists
-  for (auto it = count.begin(); it != count.end();) {
-    auto next = std::next(it);
-    if (next != count.end() && it->second < (mode == 1 ? 1u : kMinClassElements)) {
-      for (size_t b = 0; b < B; ++b) {
-        if ((*classOfElem)[b] == it->first) (*classOfElem)[b] = next->first;
-      }
-      next->second += it->second;
-      it = count.erase(it);
-    } else {
-      it = next;
-    }
-  }
-  if (count.size() < 2) return false;
-  uint32_t small = 0;
-  for (auto& kv : count) {
-    if (kv.first != count.rbegin()->first) small += kv.second;
-  }
-  if (mode != 1 && small < kMinSplitElements) return false;
-  classesOut->clear();
-  for (auto it = count.rbegin(); it != count.rend(); ++it) classesOut->push_back(it->first);  // large elements first
-  return true;
-}
-bool planEncodeClasses(const std::vector<uint32_t>& sizes, uint32_t floatType, std::vector<EncodeClass>* classes, std::vector<uint32_t>* work) {
-  std::vector<uint32_t> classOfElem, order;
-  if (!classifyBySize(sizes, [](uint32_t sz) { return encTileBlocksFor(sz); }, floatType != kFloat32 && !encIsCast(floatType), &classOfElem, &order)) return false;
-  const size_t B = sizes.size();
-  const uint32_t wordBytes = floatType ? floatWordBytes(encArchiveType(floatType)) : 1u;  // (a cast call's parts go by the archive's words)
-  classes->clear();
-  for (uint32_t c : order) {
-    EncodeClass k;
-    k.tileBlocks = c;
-    std::vector<uint32_t> elems;
-    for (size_t b = 0; b < B; ++b) {
-      if (classOfElem[b] == c) {
-        elems.push_back((uint32_t)b);
-        k.maxSize = std::max(k.maxSize, sizes[b]);
-      }
-    }
-    if (c == kBlocksPerSingleTile) {
-      k.elemsAt = (uint32_t)work->size();
-      k.numElems = (uint32_t)elems.size();
-      work->insert(work->end(), elems.begin(), elems.end());
-    } else {
-      // tiles element by element, the class's larger elements first; histogram parts sized for the usual number of
-      // workgroups over the CLASS (the classes run one after the other, each should fill the chip)
-      std::stable_sort(elems.begin(), elems.end(), [&](uint32_t x, uint32_t y) { return sizes[x] > sizes[y]; });
-      const uint32_t tileSymbols = c * kBlockSize;
-      std::vector<uint32_t> tileBase(B, 0u);
-      k.tilesAt = (uint32_t)work->size();
-      uint64_t classBytes = 0;
-      for (uint32_t b : elems) {
-        tileBase[b] = (uint32_t)(work->size() - k.tilesAt);
-        const uint32_t tiles = divUp(sizes[b], tileSymbols);
-        if (tiles > 65536u) {
-          work->clear();
-          classes->clear();
-          return false;
-        }
-        for (uint32_t r = 0; r < tiles; ++r) work->push_back((b << 16) | r);
-        classBytes += (uint64_t)sizes[b] * wordBytes;
-      }
-      k.numTiles = (uint32_t)(work->size() - k.tilesAt);
-      const uint64_t target = floatType == 0 ? kHistTargetWgsForListsRaw : kHistTargetWgsForLists;
-      const uint64_t partBytes = std::max<uint64_t>(32u * 1024u, roundUp64(divUp64(classBytes, target), 16u * 1024u));
-      k.histPartBytes = (uint32_t)std::min<uint64_t>(partBytes, 0x40000000ull);
-      k.histAt = (uint32_t)work->size();
-      for (uint32_t b : elems) {
-        const uint32_t parts = (uint32_t)std::max<uint64_t>(1u, divUp64((uint64_t)sizes[b] * wordBytes, k.histPartBytes));
-        if (parts > 65536u) {
-          work->clear();
-          classes->clear();
-          return false;
-        }
-        for (uint32_t q = 0; q < parts; ++q) work->push_back((b << 16) | q);
-      }
-      k.numHistParts = (uint32_t)(work->size() - k.histAt);
-      k.tileBaseAt = (uint32_t)work->size();
-      work->insert(work->end(), tileBase.begin(), tileBase.end());
-    }
-    classes->push_back(k);
-  }
-  return true;
-}
-
-// ... and the decoder's classes, from the output capacities (its tiles do not depend on one another: tile-major lists)
-struct DecodeClass {
-  uint32_t tileBlocks = 0, maxBlocks = 0;
-  uint32_t tilesAt = 0, numTiles = 0;   // tiles of >= 2 blocks: [numTiles] element << 16 | tile
-  uint32_t elemsAt = 0, numElems = 0;   // single-block class: [numElems] the elements
-};
-uint32_t decTileBlocksFor(uint32_t maxBlocks);
-bool planDecodeClasses(const std::vector<uint32_t>& caps, std::vector<DecodeClass>* classes, std::vector<uint32_t>* work) {
-  std::vector<uint32_t> classOfElem, order;
-  if (!classifyBySize(caps, [](uint32_t cap) { return decTileBlocksFor(divUp(cap, kBlockSize)); }, true, &classOfElem, &order)) return false;
-  const size_t B = caps.size();
-  classes->clear();
-  for (uint32_t c : order) {
-    DecodeClass k;
-    k.tileBlocks = c;
-    std::vector<uint32_t> elems;
-    for (size_t b = 0; b < B; ++b) {
-      if (classOfElem[b] == c) {
-        elems.push_back((uint32_t)b);
-        k.maxBlocks = std::max(k.maxBlocks, divUp(caps[b], kBlockSize));
-      }
-    }
-    if (c == 1u) {
-      k.elemsAt = (uint32_t)work->size();
-      k.numElems = (uint32_t)elems.size();
-      work->insert(work->end(), elems.begin(), elems.end());
-    } else {
-      std::stable_sort(elems.begin(), elems.end(), [&](uint32_t x, uint32_t y) { return caps[x] > caps[y]; });
-      const uint32_t tileSymbols = c * kBlockSize;
-      const uint32_t maxTiles = std::max(1u, divUp(k.maxBlocks, c));
-      if (maxTiles > 65536u) {
-        work->clear();
-        classes->clear();
-        return false;
-      }
-      k.tilesAt = (uint32_t)work->size();
-      for (uint32_t r = 0; r < maxTiles; ++r) {
-        for (uint32_t b : elems) {
-          if (std::max(divUp(caps[b], tileSymbols), 1u) <= r) break;  // (descending capacities)
-          work->push_back((b << 16) | r);
-        }
-      }
-      k.numTiles = (uint32_t)(work->size() - k.tilesAt);
-    }
-    classes->push_back(k);
-  }
-  return true;
-}
-
-// A training or collective loop compresses the same list of tensors step after step: the last plan of each kind is kept
-// per host thread and reused when the sizes (and everything else the plan depends on) are the same -- planning a batch
-// of 32 769 tensors costs ~100 us of host time, comparing its sizes 10.
-template <typename Class>
-struct ClassPlanCache {
-  std::vector<uint32_t> sizes, work;
-  std::vector<Class> classes;
-  uint32_t floatType = 0xffffffffu;
-  int modeClasses = -2, modeLists = -2;
-  bool valid = false, split = false;
-  bool matches(const std::vector<uint32_t>& sz, uint32_t ft) const {
-    return valid && floatType == ft && modeClasses == g_sizeClasses.load() && modeLists == g_workLists.load() && sizes.size() == sz.size() &&
-        (sz.empty() || memcmp(sizes.data(), sz.data(), sz.size() * 4u) == 0);
-  }
-  void remember(const std::vector<uint32_t>& sz, uint32_t ft, bool didSplit, const std::vector<Class>& cl, const std::vector<uint32_t>& wk) {
-    sizes = sz, floatType = ft, split = didSplit, classes = cl, work = wk;
-    modeClasses = g_sizeClasses.load(), modeLists = g_workLists.load();
-    valid = true;
-  }
-};
-bool planEncodeClassesCached(const std::vector<uint32_t>& sizes, uint32_t floatType, std::vector<EncodeClass>* classes, std::vector<uint32_t>* work) {
-  if (sizes.size() < kMinSplitElements) return planEncodeClasses(sizes, floatType, classes, work);  // (cheap to plan, and rarely split)
-  static thread_local ClassPlanCache<EncodeClass> cache;
-  if (!cache.matches(sizes, floatType)) {
-    std::vector<EncodeClass> cl;
-    std::vector<uint32_t> wk;
-    const bool split = planEncodeClasses(sizes, floatType, &cl, &wk);
-    cache.remember(sizes, floatType, split, cl, wk);
-  }
-  if (!cache.split) return false;
-  *classes = cache.classes;
-  *work = cache.work;
-  return true;
-}
-bool planDecodeClassesCached(const std::vector<uint32_t>& caps, std::vector<DecodeClass>* classes, std::vector<uint32_t>* work) {
-  if (caps.size() < kMinSplitElements) return planDecodeClasses(caps, classes, work);
-  static thread_local ClassPlanCache<DecodeClass> cache;
-  if (!cache.matches(caps, 0u)) {
-    std::vector<DecodeClass> cl;
-    std::vector<uint32_t> wk;
-    const bool split = planDecodeClasses(caps, &cl, &wk);
-    cache.remember(caps, 0u, split, cl, wk);
-  }
-  if (!cache.split) return false;
-  *classes = cache.classes;
-  *work = cache.work;
-  return true;
-}
+// Work planning -- tile geometry, the work lists of ragged batches, size classes -- is host arithmetic in work_plan.h.
+// Its two test hooks live here: dgpu_debug_set_work_lists / DGPU_WORK_LISTS and dgpu_debug_set_size_classes /
+// DGPU_SIZE_CLASSES force lists / classes on (1: wherever the batch has a size array) or off (0); -1 = the policy.
+std::atomic<int> g_workLists{envInt("DGPU_WORK_LISTS", -1)};
+std::atomic<int> g_sizeClasses{envInt("DGPU_SIZE_CLASSES", -1)};
+PlanPolicy planPolicy() { return {g_workLists.load(), g_sizeClasses.load()}; }
 
 bool histAccumulates(uint32_t B, uint32_t maxBytes, bool raw) {
   return B <= kHistAccMaxBatch && histPartsAccFor(B, maxBytes) > histPartsFor(B, maxBytes, raw);
@@ -1359,10 +1037,7 @@ bool histogramLoadsNonTemporal(uint32_t ft) {
 // one of each element sums and normalises them and clears the tile descriptors +
 // ticket for the encode kernel.
 // (DGPU_TWO_LEVEL_LOOKBACK=0: the single level everywhere -- A/B runs and tests)
-std::atomic<int> g_twoLevelLookback{[] {
-  const char* e = getenv("DGPU_TWO_LEVEL_LOOKBACK");
-  return e && *e ? atoi(e) : 1;
-}()};
+std::atomic<int> g_twoLevelLookback{envInt("DGPU_TWO_LEVEL_LOOKBACK", 1)};
 struct EncodeShared {
   uint32_t* checksumTemp = nullptr;  // [B] the batch's checksums (computed by the first class's call)
   uint4* table = nullptr;            // [B][256] encoder tables, indexed by the element's own index
@@ -1371,22 +1046,18 @@ struct EncodeShared {
 };
 int encodeCommon(
     TempArena& arena, StreamLease& lease, hipStream_t stream, int P, bool useChecksum, uint32_t B,
-    const BatchView& in, const BatchView& archives, uint32_t sourceType, uint32_t maxSize,
-    const uint32_t* hist_dev /*may be null*/, uint32_t* outSize_dev,
-    uint32_t outCapacity = 0xffffffffu /* bytes at every archive pointer; block data beyond it is dropped */,
-    const RaggedPlan* plan = nullptr, const uint32_t* work_dev = nullptr /* the plan's lists on the device */,
-    const EncodeClass* cls = nullptr /* one size class of the batch (its lists in work_dev); maxSize is the class's */,
-    EncodeShared* shared = nullptr /* what the classes of one call share */) {
+    const BatchView& in, const BatchView& archives, uint32_t sourceType,
+    const LaunchGroup& group /* the whole batch, or one size class of it */, const uint32_t* work_dev /* the plan's lists on the device */,
+    EncodeShared& shared /* what the groups of one call share */, const uint32_t* hist_dev /*may be null*/, uint32_t* outSize_dev,
+    uint32_t outCapacity /* bytes at every archive pointer; block data beyond it is dropped */) {
   const uint32_t floatType = encArchiveType(sourceType);
   const uint32_t wordBytes = floatType ? floatWordBytes(floatType) : 1u;
-  const uint32_t tileBlocks = cls ? cls->tileBlocks : encTileBlocksFor(maxSize, sourceType);
-  const uint32_t maxTiles = cls ? std::max(1u, divUp(divUp(maxSize, kBlockSize), tileBlocks)) : tilesFor(maxSize, sourceType);
+  const uint32_t tileBlocks = group.tileBlocks, maxTiles = group.maxTiles, maxSize = group.maxSize;
 
-  uint32_t* checksumTemp = shared ? shared->checksumTemp : nullptr;
+  uint32_t* checksumTemp = shared.checksumTemp;
   if (useChecksum && !checksumTemp) {
     DGPU_ALLOC(ck, uint32_t, arena, B);
-    checksumTemp = ck;
-    if (shared) shared->checksumTemp = ck;
+    checksumTemp = shared.checksumTemp = ck;
     DGPU_HIP(hipMemsetAsync(checksumTemp, 0, (size_t)B * 4, stream));
     // Float quirk kept from the reference (GpuFloatCompress.cuh:466-468): the
     // size in float WORDS is consumed as a BYTE count by the checksum.
@@ -1399,24 +1070,21 @@ int encodeCommon(
   // Encoder tables [B][256] x 16 bytes, normalisation -> encoder.  Not for batches of single-block elements: there
   // the table would be as many bytes as the element's symbols, and k_ans_encode_pair derives it from the pdf table in
   // the archive header instead.
-  uint4* table = shared ? shared->table : nullptr;
+  uint4* table = shared.table;
   if (tileBlocks != kBlocksPerSingleTile && !table) {
     DGPU_ALLOC(tb, uint4, arena, (size_t)B * kNumSymbols);
-    table = tb;
-    if (shared) shared->table = tb;
+    table = shared.table = tb;
   }
-  // Work lists (descriptors and claim words for the tiles that exist only): a batch whose elements differ widely in
-  // size (plan), or one size class of a batch (cls)
-  const bool lists = cls ? tileBlocks != kBlocksPerSingleTile : (plan && plan->use && work_dev);
-  const uint32_t numListedTiles = !lists ? 0u : (cls ? cls->numTiles : plan->numTiles);
-  const uint32_t numListedHistParts = !lists ? 0u : (cls ? cls->numHistParts : plan->numHistParts);
-  const uint32_t listedHistPartBytes = !lists ? 0u : (cls ? cls->histPartBytes : plan->histPartBytes);
-  const uint32_t* tilesList = !lists ? nullptr : (cls ? work_dev + cls->tilesAt : work_dev);
-  const uint32_t* histPartsList = !lists ? nullptr : (cls ? work_dev + cls->histAt : work_dev + (size_t)plan->numTiles);
-  const uint32_t* tileBaseList = !lists ? nullptr : (cls ? work_dev + cls->tileBaseAt : work_dev + (size_t)plan->numTiles + plan->numHistParts);
+  // Work lists (descriptors and claim words for the tiles that exist only) of a listed group; an unlisted group's
+  // fields are zero
+  const bool lists = group.listed && tileBlocks != kBlocksPerSingleTile;
+  const uint32_t numListedTiles = group.numTiles, numListedHistParts = group.numHistParts, listedHistPartBytes = group.histPartBytes;
+  const uint32_t* tilesList = lists ? work_dev + group.tilesAt : nullptr;
+  const uint32_t* histPartsList = lists ? work_dev + group.histAt : nullptr;
+  const uint32_t* tileBaseList = lists ? work_dev + group.tileBaseAt : nullptr;
   // (the single-block class of a batch: the elements to pair up)
-  const uint32_t* elemMap = (cls && tileBlocks == kBlocksPerSingleTile) ? work_dev + cls->elemsAt : nullptr;
-  const uint32_t numElems = elemMap ? cls->numElems : B;
+  const uint32_t* elemMap = (group.listed && !lists) ? work_dev + group.elemsAt : nullptr;
+  const uint32_t numElems = elemMap ? group.numElems : B;
   DGPU_ALLOC(tileDesc, uint64_t, arena, lists ? std::max<size_t>(numListedTiles, 1u) : (size_t)B * std::max(maxTiles, 1u));
   DGPU_ALLOC(claims, uint32_t, arena, lists ? std::max<size_t>(numListedTiles, 1u) : (size_t)B * std::max(maxTiles, 1u));
   // second level of the look-back for elements of more than 64 tiles (kernels_encode.h, lookBackTwoLevel): rectangles only
@@ -1458,12 +1126,12 @@ int encodeCommon(
     // (the size classes of one call run one after the other on the stream: they share the region of the first one
     // that is large enough)
     const size_t spillWords = (size_t)resident * slotsPerWg * encSpillSlotWords(P);
-    if (shared && shared->spill && shared->spillWords >= spillWords) {
-      spill = shared->spill;
+    if (shared.spill && shared.spillWords >= spillWords) {
+      spill = shared.spill;
     } else {
       DGPU_ALLOC(sp, uint16_t, arena, spillWords);
-      spill = sp;
-      if (shared) shared->spill = sp, shared->spillWords = spillWords;
+      spill = shared.spill = sp;
+      shared.spillWords = spillWords;
     }
     if (pairs || hwDispatch) {
       // one workgroup per pair / tile: the slots are a POOL with a pair for every wavefront that can be resident,
@@ -1573,7 +1241,7 @@ int encodeCommon(
 }
 
 // Shared tail of the encode entry points (ft: 0 for raw bytes): the batch as stride views or uploaded pointers, with
-// the work lists of its size classes or of a ragged batch, then encodeCommon once per class or once for the batch.
+// the work lists of its plan (work_plan.h), then encodeCommon once per launch group.
 int encodeBatch(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b,
     const uint32_t* histogram_dev /*may be null*/, uint32_t* outSize_dev, hipStream_t stream,
@@ -1581,26 +1249,15 @@ int encodeBatch(
   StreamLease streamLease(stream);
   TempArena arena(temp_dev, tempBytes, streamLease);
   DeviceBatch d;
-  RaggedPlan plan;
-  std::vector<EncodeClass> classes;
-  int rc = resolveBatch(b, false, streamLease, &d, [&] {
-    if (histogram_dev || !planEncodeClassesCached(b.sizes, ft, &classes, &b.work)) {
-      planEncode(b.sizes, ft, b.maxSize, histogram_dev == nullptr, &plan, &b.work);
-    }
-  });
+  std::vector<LaunchGroup> groups{encodeRectangle(b.maxSize, ft)};
+  int rc = resolveBatch(b, false, streamLease, &d, [&] { planEncodeCall(planPolicy(), b.sizes, ft, b.maxSize, histogram_dev != nullptr, &groups, &b.work); });
   if (rc) return rc;
   // (float inputs: no exponent plane in temp memory, the encoder splits the float words itself)
-  if (classes.empty()) {
-    rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, b.maxSize, histogram_dev, outSize_dev, outCapacity,
-                      &plan, d.work);
-  } else {
-    // every size class on the kernels of its own geometry, one after the other (EncodeClass)
-    EncodeShared shared;
-    for (const EncodeClass& c : classes) {
-      rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, c.maxSize, nullptr, outSize_dev, outCapacity,
-                        nullptr, d.work, &c, &shared);
-      if (rc) break;
-    }
+  // every group on the kernels of its own geometry, one after the other
+  EncodeShared shared;
+  for (const LaunchGroup& g : groups) {
+    rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, g, d.work, shared, histogram_dev, outSize_dev, outCapacity);
+    if (rc) break;
   }
   if (tempUsed) *tempUsed = arena.requested();
   return rc;
@@ -1635,18 +1292,7 @@ int floatCompressImpl(
 // Zipf bytes -1 %.  It needs enough elements to keep the eight XCDs level (16 x 8 Mi: +17 % for the decoder alone, a
 // batch of one: everything on one XCD), so small batches keep the element-major order.  -1 = this policy;
 // dgpu_debug_set_decoder_order / DGPU_DEC_ORDER force an order (tests, A/B runs).
-// blocks per decoder tile for a batch whose largest capacity has `maxBlocks` blocks: elements of up to 8 blocks:
-// 4-block workgroups, of up to 2 blocks: one wavefront (see kDecBlocksPerSmallTile)
-uint32_t decTileBlocksFor(uint32_t maxBlocks) {
-  return maxBlocks <= 1u ? kDecBlocksPerSingleTile
-      : maxBlocks <= 2u  ? kDecBlocksPerTinyTile
-      : maxBlocks <= 8u  ? kDecBlocksPerSmallTile
-                         : kDecBlocksPerTile;
-}
-std::atomic<int> g_decOrder{[] {
-  const char* e = getenv("DGPU_DEC_ORDER");
-  return e && *e ? atoi(e) : -1;
-}()};
+std::atomic<int> g_decOrder{envInt("DGPU_DEC_ORDER", -1)};
 uint32_t decodeOrder(uint32_t B) {
   const int forced = g_decOrder.load();
   if (forced >= 0 && forced <= (int)kDecOrderXcd) return (uint32_t)forced;
@@ -1667,6 +1313,21 @@ DecodeArgs decodeArgs(const Batch& b, const DeviceBatch& d, uint32_t ft, uint8_t
   return a;
 }
 
+// One launch group of a decode call, in any form: the rectangle in the order of decodeOrder (padded to whole rounds of
+// the eight XCDs where they walk their own elements), or the group's list; single-block elements (k_ans_decode_pair,
+// every capacity <= 4096 symbols) run one workgroup per pair of elements.
+int launchDecode(DecodeArgs d, const LaunchGroup& g, const uint32_t* work_dev, DecodeForm form, int P, hipStream_t stream) {
+  const bool pairs = g.tileBlocks == kDecBlocksPerSingleTile;
+  const uint32_t B = d.numInBatch;
+  d.maxTiles = g.maxTiles;
+  d.order = g.listed ? kDecOrderMap : decodeOrder(B);
+  d.workMap = g.listed ? work_dev + (pairs ? g.elemsAt : g.tilesAt) : nullptr;
+  d.numListed = g.numElems;
+  const uint32_t tiles = g.listed ? std::max(g.numTiles, 1u) : (d.order == kDecOrderXcd ? roundUp(B, 8u) : B) * g.maxTiles;
+  const uint32_t grid = pairs ? ((g.listed ? g.numElems : B) + 1u) / 2u : tiles;
+  return launchVariant(decoderVariant(P, d.floatType, g.tileBlocks, form), dim3(grid), stream, d);
+}
+
 int decodeImpl(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b, uint8_t* outSuccess_dev,
     uint32_t* outSize_dev, hipStream_t stream, int32_t* errBatch) {
@@ -1685,18 +1346,8 @@ int decodeImpl(
 
   TempArena arena(temp_dev, tempBytes, streamLease);
   DeviceBatch dev;
-  uint32_t numListedTiles = 0;
-  std::vector<DecodeClass> classes;
-  const uint32_t maxBlocks = divUp(maxCapacity, kBlockSize);
-  const uint32_t tileBlocks = decTileBlocksFor(maxBlocks);
-  const uint32_t maxTiles = std::max(1u, divUp(maxBlocks, tileBlocks));
-  // (capacities that differ widely: only the tiles inside each element's capacity are launched, see RaggedPlan)
-  rc = resolveBatch(b, true, streamLease, &dev, [&] {
-    if (!planDecodeClassesCached(b.sizes, &classes, &b.work) && tileBlocks != kDecBlocksPerSingleTile &&
-        planTileList(b.sizes, tileBlocks * kBlockSize, maxTiles, 1u, &b.work)) {
-      numListedTiles = (uint32_t)b.work.size();
-    }
-  });
+  std::vector<LaunchGroup> groups{decodeRectangle(divUp(maxCapacity, kBlockSize), true)};
+  rc = resolveBatch(b, true, streamLease, &dev, [&] { planDecodeCall(planPolicy(), b.sizes, maxCapacity, true, &groups, &b.work); });
   if (rc) return rc;
 
   uint32_t* sizesForChecksum = outSize_dev;
@@ -1712,32 +1363,10 @@ int decodeImpl(
     }
   }
 
-  DecodeArgs d = decodeArgs(b, dev, ft, successForChecksum, sizesForChecksum);
-  // (k_ans_decode_pair, every capacity <= 4096 symbols: one workgroup per pair of elements)
-  auto launch = [&](uint32_t blocks, uint32_t tiles, uint32_t elems) {
-    return launchVariant(decoderVariant(P, ft, blocks), dim3(blocks == kDecBlocksPerSingleTile ? (elems + 1u) / 2u : tiles), stream, d);
-  };
-  // every size class of the batch on the decoder of its own geometry, one after the other (DecodeClass)
-  for (const DecodeClass& c : classes) {
-    d.maxTiles = std::max(1u, divUp(c.maxBlocks, c.tileBlocks));
-    d.order = kDecOrderMap;
-    d.workMap = dev.work + (c.tileBlocks == 1u ? c.elemsAt : c.tilesAt);
-    d.numListed = c.numElems;
-    rc = launch(c.tileBlocks, std::max(c.numTiles, 1u), c.numElems);
-    if (rc) return rc;
-  }
-  if (classes.empty()) {
-    d.maxTiles = maxTiles;
-    d.order = decodeOrder(B);
-    d.workMap = nullptr;
-    d.numListed = 0;
-    uint32_t grid = (d.order == kDecOrderXcd ? roundUp(B, 8u) : B) * maxTiles;
-    if (dev.work && numListedTiles) {
-      d.order = kDecOrderMap;
-      d.workMap = dev.work;
-      grid = numListedTiles;
-    }
-    rc = launch(tileBlocks, grid, B);
+  const DecodeArgs d = decodeArgs(b, dev, ft, successForChecksum, sizesForChecksum);
+  // every group on the decoder of its own geometry, one after the other
+  for (const LaunchGroup& g : groups) {
+    rc = launchDecode(d, g, dev.work, DecodeForm::kWhole, P, stream);
     if (rc) return rc;
   }
 
@@ -1788,10 +1417,9 @@ int decodeImpl(
 }
 
 // Ranged decode (k_ans_decode_range): blocks [firstBlock[i], firstBlock[i] + numBlocks[i]) of every element, into a
-// buffer that holds the range.  One geometry per call, chosen from the largest range; the work list holds the tiles of
-// each range, counted from its first block: as many as the request and the capacity allow (the element may turn out to
-// end earlier -- those workgroups leave after the header, as the tiles beyond a short element do in a whole decode).
-// firstBlock and numBlocks travel in front of the list.  No temp memory, no host synchronisation.
+// buffer that holds the range.  The work list (planRangeCall) holds the tiles the request and the capacity allow; the
+// element may turn out to end earlier -- those workgroups leave after the header, as the tiles beyond a short element do
+// in a whole decode.  No temp memory, no host synchronisation.
 int decodeRangeImpl(
     size_t* tempUsed, uint32_t ft, int P, uint32_t B, const void* const* in, const uint32_t* inBytes,
     const uint32_t* firstBlock, const uint32_t* numBlocks, void* const* out, const uint32_t* outCapacity,
@@ -1806,42 +1434,24 @@ int decodeRangeImpl(
   if (rc) return rc;
   // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
   DGPU_REQUIRE(b.maxSize <= 0xfffff000u, "ranged decode: outCapacity must not exceed 0xfffff000");
-  std::vector<uint32_t> rangeSymbols(B);  // what the tiles of element i have to cover (0: no tile)
-  uint32_t maxBlocks = 0;
-  for (uint32_t i = 0; i < B; ++i) {
-    // (an element that asks for blocks has tile 0, which reports it, even with no capacity at all)
-    const uint32_t blocks = numBlocks[i] ? std::max(1u, std::min(numBlocks[i], divUp(outCapacity[i], kBlockSize))) : 0u;
-    rangeSymbols[i] = blocks * kBlockSize;
-    maxBlocks = std::max(maxBlocks, blocks);
-  }
-  const uint32_t tileBlocks = maxBlocks <= 2u * kDecBlocksPerSmallTile ? kDecBlocksPerSmallTile : kDecBlocksPerTile;  // as decTileBlocksFor
-  b.work.assign(firstBlock, firstBlock + B);
-  b.work.insert(b.work.end(), numBlocks, numBlocks + B);
-  if (maxBlocks == 0u) {
-    b.work.push_back(0xffffffffu);  // nothing but empty requests: one workgroup, which reports them
-  } else if (!planTileList(rangeSymbols, tileBlocks * kBlockSize, divUp(maxBlocks, tileBlocks), 0u, &b.work, nullptr, true)) {
+  LaunchGroup group;
+  if (!planRangeCall(B, firstBlock, numBlocks, outCapacity, &group, &b.work)) {
     return fail(DGPU_ERR_INVALID_ARGUMENT, "ranged decode: the ranges have too many tiles for one call");
   }
-  const uint32_t numTiles = (uint32_t)(b.work.size() - 2u * (size_t)B);
 
   StreamLease streamLease(stream);
   DeviceBatch dev;
   rc = resolveBatch(b, true, streamLease, &dev);
   if (rc) return rc;
   DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
-  d.maxTiles = std::max(1u, divUp(maxBlocks, tileBlocks));
-  d.order = kDecOrderMap;
   d.firstBlock = dev.work;
   d.numBlocks = dev.work + B;
-  d.workMap = dev.work + 2u * (size_t)B;
-  d.numListed = 0;
-  return launchVariant(decoderVariant(P, ft, tileBlocks, DecodeForm::kRanged), dim3(numTiles), stream, d);
+  return launchDecode(d, group, dev.work, DecodeForm::kRanged, P, stream);
 }
 
 // Decode-accumulate (k_ans_decode_accum): every archive widened to float32 and stored to (accumulate == 0) or added into
-// (1) its float32 accumulator.  One geometry per call, from the largest capacity (16-block tiles, 4-block tiles for
-// capacities of up to 8 blocks); the grid is the rectangle of a whole decode, or the tile list when the capacities
-// differ widely.  No temp memory, no host synchronisation.
+// (1) its float32 accumulator.  One group per call: the rectangle of a whole decode, or the tile list when the
+// capacities differ widely.  No temp memory, no host synchronisation.
 int decodeAccumulateImpl(
     size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, const void* const* in, const uint32_t* inBytes,
     void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
@@ -1857,29 +1467,14 @@ int decodeAccumulateImpl(
   if (rc) return rc;
   // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
   DGPU_REQUIRE(b.maxSize <= 0xfffff000u, "decode-accumulate: outCapacity must not exceed 0xfffff000");
-  const uint32_t maxBlocks = divUp(b.maxSize, kBlockSize);
-  const uint32_t tileBlocks = maxBlocks <= 2u * kDecBlocksPerSmallTile ? kDecBlocksPerSmallTile : kDecBlocksPerTile;  // as decTileBlocksFor
-  const uint32_t maxTiles = std::max(1u, divUp(maxBlocks, tileBlocks));
   StreamLease streamLease(stream);
   DeviceBatch dev;
-  uint32_t numListedTiles = 0;
-  rc = resolveBatch(b, true, streamLease, &dev, [&] {
-    if (planTileList(b.sizes, tileBlocks * kBlockSize, maxTiles, 1u, &b.work)) numListedTiles = (uint32_t)b.work.size();
-  });
+  std::vector<LaunchGroup> groups{decodeRectangle(divUp(b.maxSize, kBlockSize), false)};
+  rc = resolveBatch(b, true, streamLease, &dev, [&] { planDecodeCall(planPolicy(), b.sizes, b.maxSize, false, &groups, &b.work); });
   if (rc) return rc;
   DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
   d.accumulate = (uint32_t)accumulate;
-  d.maxTiles = maxTiles;
-  d.order = decodeOrder(B);
-  d.workMap = nullptr;
-  d.numListed = 0;
-  uint32_t grid = (d.order == kDecOrderXcd ? roundUp(B, 8u) : B) * maxTiles;
-  if (dev.work && numListedTiles) {
-    d.order = kDecOrderMap;
-    d.workMap = dev.work;
-    grid = numListedTiles;
-  }
-  return launchVariant(decoderVariant(P, ft, tileBlocks, DecodeForm::kAccum), dim3(grid), stream, d);
+  return launchDecode(d, groups[0], dev.work, DecodeForm::kAccum, P, stream);
 }
 
 }  // namespace

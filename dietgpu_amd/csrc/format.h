@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plan_constants.h"
+
 // Streaming (non-temporal) access helpers and the cache policy of every stream the kernels touch.  The policies
 // were chosen on ROTATING buffers -- inputs, archives and outputs that are not in the 256 MiB memory-side cache when
 // their turn comes, as in real use -- not on a loop that re-codes one buffer set (docs/HISTORY.md section 3, "cache
@@ -62,7 +64,6 @@ __device__ __forceinline__ uint4 streamLoad(const uint4* p) {
 
 
 constexpr uint32_t kNumSymbols = 256;
-constexpr uint32_t kBlockSize = 4096;      // kDefaultBlockSize, GpuANSUtils.cuh:37
 constexpr uint32_t kLanesPerBlock = 32;    // the format's interleave (kWarpSize upstream)
 constexpr uint32_t kRowsPerBlock = kBlockSize / kLanesPerBlock;
 constexpr uint32_t kStateBits = 31;        // kANSStateBits
@@ -74,11 +75,6 @@ constexpr uint32_t kAnsVersion = 0x0001u;
 constexpr uint32_t kFloatMagic = 0xf00fu;
 constexpr uint32_t kFloatVersion = 0x0001u;
 constexpr uint32_t kBlockAlignWords = 8;   // 16 bytes of u16
-
-constexpr uint32_t kFloat16 = 1, kBFloat16 = 2, kFloat32 = 3;
-
-// Blocks handled by one 256-thread workgroup: 4 wave64 x 2 half-waves.
-constexpr uint32_t kBlocksPerTile = 8;
 
 struct alignas(32) AnsHeader {
   uint32_t magicAndVersion;
@@ -100,9 +96,6 @@ struct alignas(16) FloatHeader {
 };
 static_assert(sizeof(FloatHeader) == 16, "");
 
-__host__ __device__ constexpr uint32_t divUp(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
-__host__ __device__ constexpr uint32_t roundUp(uint32_t a, uint32_t b) { return divUp(a, b) * b; }
-
 // ANSCoalescedHeader::getCompressedOverhead, GpuANSUtils.cuh:68-82
 __host__ __device__ constexpr uint32_t ansOverhead(uint32_t nb) {
   return 32u + 2u * kNumSymbols + 128u * nb + 8u * roundUp(nb, 2u);
@@ -119,7 +112,6 @@ __host__ __device__ inline uint32_t floatUncompDataSize(uint32_t ft, uint32_t n)
 __host__ __device__ inline uint32_t ansOffsetInArchive(uint32_t ft, uint32_t n) {
   return ft ? 16u + floatUncompDataSize(ft, n) : 0u;
 }
-__host__ __device__ inline uint32_t floatWordBytes(uint32_t ft) { return ft == kFloat32 ? 4u : 2u; }
 
 // One addressing object for every batch flavour of the reference
 // (BatchProviderStride / Pointer / SplitSize, BatchProvider.cuh:39-194):

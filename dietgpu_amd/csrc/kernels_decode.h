@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "format.h"
+#include "plan_constants.h"
 #include "kernels_stats.h"
 
 namespace dgpu {
@@ -431,19 +432,7 @@ constexpr uint32_t kRingChunkWords = 256;
 constexpr uint32_t kRingBytes = 2048;
 constexpr uint32_t kGroupRows = 8;
 
-// A decode workgroup is 8 wavefronts = 16 blocks sharing one LUT: 32 KiB of
-// rings + 8 KiB LUT (P = 10) lets 4 workgroups = 32 wavefronts (the maximum)
-// reside on a CU.
-constexpr uint32_t kDecBlocksPerTile = 16;
-// Batches of small elements (a few blocks each) use 4-block workgroups instead:
-// a 16-block workgroup would leave most of its waves without a block while
-// still holding its LDS and wave slots.
-constexpr uint32_t kDecBlocksPerSmallTile = 4;
-// ... and one wavefront per element for batches of elements of at most 2 blocks
-constexpr uint32_t kDecBlocksPerTinyTile = 2;
-// ... and batches of single-block elements (every capacity <= 4096 symbols) go to k_ans_decode_pair
-// (kernels_pairs.h): two ELEMENTS per wavefront
-constexpr uint32_t kDecBlocksPerSingleTile = 1;
+// (blocks per decode workgroup, kDecBlocksPer*Tile: plan_constants.h)
 __host__ __device__ constexpr uint32_t decThreads(uint32_t tileBlocks) { return tileBlocks * 32u < 64u ? 64u : tileBlocks * 32u; }
 // Store (transposition) buffers per block.  Raw bytes in 16-block tiles keep the narrow stores: a fourth
 // workgroup per CU (40 KiB instead of 48: 8 waves per SIMD) is worth more to their row loop than the 8-byte

@@ -46,6 +46,7 @@
 #pragma once
 
 #include "format.h"
+#include "plan_constants.h"
 #include "kernels_stats.h"
 
 namespace dgpu {
@@ -84,25 +85,13 @@ __host__ __device__ constexpr uint32_t encSpillSlotWords(int P) { return roundUp
 
 // (Raw bytes keep the worst-case stage: a 1664-word stage with spill slots -- 4 workgroups per CU -- measured -2 %
 // for 43 MiB more temp memory, and nothing once the row stored under the ballot; docs/HISTORY.md section 5, "Config 2".)
-// SOURCE of an encoder / histogram instantiation: the template parameter FT is the archive's float type, or -- cast
-// sources, which read float32 words and round them to the archive's 16-bit type in registers -- that type with
-// kCastSource set.  Everything about the ARCHIVE (layout, header, stage size) goes by encArchiveType(FT).
-constexpr uint32_t kCastSource = 0x100u;
-__host__ __device__ constexpr bool encIsCast(uint32_t ft) { return (ft & kCastSource) != 0u; }
-__host__ __device__ constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~kCastSource; }
+// (kCastSource, encIsCast and encArchiveType -- the SOURCE of an encoder / histogram instantiation -- are in plan_constants.h)
 __host__ __device__ constexpr uint32_t encSourceWordBytes(uint32_t ft) { return ft == 0u ? 1u : ((ft == kFloat32 || encIsCast(ft)) ? 4u : 2u); }
 
 __host__ __device__ constexpr uint32_t encStageCap(int P, bool spill, uint32_t ft, bool wide = false) {
   return spill ? (encArchiveType(ft) == kFloat16 ? kSpillStageWordsFp16 : (wide ? kSpillStageWordsWide : kSpillStageWords)) : encStageWords(P);
 }
-// Blocks per tile = per workgroup: 8 (256 threads), or 4 (128 threads) for batches whose elements have
-// at most 4 blocks -- an 8-block tile would leave half of its waves without a block there.
-constexpr uint32_t kBlocksPerSmallTile = 4;
-// ... and a single wavefront (64 threads) for batches of elements of at most 2 blocks: half the LDS per workgroup,
-// twice the resident tiles
-constexpr uint32_t kBlocksPerTinyTile = 2;
-// ... and batches of SINGLE-block elements go to k_ans_encode_pair (kernels_pairs.h): two ELEMENTS per wavefront
-constexpr uint32_t kBlocksPerSingleTile = 1;
+// (blocks per tile = per workgroup, kBlocksPer*Tile: plan_constants.h)
 __host__ __device__ constexpr uint32_t encThreads(uint32_t tileBlocks) { return tileBlocks * 32u; }
 __host__ __device__ constexpr uint32_t encLdsBytes(int P, bool spill, uint32_t ft, uint32_t tileBlocks, bool wide = false) {
   return 4096u                                       // packed symbol table

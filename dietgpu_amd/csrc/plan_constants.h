@@ -1,0 +1,42 @@
+// What the kernels and the host's work planning (work_plan.h) both go by: block size, float types, tile geometries.
+// Includes nothing but <stdint.h>, so the planner and its test program compile without ROCm.
+#pragma once
+
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define DGPU_HD __host__ __device__
+#else
+#define DGPU_HD
+#endif
+
+namespace dgpu {
+
+constexpr uint32_t kBlockSize = 4096;  // kDefaultBlockSize, GpuANSUtils.cuh:37
+constexpr uint32_t kFloat16 = 1, kBFloat16 = 2, kFloat32 = 3;
+
+DGPU_HD constexpr uint32_t divUp(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+DGPU_HD constexpr uint32_t roundUp(uint32_t a, uint32_t b) { return divUp(a, b) * b; }
+DGPU_HD inline uint32_t floatWordBytes(uint32_t ft) { return ft == kFloat32 ? 4u : 2u; }
+
+// SOURCE of an encoder / histogram instantiation: the template parameter FT is the archive's float type, or -- cast
+// sources, which read float32 words and round them to the archive's 16-bit type in registers -- that type with
+// kCastSource set.  Everything about the ARCHIVE (layout, header, stage size) goes by encArchiveType(FT).
+constexpr uint32_t kCastSource = 0x100u;
+DGPU_HD constexpr bool encIsCast(uint32_t ft) { return (ft & kCastSource) != 0u; }
+DGPU_HD constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~kCastSource; }
+
+// Encoder: blocks per tile = per workgroup.  8 (256 threads: 4 wave64 x 2 half-waves); 4 (128 threads) for batches whose
+// elements have at most 4 blocks -- an 8-block tile would leave half of its waves without a block there; a single
+// wavefront for batches of elements of at most 2 blocks: half the LDS per workgroup, twice the resident tiles; batches
+// of SINGLE-block elements go to k_ans_encode_pair (kernels_pairs.h): two ELEMENTS per wavefront.
+constexpr uint32_t kBlocksPerTile = 8, kBlocksPerSmallTile = 4, kBlocksPerTinyTile = 2, kBlocksPerSingleTile = 1;
+
+// Decoder: a workgroup is 8 wavefronts = 16 blocks sharing one LUT: 32 KiB of rings + 8 KiB LUT (P = 10) lets 4
+// workgroups = 32 wavefronts (the maximum) reside on a CU.  Batches of small elements (a few blocks each) use 4-block
+// workgroups instead: a 16-block workgroup would leave most of its waves without a block while still holding its LDS
+// and wave slots; one wavefront per element for batches of elements of at most 2 blocks; batches of single-block
+// elements (every capacity <= 4096 symbols) go to k_ans_decode_pair (kernels_pairs.h): two ELEMENTS per wavefront.
+constexpr uint32_t kDecBlocksPerTile = 16, kDecBlocksPerSmallTile = 4, kDecBlocksPerTinyTile = 2, kDecBlocksPerSingleTile = 1;
+
+}  // namespace dgpu

@@ -1912,7 +1912,7 @@ def _mixed_size_batch(rng, ft, big, count):
 def test_batches_of_widely_different_sizes(dg, ft, mode):
     # The kernels' grids are rectangles laid out for the largest element; when at least a fifth of such a rectangle would
     # be empty the host lists the tiles and histogram parts that exist and the kernels work through the lists
-    # (capi.hip, RaggedPlan).  mode -1: the library's policy (lists here: 1 element of 70 blocks next to 60 of < 3),
+    # (work_plan.h, a listed LaunchGroup).  mode -1: the library's policy (lists here: 1 element of 70 blocks next to 60 of < 3),
     # 0: the rectangles, 1: lists forced -- also on the batches of the ragged fuzz test, which the policy would leave
     # to the rectangles.  Archives byte-identical to the oracle in every mode, with checksums, decoded through the
     # same mode into capacities larger than the sizes (the decoder's list comes from the capacities).
@@ -1983,8 +1983,8 @@ def test_one_large_tensor_among_many_small_ones(dg):
 @pytest.mark.parametrize("ft", [0, O.BFLOAT16, O.FLOAT16, O.FLOAT32])
 def test_size_classes_inside_one_batch(dg, ft, mode):
     # A batch whose members fall into several size classes -- single blocks, <= 2, <= 4 (decode: <= 8) blocks, more --
-    # runs every class on the kernels of its own geometry, one class after the other (capi.hip, EncodeClass /
-    # DecodeClass).  mode 1: every class that has a member, however few (one large tensor, some of 5-7 blocks, some of
+    # runs every class on the kernels of its own geometry, one class after the other (work_plan.h, one
+    # LaunchGroup per class).  mode 1: every class that has a member, however few (one large tensor, some of 5-7 blocks, some of
     # 3-4, some of 2, many single blocks, empty ones); mode -1: the library's policy (classes of fewer than 32 members
     # join the next larger one; here the 300 single blocks next to the large tensors make it split).  Archives
     # byte-identical to the oracle, with checksums; decoded through the same mode into capacities that put some members

@@ -3,14 +3,17 @@
 (csrc/kernel_variants.h), and the digest of the launches a profiler saw them make.  Two builds of the library select
 the same kernels when their digests agree:
 
-    rocprofv3 --kernel-trace -d DIR -o seq -- python tools/launch_sequence.py          (once per build)
-    python tools/launch_sequence.py --digest DIR/seq_results.db [--lines OUT.txt]
+    rocprofv3 --kernel-trace -d DIR -o seq -- python tools/launch_sequence.py --temp-out DIR/temp.txt   (once per build)
+    python tools/launch_sequence.py --digest DIR/seq_results.db --temp DIR/temp.txt [--lines OUT.txt]
 
 The calls: raw bytes, fp16, bf16 and fp32; probBits 9, 10 and 11; elements of one block (the pair kernels) and tiles
 of 2, 4 and 8 blocks, the 8-block ones with at most 32 tiles per element (wide stage) and with more; the encoder's
 dispatch left to the policy, forced persistent and forced to the hardware; ordinary histogram loads; one batch of size
-classes (1 large + many small) and one ragged batch; a caller-supplied histogram.  The digest is over the lines
-(kernel name with its template arguments, grid, workgroup size, LDS bytes) in launch order."""
+classes (1 large + many small) and one ragged batch; a caller-supplied histogram; ranged decodes on 16-block and 4-block
+tiles and of nothing but empty requests; decode-accumulate as a rectangle and from a list; cast-compress as a rectangle,
+ragged and split into classes that hold single-block members.  The digest is over the lines (kernel name with its
+template arguments, grid, workgroup size, LDS bytes) in launch order and, with --temp, the temp bytes every call of the
+list reported (tempUsed), in call order."""
 import argparse
 import ctypes as C
 import hashlib
@@ -25,19 +28,22 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SHAPES = [(3000, 64), (8000, 2048), (16000, 2048), (100000, 16), (40 * 32768, 64)]
 
 
-def digest(db, lines_out):
+def digest(db, lines_out, temp):
     con = sqlite3.connect(db)
     cols = [d[1] for d in con.execute("pragma table_info(kernels)")]
     want = [c for c in ("name", "grid_x", "grid_y", "workgroup_x", "lds_size") if c in cols]
     rows = con.execute(f"select {', '.join(want)} from kernels where name like '%dgpu::%' order by start").fetchall()
     lines = [" ".join(str(x) for x in r) for r in rows]
+    launches = len(lines)
+    if temp:
+        lines += open(temp).read().splitlines()
     if lines_out:
         with open(lines_out, "w") as f:
             f.write("\n".join(lines) + "\n")
-    print(f"{len(lines)} launches, {len(set(lines))} distinct, sha256 {hashlib.sha256(chr(10).join(lines).encode()).hexdigest()}")
+    print(f"{launches} launches, {len(set(lines[:launches]))} distinct, {len(lines) - launches} tempUsed lines, sha256 {hashlib.sha256(chr(10).join(lines).encode()).hexdigest()}")
 
 
-def main():
+def main(temp_out):
     import torch
 
     import dietgpu_amd as dg
@@ -52,12 +58,23 @@ def main():
             return [(torch.randn([n], generator=g, device=dev) * 12).to(torch.int8).view(torch.uint8) for n in sizes]
         return [torch.randn([n], generator=g, device=dev).to(dtype) for n in sizes]
 
+    temp_lines = []
+
+    def used(what, nbytes):
+        temp_lines.append(f"tempUsed {len(temp_lines)} {what} {nbytes}")
+        print(temp_lines[-1])
+
+    def rows_of(comp, sizes):
+        return [comp[i, : int(s)] for i, s in enumerate(sizes.tolist())]
+
     def round_trip(ts, prob_bits):
         is_float = ts[0].dtype != torch.uint8
-        comp, sizes, _ = dg.compress_data(is_float, ts, False, prob_bits=prob_bits)
+        comp, sizes, temp = dg.compress_data(is_float, ts, False, prob_bits=prob_bits)
+        used("compress", temp)
         outs = [torch.empty_like(t) for t in ts]
-        dg.decompress_data(is_float, [comp[i, : int(s)] for i, s in enumerate(sizes.tolist())], outs, False, prob_bits=prob_bits)
+        used("decompress", dg.decompress_data(is_float, rows_of(comp, sizes), outs, False, prob_bits=prob_bits))
         assert all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(ts, outs)), "round trip mismatch"
+        return comp, sizes
 
     dtypes = (torch.uint8, torch.float16, torch.bfloat16, torch.float32)
     for dtype in dtypes:
@@ -89,15 +106,48 @@ def main():
     assert L.dgpu_ans_decode_batch_stride(None, 0, None, 10, 0, b, p(arch), stride, p(out), n, n, None, None, st, None) == 0
     torch.cuda.synchronize()
     assert torch.equal(out, x), "round trip mismatch (caller-supplied histogram)"
+
+    # ranged decode: ranges of up to 20 blocks (16-block tiles), of up to 8 (4-block tiles), nothing but empty requests
+    ts = tensors(torch.bfloat16, [40 * 4096 - 100 * i for i in range(12)])
+    comp, sizes = round_trip(ts, 10)
+    for first, num in (([i % 5 for i in range(12)], [20 - i for i in range(12)]), ([i for i in range(12)], [1 + i % 8 for i in range(12)]),
+                       ([0] * 12, [0] * 12)):
+        outs = [torch.zeros([max(n, 1) * 4096], dtype=torch.bfloat16, device=dev) for n in num]
+        used("decompress_range", dg.decompress_data_range(True, rows_of(comp, sizes), outs, first, num, prob_bits=10))
+        for t, o, f, n in zip(ts, outs, first, num):
+            want = t[f * 4096 : (f + n) * 4096]
+            assert torch.equal(o[: want.numel()].view(torch.int16), want.view(torch.int16)), "ranged decode mismatch"
+
+    # decode-accumulate: equal capacities (the rectangle), capacities that differ widely (the list)
+    for words in ([100000] * 16, [64 * 1024 + 15000 * i for i in range(64)]):
+        ts = tensors(torch.bfloat16, words)
+        comp, sizes = round_trip(ts, 10)
+        accs = [torch.ones([n], dtype=torch.float32, device=dev) for n in words]
+        used("decompress_accumulate", dg.decompress_data_accumulate(rows_of(comp, sizes), accs, True, prob_bits=10, dtype=torch.bfloat16))
+        assert all(torch.equal(a, t.float() + 1) for a, t in zip(accs, ts)), "decode-accumulate mismatch"
+
+    # cast-compress: the rectangle, a ragged batch, size classes with single-block members (they run on 2-block tiles)
+    for words in ([100000] * 16, [64 * 1024 + 15000 * i for i in range(64)], [2 * 1024 * 1024] + [1000 + 37 * i for i in range(300)]):
+        ts = tensors(torch.float32, words)
+        comp, sizes, temp = dg.compress_data_cast(ts, torch.bfloat16, prob_bits=10)
+        used("compress_cast", temp)
+        outs = [torch.empty([n], dtype=torch.bfloat16, device=dev) for n in words]
+        used("decompress", dg.decompress_data(True, rows_of(comp, sizes), outs, False, prob_bits=10))
+        assert all(torch.equal(o.view(torch.int16), t.to(torch.bfloat16).view(torch.int16)) for o, t in zip(outs, ts)), "cast-compress mismatch"
+    if temp_out:
+        with open(temp_out, "w") as f:
+            f.write("\n".join(temp_lines) + "\n")
     print("launch sequence done")
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--digest", default=None, help="the profiler's results database of a run of this script")
-    ap.add_argument("--lines", default=None, help="with --digest: write the launch lines here")
+    ap.add_argument("--lines", default=None, help="with --digest: write the launch lines (and the tempUsed lines) here")
+    ap.add_argument("--temp", default=None, help="with --digest: the --temp-out file of that run, which the digest then covers")
+    ap.add_argument("--temp-out", default=None, help="write the tempUsed of every call here")
     a = ap.parse_args()
     if a.digest:
-        digest(a.digest, a.lines)
+        digest(a.digest, a.lines, a.temp)
     else:
-        main()
+        main(a.temp_out)
