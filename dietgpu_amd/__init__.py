@@ -17,6 +17,7 @@ from .ops import (  # noqa: F401
     decompress_data,
     decompress_data_accumulate,
     decompress_data_range,
+    decompress_data_reduce,
     decompress_data_simple,
     decompress_data_slice,
     decompress_data_split_size,

@@ -1477,6 +1477,45 @@ int decodeAccumulateImpl(
   return launchDecode(d, groups[0], dev.work, DecodeForm::kAccum, P, stream);
 }
 
+// Decode-reduce (k_ans_decode_reduce): S = numSources archives per float32 accumulator, summed left to right in one
+// launch, all or nothing per member.  The batch carries B * S archive pointers and inBytes (member-major) beside B
+// accumulators and capacities; the parameter block holds every one of them, so its hash -- the parameter-cache key --
+// covers each source pointer and size, and S through the block's length and layout.  The launch plan is that of a
+// decode-accumulate call with the same capacities.  No temp memory, no host synchronisation.
+int decodeReduceImpl(
+    size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, uint32_t S, const void* const* in, const uint32_t* inBytes,
+    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+  DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
+  DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "decode-reduce: accumulate must be 0 or 1");
+  DGPU_REQUIRE(S >= 1u && S <= kMaxReduceSources, "decode-reduce: numSources must be between 1 and 64");
+  DGPU_REQUIRE((uint64_t)B * S <= 65535u, "decode-reduce: numInBatch * numSources must be <= 65535");
+  if (S == 1u) return decodeAccumulateImpl(tempUsed, ft, P, accumulate, B, in, inBytes, out, outCapacity, outSuccess_dev, outSize_dev, stream);
+  bool done;
+  int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
+  if (done) return rc;
+  DGPU_REQUIRE(in && inBytes && out && outCapacity, "decode-reduce: null array with numInBatch > 0");
+  Batch b;
+  // (pointerBatch, with S inputs per output)
+  rc = sideAddresses(ptrSide(in, 16, kMsgCompIn), B * S, &b.inPtrs);
+  if (!rc) rc = sideAddresses(ptrSide(out, 4, "decode-reduce: accumulators must be 4-byte aligned"), B, &b.outPtrs);
+  if (rc) return rc;
+  b.n = B;
+  b.sizes.assign(outCapacity, outCapacity + B);
+  b.inBytes.assign(inBytes, inBytes + (size_t)B * S);
+  for (uint32_t i = 0; i < B; ++i) b.maxSize = std::max(b.maxSize, outCapacity[i]);
+  // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
+  DGPU_REQUIRE(b.maxSize <= 0xfffff000u, "decode-reduce: outCapacity must not exceed 0xfffff000");
+  StreamLease streamLease(stream);
+  DeviceBatch dev;
+  std::vector<LaunchGroup> groups{decodeRectangle(divUp(b.maxSize, kBlockSize), false)};
+  rc = resolveBatch(b, true, streamLease, &dev, [&] { planDecodeCall(planPolicy(), b.sizes, b.maxSize, false, &groups, &b.work); });
+  if (rc) return rc;
+  DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
+  d.accumulate = (uint32_t)accumulate;
+  d.numSources = S;
+  return launchDecode(d, groups[0], dev.work, DecodeForm::kReduce, P, stream);
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1772,6 +1811,17 @@ int dgpu_float_decode_accumulate(
   (void)tempBytes;
   return decodeAccumulateImpl(tempUsed, floatType, probBits, accumulate, numInBatch, in, inBytes, out, outCapacity,
                               outSuccess_dev, outSize_dev, (hipStream_t)stream);
+}
+
+// ---- decode-reduce (no upstream equivalent) ---------------------------------------
+int dgpu_float_decode_reduce(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, void* const* out,
+    const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream) {
+  (void)temp_dev;
+  (void)tempBytes;
+  return decodeReduceImpl(tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, out, outCapacity,
+                          outSuccess_dev, outSize_dev, (hipStream_t)stream);
 }
 
 // ---- float stride batches with capacities on both sides (the compressed collectives) --------------------

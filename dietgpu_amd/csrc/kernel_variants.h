@@ -140,7 +140,8 @@ inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, boo
 //   * DecodeForm::kRanged: k_ans_decode_range, which decodes a block range of every element; it exists for 16- and
 //     4-block tiles (a range of one or two blocks takes the 4-block form);
 //   * DecodeForm::kAccum: k_ans_decode_accum, which widens to float32 and stores to / adds into float32 accumulators;
-//     float types only (raw bytes: the float32 form), 16- and 4-block tiles.
+//     float types only (raw bytes: the float32 form), 16- and 4-block tiles;
+//   * DecodeForm::kReduce: k_ans_decode_reduce, the same with DecodeArgs::numSources archives per accumulator.
 inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, DecodeForm form = DecodeForm::kWhole) {
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> DecodeVariant {
     constexpr int kP = decltype(p)::value;
@@ -150,6 +151,14 @@ inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, Dec
         constexpr uint32_t kTB = decltype(tb)::value;
         constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
         return {k_ans_decode_accum<kP, kAccFT, kTB>, decThreads(kTB), decLdsBytes(kP, kAccFT, kTB), "k_ans_decode_accum"};
+      };
+      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
+    }
+    if (form == DecodeForm::kReduce) {
+      auto tiled = [](auto tb) -> DecodeVariant {
+        constexpr uint32_t kTB = decltype(tb)::value;
+        constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
+        return {k_ans_decode_reduce<kP, kAccFT, kTB>, decThreads(kTB), decLdsBytes(kP, kAccFT, kTB), "k_ans_decode_reduce"};
       };
       return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
     }

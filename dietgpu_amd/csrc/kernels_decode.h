@@ -67,6 +67,8 @@ struct DecodeArgs {
   const uint32_t* numBlocks = nullptr;   // [B]; 0xffffffff = to the end of the element
   // k_ans_decode_accum only: out holds float32 accumulators; 0: acc = decoded (the accumulator is not read), 1: acc += decoded
   uint32_t accumulate = 0;
+  // k_ans_decode_reduce only: in / inBytes hold numInBatch * numSources entries, source s of member b at b * numSources + s
+  uint32_t numSources = 1;
 };
 __device__ __forceinline__ uint64_t decodeInBytes(const DecodeArgs& a, uint32_t b) {
   return a.inBytes ? (uint64_t)a.inBytes[b] : (a.uniformInBytes ? (uint64_t)a.uniformInBytes : ~0ull);
@@ -750,10 +752,12 @@ __device__ __forceinline__ void decodeBlock(
 // outSize are those of the whole decode, with one difference: EVERY tile makes tile 0's check of all the element's block
 // descriptors (8 bytes per block, from the L2, in the round trip of the tile's own descriptor), and no tile of an element
 // with a malformed descriptor stores -- a failing element leaves its accumulator as it was.
-enum class DecodeForm { kWhole, kRanged, kAccum };
+// (kReduce: decodeReduceTile, below)
+enum class DecodeForm { kWhole, kRanged, kAccum, kReduce };
 template <int P, uint32_t FT, uint32_t kTileBlocks, DecodeForm kForm>
 __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccum = kForm == DecodeForm::kAccum;
+  static_assert(kForm != DecodeForm::kReduce, "decode-reduce has a body of its own: decodeReduceTile");
   static_assert(!kAccum || FT != 0u, "accumulating decode: float archives only");
   using Sink = std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32>, RowSink<FT>>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks);
@@ -1134,6 +1138,257 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Decode-reduce (k_ans_decode_reduce): member b has S = numSources archives, in.ptr(b * S + s), and ONE float32
+// accumulator; the workgroup of (member, tile) decodes its blocks of source 0, 1, ... S-1 one after the other into the
+// accumulator words of the tile -- acc = ((acc + x0) + x1) + ..., or (x0 + x1) + ... with accumulate == 0 -- which is bit for
+// bit what S decode-accumulate calls leave.  Grid, workgroup order, tile-to-block mapping, LDS layout, sink and row loop
+// (decodeBlock) are k_ans_decode_accum's.  A sibling of decodeTile, not a form of it: that function is the body of
+// every shipped decoder and stays as it is.
+//
+// 1. ALL sources are validated before the first store, in every tile of the member, so a member with one bad source
+//    keeps every bit of its accumulator.  Wave w checks the headers (those of a bounded decode-accumulate against the
+//    member's capacity and the source's own inBytes) and sums the pdf table of sources w, w + waves, ...; after a barrier
+//    every thread knows the S verdicts and word counts, which must all be equal; then the S * numBlocks block descriptors
+//    are checked in ONE strided loop over the workgroup (8 bytes each, from the L2, no load waiting for another), and a
+//    second barrier collects that verdict.  Tile 0 reports: success, and the word count source 0 states.
+// 2. Per source: descriptor, lane states and (wave 0) pdf table are requested; the LUT is rebuilt (the binary-search
+//    build for both tile sizes: the scan build of the small tiles would be a second copy of sixty lines for a
+//    start-up cost that a tile pays once per source); decodeBlock runs with accumulate = (s > 0) | a.accumulate.
+//    Between two sources the accumulator goes through memory: the words a wave adds to for source s + 1 are the words
+//    the same wave stored for source s, though other lanes may have (wide layout).  So before the barrier that frees
+//    rings and LUT for the rebuild every wave releases at workgroup scope and drains its stores; after it, it acquires,
+//    and only then are the accumulator words of source s + 1 requested (decodePrefetch and everything in decodeBlock).
+//    The workgroup sits on one CU, whose L1 all its waves share: this costs the wait and no cache invalidation.
+struct ReduceSource {  // verdict on one source (LDS)
+  uint32_t ok;          // headers and pdf sum
+  uint32_t total;       // words the ANS header states (ok)
+  uint32_t totalWords;  // compressed words (ok)
+  uint32_t report;      // what a decode of this source alone would write to outSize
+};
+constexpr uint32_t kMaxReduceSources = 64;
+
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
+  static_assert(FT != 0u, "decode-reduce: float archives only");
+  using Sink = AccumSink<FT>;
+  constexpr uint32_t kDecThreads = decThreads(kTileBlocks), kWaves = kDecThreads / 64u;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint2* sLut = (uint2*)(smem + kTileBlocks * kRingBytes);
+  constexpr uint32_t kXpose = decXposeBytes(P, FT, kTileBlocks);
+  // the verdicts live in the ring area behind the LUT-build scratch (2 KiB + a few words at offset 0), which source 0
+  // fills while slower waves may still be reading them
+  static_assert(kTileBlocks * kRingBytes >= 4096u + kMaxReduceSources * sizeof(ReduceSource) + 4u * kWaves, "");
+  ReduceSource* sSrc = (ReduceSource*)(smem + 4096u);
+  uint32_t* sWaveBad = (uint32_t*)(sSrc + kMaxReduceSources);
+
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+  uint32_t b, tile;
+  if (!decodeTileOf(a, blockIdx.x, &b, &tile)) return;  // uniform
+  const uint32_t S = a.numSources, first = b * S;
+  const uint32_t capacity = a.out.size(b);
+  const uint32_t tileFirst = tile * kTileBlocks;
+  // (a rectangle is laid out for the largest capacity: no valid member has blocks past its own)
+  if (tile != 0 && (uint64_t)tileFirst * kBlockSize >= capacity) return;  // uniform
+
+  // ---- 1. validate every source ----
+  for (uint32_t s = wave; s < S; s += kWaves) {  // (everything here is wave-uniform)
+    const uint8_t* archive = a.in.ptr(first + s);
+    const uint64_t inBytes = a.inBytes[first + s];
+    ReduceSource r = {0u, 0u, 0u, 0u};
+    if (inBytes >= sizeof(FloatHeader)) {
+      const FloatHeader fh = *(const FloatHeader*)archive;
+      r.report = fh.size;
+      const bool fhOk = fh.magicAndVersion == ((kFloatMagic << 16) | kFloatVersion) && (fh.options & 0xfu) == FT && fh.size <= capacity &&
+          (uint64_t)sizeof(FloatHeader) + floatUncompDataSize(FT, fh.size) + sizeof(AnsHeader) <= inBytes;
+      if (fhOk) {
+        const uint8_t* ans = archive + ansOffsetInArchive(FT, fh.size);
+        const AnsHeader header = *(const AnsHeader*)ans;
+        const uint32_t nb = header.numBlocks, total = header.totalUncompressedWords;
+        bool ok = capacity >= total && header.magicAndVersion == ((kAnsMagic << 16) | kAnsVersion) && (header.options & 0xfu) == (uint32_t)P &&
+            fh.size == total && nb == divUp(total, kBlockSize) &&
+            (uint64_t)ansOffsetInArchive(FT, total) + ansOverhead(nb) + 2ull * header.totalCompressedWords <= inBytes;
+        if (ok && nb != 0u) {
+          // the probabilities of a non-empty element sum to 2^P: four per lane, then over the wave
+          const uint2 raw = *(const uint2*)(ans + sizeof(AnsHeader) + 8u * lane);
+          uint32_t sum = (raw.x & 0xffffu) + (raw.x >> 16) + (raw.y & 0xffffu) + (raw.y >> 16);
+#pragma unroll
+          for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+          ok = sum == (1u << P);
+        }
+        r.ok = ok ? 1u : 0u;
+        r.total = total;
+        r.totalWords = header.totalCompressedWords;
+        r.report = total;
+      }
+    }
+    if (lane == 0u) sSrc[s] = r;
+  }
+  __syncthreads();
+  const uint32_t total = sSrc[0].total, report = sSrc[0].report;
+  bool memberOk = true;
+  for (uint32_t s = 0; s < S; ++s) memberOk = memberOk && sSrc[s].ok != 0u && sSrc[s].total == total;
+  if (!memberOk) {  // uniform, and the same in every tile of the member: nothing of it is stored
+    if (tile == 0 && tid == 0) {
+      if (a.outSuccess) a.outSuccess[b] = 0;
+      if (a.outSize) a.outSize[b] = report;
+    }
+    return;
+  }
+  const uint32_t nb = divUp(total, kBlockSize);
+  if (tileFirst >= nb && tile != 0) return;  // uniform
+  const uint32_t ansOff = ansOffsetInArchive(FT, total);
+  {
+    // block i of source s must be what an encoder can produce (decodeTile's blockOk)
+    bool allBlocksOk = true;
+    for (uint32_t i = tid; i < S * nb; i += kDecThreads) {
+      const uint32_t s = i / nb, blk = i - s * nb;
+      const uint2 bw = ((const uint2*)(a.in.ptr(first + s) + ansOff + ansBlockWordsOffset(nb)))[blk];
+      const uint32_t want = (blk + 1u < nb) ? kBlockSize : total - blk * kBlockSize;
+      const bool ok = (bw.x >> 16) == want && (bw.y & (kBlockAlignWords - 1u)) == 0u &&
+          (uint64_t)bw.y + roundUp(bw.x & 0xffffu, kBlockAlignWords) <= (uint64_t)sSrc[s].totalWords;
+      allBlocksOk = allBlocksOk & ok;
+    }
+    const bool waveBad = __ballot(!allBlocksOk) != 0ull;
+    if (lane == 0u) sWaveBad[wave] = waveBad ? 1u : 0u;
+  }
+  __syncthreads();
+  uint32_t anyBad = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kWaves; ++w) anyBad |= sWaveBad[w];
+  if (tile == 0 && tid == 0) {
+    if (a.outSuccess) a.outSuccess[b] = anyBad ? 0 : 1;
+    if (a.outSize) a.outSize[b] = report;
+  }
+  if (anyBad != 0u || tileFirst >= nb) return;  // uniform
+
+  // ---- 2. one source after the other ----
+  const uint32_t ldsBase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem;
+  constexpr bool kCompact = decCompactLut(P, kTileBlocks);
+  const bool wide = kXpose != 0u;  // (accumulators are float-aligned, the host checks it)
+  uint32_t* sCdf = (uint32_t*)smem;
+  uint32_t* sPdf = sCdf + kNumSymbols;
+
+#pragma unroll 1
+  for (uint32_t s = 0; s < S; ++s) {
+    // Everything a lane derives from its index is derived HERE, from a value the compiler cannot see through: hoisted
+    // out of the loop, these addresses and offsets stay in registers across decodeBlock (151 VGPRs: one wave per SIMD,
+    // i.e. one of two workgroups per CU, fewer than k_ans_decode_accum; recomputed per source they cost a few dozen VALU
+    // per source).  tests/test_reduce_kernel_resources.py holds the 16-bit forms to the 128 VGPRs of four waves per SIMD.
+    uint32_t tidS = threadIdx.x;
+    asm volatile("" : "+v"(tidS));
+    const uint32_t laneS = tidS & 63u;
+    const bool upper = laneS >= 32u;
+    const uint32_t hl = laneS & 31u;
+    const uint32_t hw = wave * 2u + (upper ? 1u : 0u);
+    const uint32_t block = tileFirst + hw;
+    const bool haveBlock = block < nb;
+    // (a half without a block points at its wave's first block: its prefetches stay inside archive and accumulator)
+    const uint32_t sinkBlock = haveBlock ? block : (block & ~1u);
+    const uint32_t xpose = ldsBase + kTileBlocks * kRingBytes + decLutBytes(P, kTileBlocks) + hw * kXpose;
+    const uint32_t ringLds = ldsBase + hw * kRingBytes;
+    const uint8_t* archive = a.in.ptr(first + s);
+    const uint8_t* ans = archive + ansOff;
+    uint2 pdfRaw = make_uint2(0u, 0u), bwMine = make_uint2(0u, 0u);
+    uint32_t state = 0;
+    if (wave == 0) pdfRaw = ((const uint2*)(ans + sizeof(AnsHeader)))[laneS];  // pdf[4 lane .. 4 lane + 3]
+    if (haveBlock) {
+      bwMine = ((const uint2*)(ans + ansBlockWordsOffset(nb)))[block];
+      state = ((const uint32_t*)(ans + ansStatesOffset()))[block * 32u + hl];
+    }
+    if (s != 0u) {
+      // source s - 1 is in the accumulator before source s asks for it; the barrier also frees LUT and rings
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    const uint32_t n = bwMine.x >> 16, numWords = bwMine.x & 0xffffu;
+    const uint8_t* gwords = ans + ansOverhead(nb) + 2u * (size_t)bwMine.y;
+    Sink sink;
+    sink.accumulate = (s != 0u || a.accumulate != 0u) ? 1u : 0u;
+    sink.init(a.out.ptr(b), archive, total, (size_t)sinkBlock * kBlockSize, hl);
+    // uniform per wave (the staging mode is this source's own; full / tail follow the word count, the same for all)
+    const uint32_t nFirst = __shfl(n, 0, 64);
+    const uint32_t nSecond = __shfl(n, 32, 64);
+    const uint32_t wFirst = __shfl(numWords, 0, 64);
+    const uint32_t wSecond = __shfl(numWords, 32, 64);
+    const bool noRing = wFirst <= kRingBytes / 2u && wSecond <= kRingBytes / 2u;
+    const bool fullPair = nFirst == kBlockSize && nSecond == kBlockSize;
+    const bool fullSingle = nFirst == kBlockSize && nSecond == 0u;
+    DecodePreOf<typename Sink::GroupPre> pre;
+    if ((fullPair || fullSingle) && noRing) decodePrefetch<FT>(pre, gwords, numWords, sink, hl, wide);
+
+    // the LUT of this source (see decodeTile): wave 0 scans the 256 pdfs, every thread fills its slots
+    if (wave == 0) {
+      const uint32_t p0 = pdfRaw.x & 0xffffu, p1 = pdfRaw.x >> 16, p2 = pdfRaw.y & 0xffffu, p3 = pdfRaw.y >> 16;
+      const uint32_t mine = p0 + p1 + p2 + p3;
+      const uint32_t base = waveInclusiveScan(mine, laneS) - mine;
+      ((uint4*)sCdf)[laneS] = make_uint4(base, base + p0, base + p0 + p1, base + p0 + p1 + p2);
+      ((uint4*)sPdf)[laneS] = make_uint4(p0, p1, p2, p3);
+    }
+    __syncthreads();
+    for (uint32_t x = tidS; x < (1u << P); x += kDecThreads) {
+      uint32_t lo = 0, hi = kNumSymbols;  // the last symbol with cdf <= x
+#pragma unroll
+      for (int it = 0; it < 8; ++it) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const bool le = sCdf[mid] <= x;
+        lo = le ? mid : lo;
+        hi = le ? hi : mid;
+      }
+      if (kCompact) ((uint32_t*)sLut)[x] = (sPdf[lo] & 0xfffu) | (((x - sCdf[lo]) & 0xfffu) << 12) | (lo << 24);
+      else sLut[x] = make_uint2((sPdf[lo] & 0xfffu) | (lo << 24), (x - sCdf[lo]) & 0xfffu);
+    }
+    __syncthreads();  // LUT visible, scratch free
+
+    // the dispatch of decodeTile
+#define DGPU_REDUCE_FULL(WIDE, IDLE, NORING) \
+  decodeBlock<P, FT, true, WIDE, IDLE, kCompact, NORING, NORING, false, Sink>(xpose, state, n, kRowsPerBlock / kGroupRows, gwords, numWords, ringLds, sLut, sink, hl, upper, &pre)
+#define DGPU_REDUCE_TAIL(WIDE, IDLE, NORING) \
+  decodeBlock<P, FT, true, WIDE, IDLE, kCompact, NORING, false, true, Sink>(xpose, state, n, groups, gwords, numWords, ringLds, sLut, sink, hl, upper, nullptr, topRows)
+    if (fullPair) {
+      if (wide) {
+        if (noRing) DGPU_REDUCE_FULL(true, false, true); else DGPU_REDUCE_FULL(true, false, false);
+      } else {
+        if (noRing) DGPU_REDUCE_FULL(false, false, true); else DGPU_REDUCE_FULL(false, false, false);
+      }
+    } else if (fullSingle) {
+      if (wide) {
+        if (noRing) DGPU_REDUCE_FULL(true, true, true); else DGPU_REDUCE_FULL(true, true, false);
+      } else {
+        if (noRing) DGPU_REDUCE_FULL(false, true, true); else DGPU_REDUCE_FULL(false, true, false);
+      }
+    } else {
+      const uint32_t maxN = nFirst > nSecond ? nFirst : nSecond;
+      const uint32_t maxRows = divUp(maxN, 32u);
+      const uint32_t fullRows = (nSecond ? nSecond : nFirst) / 32u;  // (the last block of the wave is the partial one)
+      const uint32_t groups = fullRows / kGroupRows;
+      const uint32_t topRows = maxRows - groups * kGroupRows;
+      const bool tailPair = nFirst == kBlockSize && nSecond != 0u, tailSingle = nFirst != 0u && nSecond == 0u;
+      if (tailPair && groups != 0u) {
+        if (wide) {
+          if (noRing) DGPU_REDUCE_TAIL(true, false, true); else DGPU_REDUCE_TAIL(true, false, false);
+        } else {
+          if (noRing) DGPU_REDUCE_TAIL(false, false, true); else DGPU_REDUCE_TAIL(false, false, false);
+        }
+      } else if (tailSingle && groups != 0u) {
+        if (wide) {
+          if (noRing) DGPU_REDUCE_TAIL(true, true, true); else DGPU_REDUCE_TAIL(true, true, false);
+        } else {
+          if (noRing) DGPU_REDUCE_TAIL(false, true, true); else DGPU_REDUCE_TAIL(false, true, false);
+        }
+      } else {
+        decodeBlock<P, FT, false, false, false, kCompact, false, false, false, Sink>(xpose, state, n, divUp(maxRows, kGroupRows), gwords, numWords, ringLds, sLut, sink, hl, upper);
+      }
+    }
+#undef DGPU_REDUCE_FULL
+#undef DGPU_REDUCE_TAIL
+  }
+}
+
 // grid = the (element, tile) pairs in the order of DecodeArgs::order
 template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode(DecodeArgs a) {
@@ -1152,6 +1407,13 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_range(De
 template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_accum(DecodeArgs a) {
   decodeTile<P, FT, kTileBlocks, DecodeForm::kAccum>(a);
+}
+
+// Reducing form: grid and order as k_ans_decode_accum, DecodeArgs::numSources archives per accumulator (decodeReduceTile).
+// Built for the float types, 16- and 4-block tiles.
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce(DecodeArgs a) {
+  decodeReduceTile<P, FT, kTileBlocks>(a);
 }
 
 }  // namespace dgpu

@@ -524,6 +524,42 @@ int64_t decompress_data_accumulate(
   return (int64_t)used;
 }
 
+// Decode-reduce (no reference op): num_sources archives per accumulator, ts_in flattened member-major (source s of
+// accumulator i is ts_in[i * num_sources + s]), summed left to right in one launch, all or nothing per accumulator
+// (dgpu_float_decode_reduce).  accumulate = false stores the first source: the accumulators are never read.
+int64_t decompress_data_reduce(
+    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, bool accumulate,
+    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes) {
+  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
+  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
+  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType >= (int64_t)DGPU_FLOAT16 && floatType <= (int64_t)DGPU_FLOAT32, "dietgpu: float_type must be 1, 2 or 3");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tAccs.size();
+  // (every source beside its accumulator: the checks of a decode call, then the accumulators once)
+  std::vector<at::Tensor> accOfSource(tIns.size());
+  for (size_t i = 0; i < tIns.size(); ++i) accOfSource[i] = tAccs[i / (size_t)numSources];
+  DecodeTensors sources = marshalDecode(true, tIns, accOfSource, dev, [&](size_t i) {
+    TORCH_CHECK(accOfSource[i].scalar_type() == at::ScalarType::Float, "dietgpu: accumulators must be float32");
+  });
+  std::vector<void*> outPtrs(n);
+  std::vector<uint32_t> outCapacity(n);
+  for (size_t i = 0; i < n; ++i) {
+    outPtrs[i] = sources.outPtrs[i * (size_t)numSources];
+    outCapacity[i] = sources.outCapacity[i * (size_t)numSources];
+  }
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  size_t used = 0;
+  check(dgpu_float_decode_reduce(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
+                                 (uint32_t)numSources, sources.inPtrs.data(), sources.inBytes.data(), outPtrs.data(), outCapacity.data(),
+                                 ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
+        "floatDecompressReduce", true);
+  return (int64_t)used;
+}
+
 // Cast-compress (no reference op): float32 tensor i rounded to float_type (1 = float16, 2 = bfloat16) in registers and
 // compressed into an ordinary archive of that type (dgpu_float_cast_compress).  Output conventions of compress_data.
 std::tuple<at::Tensor, at::Tensor, int64_t> compress_data_cast(
@@ -607,6 +643,9 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "decompress_data_accumulate(Tensor[] ts_in, Tensor[] ts_acc, int float_type, bool accumulate=True, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
       &dietgpu_amd::decompress_data_accumulate);
+  m.def(
+      "decompress_data_reduce(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
+      &dietgpu_amd::decompress_data_reduce);
   m.def(
       "compress_data_cast(Tensor[] ts_in, int float_type, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::compress_data_cast);

@@ -126,6 +126,15 @@ class GpuFloatCodec:
         ops.decompress_data_accumulate(rows, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype)
         return status
 
+    def decompress_reduce(self, rows_per_acc, accs, accumulate):
+        """rows_per_acc[i]: equally long lists of rows, summed left to right into (accumulate) or stored as their sum to
+        the float32 tensor accs[i], in ONE launch and all or nothing per accumulator -> status, one per accumulator"""
+        from . import ops
+
+        status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
+        ops.decompress_data_reduce(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype)
+        return status
+
 
 def compressed_all_gather(tensors, codec=None):
     """All-gathers a list of equally-shaped float tensors per rank, moving compressed bytes.
@@ -176,18 +185,25 @@ def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec):
     return gathered, stats
 
 
+_MAX_REDUCE_SOURCES = 64  # of one decode-reduce call (dgpu_float_decode_reduce)
+
+
 def compressed_reduce_scatter(tensor, codec=None):
     """Reduce-scatter (sum) of a flat float tensor, moving compressed bytes and summing in float32.
 
     `tensor`: this rank's flat fp16 / bf16 / fp32 tensor; its length is a multiple of the world size and the same on
     every rank.  Shard j of every rank goes to rank j, compressed; rank j decodes the `world` rows it received straight
-    into ONE float32 shard -- no 16-bit scratch tensor, no separate add: rank 0's row is stored (accumulate off, so the
-    shard needs no memset), then one decode-accumulate call per further source rank, in ascending rank order on the
-    current stream.  The result is therefore, by construction, the sequential float32 sum in rank order,
-    ((x_0 + x_1) + x_2) + ..., of the exactly widened inputs: bit-identical on every run and to the same sum computed
-    uncompressed.  Returns (shard_fp32, stats), stats as `compressed_all_gather`.  RuntimeError if a row fails to decode.
-    `codec` needs compress(list) -> (uint8 [n, cap], int32 [n]) and decompress_accumulate(rows, accs, accumulate) ->
-    uint8 status [n]."""
+    into ONE float32 shard -- no 16-bit scratch tensor, no separate add.  A codec with decompress_reduce(rows_per_acc,
+    accs, accumulate) sums all rows in ONE decode-reduce call (accumulate off: rank 0's row is stored, so the shard needs
+    no memset) with one status read; a codec without it (or a world of more than 64 ranks) stores rank 0's row and makes
+    one decode-accumulate call per further source rank, in ascending rank order on the current stream.  Either way the
+    result is, by construction, the sequential float32 sum in rank order, ((x_0 + x_1) + x_2) + ..., of the exactly
+    widened inputs: bit-identical on every run, between the two paths and to the same sum computed uncompressed.
+    Returns (shard_fp32, stats), stats as `compressed_all_gather`.  RuntimeError if a row fails to decode; on the
+    decode-reduce path the shard was then not partly summed (the call adds all rows or none).
+    `codec` needs compress(list) -> (uint8 [n, cap], int32 [n]) and, for the shard's sum, decompress_reduce(rows_per_acc,
+    accs, accumulate) -> uint8 status [len(accs)] or decompress_accumulate(rows, accs, accumulate) -> uint8 status [n];
+    a world of more than 64 ranks needs decompress_accumulate (RuntimeError without it)."""
     codec = codec or GpuFloatCodec()
     world = dist.get_world_size()
     if tensor.dim() != 1 or tensor.numel() % world != 0:
@@ -211,10 +227,20 @@ def compressed_reduce_scatter(tensor, codec=None):
 
     me = dist.get_rank()
     shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
-    for r in range(world):
-        status = codec.decompress_accumulate([recv[r, : int(all_sizes[r, me])]], [shard], r != 0)
+    has_reduce = callable(getattr(codec, "decompress_reduce", None))
+    if not (has_reduce and world <= _MAX_REDUCE_SOURCES) and not callable(getattr(codec, "decompress_accumulate", None)):
+        raise RuntimeError(f"compressed_reduce_scatter: the codec has no decompress_accumulate, which a world of {world} ranks "
+                           f"(more than {_MAX_REDUCE_SOURCES}) or a codec without decompress_reduce needs")
+    if has_reduce and world <= _MAX_REDUCE_SOURCES:
+        status = codec.decompress_reduce([[recv[r, : int(all_sizes[r, me])] for r in range(world)]], [shard], False)
         if not bool(status.all().item()):
-            raise RuntimeError(f"decode-accumulate of rank {r}'s row failed")
+            raise RuntimeError("decode-reduce of the received rows failed: a row is malformed or the rows differ in length; "
+                               "the shard was not partly summed")
+    else:
+        for r in range(world):
+            status = codec.decompress_accumulate([recv[r, : int(all_sizes[r, me])]], [shard], r != 0)
+            if not bool(status.all().item()):
+                raise RuntimeError(f"decode-accumulate of rank {r}'s row failed")
     stats = {
         "raw_bytes": tensor.numel() * tensor.element_size(),
         "wire_bytes": world * width,

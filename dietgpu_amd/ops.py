@@ -604,6 +604,62 @@ def decompress_data_accumulate(ts_in, ts_acc, accumulate=True, temp_mem=None, ou
     return int(used.value)
 
 
+# ------------------------------------------------------------------ decode-reduce
+# (no reference op: dgpu_float_decode_reduce, include/dietgpu_amd.h)
+MAX_REDUCE_SOURCES = 64
+
+
+def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
+                           prob_bits=K_DEFAULT_PRECISION, dtype=None):
+    """Sums SEVERAL float archives per accumulator in one launch: ts_in is a list, one entry per accumulator, of equally
+    long lists of uint8 CUDA tensors (at most 64 each); ts_acc[i] = ((ts_acc[i] + x0) + x1) + ... with accumulate=True,
+    (x0 + x1) + ... with accumulate=False -- the first source is then STORED, the accumulator is never read and no
+    memset is needed.  Strictly left to right, one IEEE float32 add per word and source: bit for bit what one
+    `decompress_data_accumulate` call per source leaves -> temp bytes used (0).
+
+    All or nothing per accumulator: out_status[i] is 1 only if every source of ts_in[i] is a sound archive of the
+    call's float type that fits ts_acc[i] and all of them hold the same number of words; otherwise it is 0 and
+    ts_acc[i] keeps every bit it had.  out_sizes[i] is the size the header of ts_in[i][0] states.  `dtype` as in
+    decompress_data_accumulate (given: no host synchronisation; else read from the header of ts_in[0][0])."""
+    _check(len(ts_in) > 0)
+    _check(len(ts_in) == len(ts_acc), "one list of sources per accumulator")
+    sources = len(ts_in[0])
+    _check(1 <= sources <= MAX_REDUCE_SOURCES, "between 1 and 64 sources per accumulator")
+    for srcs in ts_in:
+        _check(len(srcs) == sources, "every accumulator takes the same number of sources")
+    flat = [t for srcs in ts_in for t in srcs]  # member-major
+    _check(flat[0].is_cuda, "tensors must be on the GPU")
+    dev = flat[0].get_device()
+    for ti in flat:
+        _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous() and ti.dtype == torch.uint8)
+    for ta in ts_acc:
+        _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
+        _check(ta.dtype == torch.float32, "accumulators must be float32")
+        _check(ta.numel() <= _U32_MAX)
+    n = len(ts_acc)
+    _validate_status(out_status, out_sizes, n, dev)
+    with torch.cuda.device(dev):
+        tp, tb = _temp(temp_mem, dev)
+        if dtype is not None:
+            _check(dtype in _DTYPE_TO_FT, "dtype must be float16, bfloat16 or float32")
+            ft = _DTYPE_TO_FT[dtype]
+        else:
+            ft = _header_info(True, flat[:1], tp, tb)[1][0]
+            _check(ft in _FT_TO_DTYPE, "ts_in[0][0] is not a float archive")
+        if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce"):
+            torch.ops.dietgpu_amd.set_precision(prob_bits)
+            try:
+                return torch.ops.dietgpu_amd.decompress_data_reduce(flat, sources, ts_acc, ft, bool(accumulate), temp_mem,
+                                                                    out_status, out_sizes)
+            finally:
+                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+        used = C.c_size_t(0)
+        check(lib().dgpu_float_decode_reduce(
+            tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
+            _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), _ptr(out_status), _ptr(out_sizes), _stream()))
+    return int(used.value)
+
+
 def _check_slice_args(compress_as_float, ts_in, dtype):
     _check(len(ts_in) > 0)
     for t in ts_in:

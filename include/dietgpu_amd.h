@@ -67,8 +67,8 @@ const char* dgpu_version(void);
  * against this header (the tensor-op library of this repository, a cgo / JNI binding) compares the value it was compiled
  * with against the library it finds at run time, so that a stale build fails at load instead of inside a call.  An entry
  * point that is only ADDED leaves every existing one as it was and does not move the version: a library without the new
- * symbol fails at load too, by symbol resolution, in anything that links it (dgpu_float_decode_accumulate and
- * dgpu_float_cast_compress were added at version 8). */
+ * symbol fails at load too, by symbol resolution, in anything that links it (dgpu_float_decode_accumulate,
+ * dgpu_float_cast_compress and dgpu_float_decode_reduce were added at version 8). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -304,6 +304,39 @@ int dgpu_float_decode_accumulate(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
     uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
     void* const* out /* float32 */, const uint32_t* outCapacity /* float words */,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
+
+/* ---- decode-reduce (no upstream equivalent) ------------------------------------------
+ * dgpu_float_decode_accumulate with numSources archives per accumulator, summed in ONE launch: the receiving side of a
+ * compressed reduce-scatter, where `world` compressed rows belong to one float32 shard.
+ *   - Layout: member-major.  Source s of member i is in[i * numSources + s], with inBytes[i * numSources + s] bytes
+ *     available; out, outCapacity, outSuccess_dev and outSize_dev have numInBatch entries.
+ *   - Result: strictly left to right, one IEEE float32 add (__fadd_rn) per word and source.  accumulate == 1:
+ *     out[i] = ((acc + x0) + x1) + ... + x(S-1).  accumulate == 0: out[i] = (x0 + x1) + ... + x(S-1); the widened bits of
+ *     x0 are stored as they are and the accumulator is never read.  Widening as in dgpu_float_decode_accumulate.  Bit
+ *     for bit what numSources successive dgpu_float_decode_accumulate calls leave, the first with `accumulate`, the
+ *     rest with 1.
+ *   - All or nothing per member: outSuccess_dev[i] = 1 only if EVERY source of member i passes every check of a bounded
+ *     decode-accumulate against outCapacity[i] and its own inBytes (float header, ANS header, probBits, float type,
+ *     block count, every block descriptor, pdf sum, the archive inside inBytes) and all numSources headers state the
+ *     same word count.  Otherwise outSuccess_dev[i] = 0, out[i] keeps every bit it had (also with accumulate == 0), and
+ *     the other members are not disturbed.
+ *   - outSize_dev[i]: the word count the header of source 0 states, as a decode of source 0 alone reports it (0 if
+ *     source 0 has fewer bytes than a header).
+ *   - floatType must be DGPU_FLOAT16, DGPU_BFLOAT16 or DGPU_FLOAT32, accumulate 0 or 1, probBits 9, 10 or 11,
+ *     1 <= numSources <= 64, numInBatch * numSources <= 65535, in[...] 16-byte aligned, out[i] 4-byte aligned,
+ *     outCapacity[i] <= 0xfffff000, no array null when numInBatch > 0: DGPU_ERR_INVALID_ARGUMENT otherwise, with a
+ *     dgpu_last_error() text, before anything is enqueued.  An empty batch returns 0 with *tempUsed = 0.  The
+ *     accumulators of different members MUST NOT overlap; sources may alias each other.
+ *   - numSources == 1 IS dgpu_float_decode_accumulate (the call forwards to it).
+ *   - No useChecksum (see above).  One kernel geometry per call, from its largest capacity.
+ *   - No temp memory is used (*tempUsed = 0) and nothing synchronises: capturable into a HIP graph under the same
+ *     conditions as the other pointer-array decode calls (the arrays resident from an earlier identical call). */
+int dgpu_float_decode_reduce(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources,
+    const void* const* in /* [numInBatch * numSources] */, const uint32_t* inBytes /* same shape */,
+    void* const* out /* float32, [numInBatch] */, const uint32_t* outCapacity /* float words, [numInBatch] */,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
 
 /* ---- cast-compress (no upstream equivalent) -------------------------------------------

@@ -22,4 +22,20 @@ inline void floatDecompressAccumulate(
                   "floatDecompressAccumulate");
 }
 
+// Decode-reduce: numSources archives per accumulator, member-major (source s of member i is in[i * numSources + s], with
+// inBytes of the same shape), summed strictly left to right in ONE launch -- bit for bit what numSources successive
+// floatDecompressAccumulate calls leave, the first with `accumulate`, the rest with true -- and all or nothing per
+// member: outSuccess_dev[i] = 0 leaves out[i] as it was.  dgpu_float_decode_reduce of ../dietgpu_amd.h.
+inline void floatDecompressReduce(
+    StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, uint32_t numSources,
+    const void** in, const uint32_t* inBytes, float** out, const uint32_t* outCapacity, uint8_t* outSuccess_dev,
+    uint32_t* outSize_dev, hipStream_t stream) {
+  (void)res;
+  size_t used = 0;
+  detail::checkRc(dgpu_float_decode_reduce(nullptr, 0, &used, (uint32_t)config.floatType, config.ansConfig.probBits,
+                                           accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, (void* const*)out,
+                                           outCapacity, outSuccess_dev, outSize_dev, stream),
+                  "floatDecompressReduce");
+}
+
 }  // namespace dietgpu
