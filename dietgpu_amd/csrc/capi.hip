@@ -1049,7 +1049,9 @@ int encodeCommon(
     const BatchView& in, const BatchView& archives, uint32_t sourceType,
     const LaunchGroup& group /* the whole batch, or one size class of it */, const uint32_t* work_dev /* the plan's lists on the device */,
     EncodeShared& shared /* what the groups of one call share */, const uint32_t* hist_dev /*may be null*/, uint32_t* outSize_dev,
-    uint32_t outCapacity /* bytes at every archive pointer; block data beyond it is dropped */) {
+    uint32_t outCapacity /* bytes at every archive pointer; block data beyond it is dropped */,
+    uint32_t* histAcc_dev = nullptr /* the histogram in the stream's zero-at-rest counters instead of hist_dev (reduce-compress):
+                                       the normalisation reads them and puts them back to zero */) {
   const uint32_t floatType = encArchiveType(sourceType);
   const uint32_t wordBytes = floatType ? floatWordBytes(floatType) : 1u;
   const uint32_t tileBlocks = group.tileBlocks, maxTiles = group.maxTiles, maxSize = group.maxSize;
@@ -1169,7 +1171,8 @@ int encodeCommon(
   n.groupWords = groupWords;
   n.groupWordsPerElement = lookbackGroups * (kGroupArriveStride + 1u);
 
-  if (!hist_dev && tileBlocks == kBlocksPerSingleTile && maxTiles > 0 && floatType != kFloat32) {
+  const bool haveHist = hist_dev || histAcc_dev;
+  if (!haveHist && tileBlocks == kBlocksPerSingleTile && maxTiles > 0 && floatType != kFloat32) {
     // batches of single-block elements: one wavefront counts and normalises an element (kernels_pairs.h); no partial
     // histograms, no arrival counters.  (Measured on 32768 elements, profiles/r04_ab_single_block_elements.txt:
     // bf16 75.5 -> 65.5 us, fp16 80.5 -> 73.7; float32 -- 16 bytes of input per symbol and lane -- 69 -> 75.5, so
@@ -1177,7 +1180,7 @@ int encodeCommon(
     int rc = launchVariant(statsSingleVariant(floatType, histogramLoadsNonTemporal(floatType)), dim3(divUp(numElems, kSingleStatWaves)), stream,
                            in, n, elemMap, numElems);
     if (rc) return rc;
-  } else if (!hist_dev) {
+  } else if (!haveHist) {
     const bool histList = lists && numListedHistParts != 0;
     const bool accumulate = !histList && histAccumulates(B, maxSize * wordBytes, floatType == 0);
     dim3 grid(accumulate ? histPartsAccFor(B, maxSize * wordBytes) : histPartsFor(B, maxSize * wordBytes, floatType == 0), B);
@@ -1203,7 +1206,8 @@ int encodeCommon(
     rc = launchVariant(histogramVariant(sourceType, smallBins, histogramLoadsNonTemporal(floatType)), grid, stream, in, histTemp, 1u, fuse);
     if (rc) return rc;
   } else {
-    // caller-supplied histogram: stand-alone normalisation
+    // caller-supplied histogram (or the counts of reduce-compress): stand-alone normalisation
+    n.histAcc = histAcc_dev;
     DGPU_LAUNCH("k_normalize", stream, k_normalize, dim3(B), dim3(256), 0, stream, n);
     DGPU_HIP(hipGetLastError());
   }
@@ -1516,6 +1520,77 @@ int decodeReduceImpl(
   return launchDecode(d, groups[0], dev.work, DecodeForm::kReduce, P, stream);
 }
 
+// Reduce-compress: decode-reduce into the accumulators, then cast-compress of the accumulators, without the cast
+// histogram pass -- the reduce kernel (k_ans_decode_reduce_stats) counts the exponent bytes of the rounded sums as it
+// stores them, and the cast encoder runs on the table normalised from those counts (encodeCommon with a histogram).
+// The counts [B][256] are zero when the reduce kernel starts: for B <= kAccElements they are the stream's zero-at-rest
+// histogram counters (held under the stream lease; k_normalize reads them and puts them back to zero), otherwise a
+// region of temp memory cleared by one memset on the stream.  A member that fails the reduce has no counts: its table is
+// the flat one, which codes any data.  Everything is validated before the first enqueue; nothing synchronises.
+int reduceCompressImpl(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, uint32_t S,
+    const void* const* in, const uint32_t* inBytes, void* const* acc, const uint32_t* outCapacity, void* const* outArchive,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream) {
+  DGPU_REQUIRE(ft == kFloat16 || ft == kBFloat16, "reduce-compress: floatType must be float16 or bfloat16 (float32: decode-reduce, then dgpu_float_compress)");
+  DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "reduce-compress: accumulate must be 0 or 1");
+  DGPU_REQUIRE(S >= 1u && S <= kMaxReduceSources, "reduce-compress: numSources must be between 1 and 64");
+  DGPU_REQUIRE((uint64_t)B * S <= 65535u, "reduce-compress: numInBatch * numSources must be <= 65535");
+  bool done;
+  int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
+  if (done) return rc;
+  DGPU_REQUIRE(in && inBytes && acc && outCapacity && outArchive, "reduce-compress: null array with numInBatch > 0");
+  // the reduce side: B * S archives into B accumulators (decodeReduceImpl); the compress side: the accumulators into B archives
+  Batch bd, be;
+  rc = sideAddresses(ptrSide(in, 16, kMsgCompIn), B * S, &bd.inPtrs);
+  if (!rc) rc = sideAddresses(ptrSide(acc, 4, "reduce-compress: accumulators must be 4-byte aligned"), B, &bd.outPtrs);
+  if (!rc) rc = pointerBatch(&be, B, ptrSide(acc, 4, "reduce-compress: accumulators must be 4-byte aligned"), ptrSide(outArchive, 16, kMsgCompOut), outCapacity);
+  if (rc) return rc;
+  bd.n = B;
+  bd.sizes = be.sizes;
+  bd.inBytes.assign(inBytes, inBytes + (size_t)B * S);
+  bd.maxSize = be.maxSize;
+  DGPU_REQUIRE(encodableSize(be.maxSize),
+               "reduce-compress: outCapacity larger than 1717538816 words: the maximum compressed size of its exponent plane exceeds INT32_MAX (GpuANSEncode.cu:22)");
+
+  StreamLease streamLease(stream);
+  TempArena arena(temp_dev, tempBytes, streamLease);
+  DeviceBatch devD, devE;
+  std::vector<LaunchGroup> groupsD{decodeRectangle(divUp(bd.maxSize, kBlockSize), false)};
+  rc = resolveBatch(bd, true, streamLease, &devD, [&] { planDecodeCall(planPolicy(), bd.sizes, bd.maxSize, false, &groupsD, &bd.work); });
+  if (rc) return rc;
+  const uint32_t castType = ft | kCastSource;
+  std::vector<LaunchGroup> groupsE{encodeRectangle(be.maxSize, castType)};
+  rc = resolveBatch(be, false, streamLease, &devE, [&] { planEncodeCall(planPolicy(), be.sizes, castType, be.maxSize, true, &groupsE, &be.work); });
+  if (rc) return rc;
+
+  uint32_t *counts = nullptr, *countsAtRest = nullptr;
+  if (B <= kAccElements) {
+    uint32_t* arrive = nullptr;
+    rc = arrivalCounters(streamLease, &arrive, &countsAtRest);
+    if (rc) return rc;
+    counts = countsAtRest;
+  } else {
+    DGPU_ALLOC(c, uint32_t, arena, (size_t)B * kNumSymbols);
+    counts = c;
+    DGPU_HIP(hipMemsetAsync(counts, 0, (size_t)B * kNumSymbols * 4, stream));
+  }
+
+  DecodeArgs d = decodeArgs(bd, devD, ft, outSuccess_dev, outSize_dev);
+  d.accumulate = (uint32_t)accumulate;
+  d.numSources = S;
+  d.stats = counts;
+  rc = launchDecode(d, groupsD[0], devD.work, DecodeForm::kReduceStats, P, stream);
+  if (!rc) {
+    EncodeShared shared;
+    rc = encodeCommon(arena, streamLease, stream, P, false, B, devE.in, devE.out, castType, groupsE[0], devE.work, shared,
+                      countsAtRest ? nullptr : counts, outArchiveSize_dev, 0xffffffffu, countsAtRest);
+    // (the normalisation may not have been enqueued: the counters are zero at rest whatever happened)
+    if (rc && countsAtRest) (void)hipMemsetAsync(countsAtRest, 0, (size_t)B * kNumSymbols * 4, stream);
+  }
+  if (tempUsed) *tempUsed = arena.requested();
+  return rc;
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1649,6 +1724,11 @@ size_t dgpu_ans_decode_temp_bytes(uint32_t B, uint32_t maxBytes, int probBits) {
 size_t dgpu_float_compress_temp_bytes(uint32_t ft, uint32_t B, uint32_t maxFloats) {
   // no exponent plane: the split is fused into the encoder
   return encodeTempBytes(B, maxFloats, validFloatType(ft) ? floatWordBytes(ft) : 4u, true);
+}
+
+size_t dgpu_float_reduce_compress_temp_bytes(uint32_t ft, uint32_t B, uint32_t maxWords) {
+  // the compress side's, and the counts of a batch that is too large for the stream's counters
+  return dgpu_float_compress_temp_bytes(ft, B, maxWords) + (B > kAccElements ? alignUp((size_t)B * kNumSymbols * 4, kTempAlign) : 0u);
 }
 
 size_t dgpu_float_decompress_temp_bytes(uint32_t ft, uint32_t B, uint32_t maxFloats, int probBits) {
@@ -1822,6 +1902,16 @@ int dgpu_float_decode_reduce(
   (void)tempBytes;
   return decodeReduceImpl(tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, out, outCapacity,
                           outSuccess_dev, outSize_dev, (hipStream_t)stream);
+}
+
+// ---- reduce-compress (no upstream equivalent) -------------------------------------
+int dgpu_float_reduce_compress(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, void* const* acc,
+    const uint32_t* outCapacity, void* const* outArchive, uint8_t* outSuccess_dev, uint32_t* outSize_dev,
+    uint32_t* outArchiveSize_dev, void* stream) {
+  return reduceCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, acc,
+                            outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream);
 }
 
 // ---- float stride batches with capacities on both sides (the compressed collectives) --------------------

@@ -141,7 +141,10 @@ inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, boo
 //     4-block tiles (a range of one or two blocks takes the 4-block form);
 //   * DecodeForm::kAccum: k_ans_decode_accum, which widens to float32 and stores to / adds into float32 accumulators;
 //     float types only (raw bytes: the float32 form), 16- and 4-block tiles;
-//   * DecodeForm::kReduce: k_ans_decode_reduce, the same with DecodeArgs::numSources archives per accumulator.
+//   * DecodeForm::kReduce: k_ans_decode_reduce, the same with DecodeArgs::numSources archives per accumulator;
+//   * DecodeForm::kReduceStats: k_ans_decode_reduce_stats, which also counts the exponent bytes of the rounded sums
+//     (DecodeArgs::stats); float16 and bfloat16 only (anything else: the bfloat16 form), 16- and 4-block tiles, with
+//     the LDS of the bins behind that of the plain form.
 inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, DecodeForm form = DecodeForm::kWhole) {
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> DecodeVariant {
     constexpr int kP = decltype(p)::value;
@@ -159,6 +162,14 @@ inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, Dec
         constexpr uint32_t kTB = decltype(tb)::value;
         constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
         return {k_ans_decode_reduce<kP, kAccFT, kTB>, decThreads(kTB), decLdsBytes(kP, kAccFT, kTB), "k_ans_decode_reduce"};
+      };
+      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
+    }
+    if (form == DecodeForm::kReduceStats) {
+      auto tiled = [](auto tb) -> DecodeVariant {
+        constexpr uint32_t kTB = decltype(tb)::value;
+        constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
+        return {k_ans_decode_reduce_stats<kP, kCastFT, kTB>, decThreads(kTB), decReduceStatsLdsBytes(kP, kCastFT, kTB), "k_ans_decode_reduce_stats"};
       };
       return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
     }

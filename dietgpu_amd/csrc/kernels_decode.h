@@ -69,6 +69,9 @@ struct DecodeArgs {
   uint32_t accumulate = 0;
   // k_ans_decode_reduce only: in / inBytes hold numInBatch * numSources entries, source s of member b at b * numSources + s
   uint32_t numSources = 1;
+  // k_ans_decode_reduce_stats only: [numInBatch][256] counts of the exponent bytes of the stored sums, rounded to the
+  // archive type (zero at launch; see decodeReduceTile, kStats)
+  uint32_t* stats = nullptr;
 };
 __device__ __forceinline__ uint64_t decodeInBytes(const DecodeArgs& a, uint32_t b) {
   return a.inBytes ? (uint64_t)a.inBytes[b] : (a.uniformInBytes ? (uint64_t)a.uniformInBytes : ~0ull);
@@ -325,12 +328,36 @@ struct AccumGroupPre {  // one 8-row group of a lane: 8 non-compressed bytes and
   u32x4w a0, a1;
 };
 
-template <uint32_t FT>
-struct AccumSink {  // kFloat16 / kBFloat16
+// kSlots != 0 (k_ans_decode_reduce_stats): every float32 word the sink stores is also rounded to FT (castRound, the cast
+// encoder's own rounding) and the exponent byte of the rounded word -- the encoder's split: fp16 w >> 8, bf16 bits
+// 14..7 -- is counted in the workgroup's LDS bins, in this lane's slot column `bins` (an LDS address; bin c at
+// bins + c * kSlots * 4; 0: this is not the last source, nothing is counted).  Counting sits inside store() and
+// flushGroup(), which run for the lanes that store and for no others: the counts of a member add up to its words.
+constexpr uint32_t kStatsSlotsLarge = 16, kStatsSlotsSmall = 8;  // lane slots per bin: 16-block / 4-block tiles
+__host__ __device__ constexpr uint32_t decStatsSlots(uint32_t tileBlocks) { return tileBlocks <= 4u ? kStatsSlotsSmall : kStatsSlotsLarge; }
+__host__ __device__ constexpr uint32_t decStatsBinBytes(uint32_t tileBlocks) { return kNumSymbols * decStatsSlots(tileBlocks) * 4u; }
+typedef __attribute__((address_space(3))) uint32_t LdsU32w;
+template <bool kStats>
+struct AccumBins {};
+template <>
+struct AccumBins<true> {
+  uint32_t bins;
+};
+
+template <uint32_t FT, uint32_t kSlots = 0>
+struct AccumSink : AccumBins<kSlots != 0u> {  // kFloat16 / kBFloat16
   static_assert(FT == kFloat16 || FT == kBFloat16, "");
+  static constexpr bool kStats = kSlots != 0u;
   float* out;
   const uint8_t* nc;
   uint32_t accumulate;
+  // kStats: the stored float32 bits `o` enter the histogram of the archive the cast encoder will make of them
+  __device__ __forceinline__ void count(uint32_t o) const {
+    if constexpr (kStats) {
+      const uint32_t c = (castRound<FT>(o) >> (FT == kFloat16 ? 8u : 7u)) & 0xffu;
+      __hip_atomic_fetch_add((LdsU32w*)(uintptr_t)(this->bins + c * (kSlots * 4u)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
   __device__ __forceinline__ void init(uint8_t* outBase, const uint8_t* archive, uint32_t, size_t first, uint32_t hl) {
     out = (float*)outBase + first + hl;
     nc = archive + 16u + first + hl;
@@ -347,6 +374,9 @@ struct AccumSink {  // kFloat16 / kBFloat16
     const float v = accWiden16<FT>(RowSink<FT>::joinWord(e0, p.r) >> 16);
     const uint32_t o = accumulate ? accAdd(p.acc, v) : __builtin_bit_cast(uint32_t, v);
     streamStore<kNtDecStores>((uint32_t*)&out[row * 32u], o);
+    if constexpr (kStats) {
+      if (this->bins) count(o);
+    }
   }
   static constexpr uint32_t kXposeBytes = 512;
   __device__ __forceinline__ AccumGroupPre prefetchGroup(uint32_t g, uint32_t hl) const {
@@ -385,11 +415,21 @@ struct AccumSink {  // kFloat16 / kBFloat16
       dst[0] = o0;
       dst[1] = o1;
     }
+    if constexpr (kStats) {
+      if (this->bins) {
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+          count(o0[k]);
+          count(o1[k]);
+        }
+      }
+    }
   }
 };
 
-template <>
-struct AccumSink<kFloat32> {  // row-wise, as RowSink<kFloat32>: 128-byte pieces already
+template <uint32_t kSlots>
+struct AccumSink<kFloat32, kSlots> {  // row-wise, as RowSink<kFloat32>: 128-byte pieces already
+  static_assert(kSlots == 0u, "counting sinks: the 16-bit archive types only");
   float* out;
   const uint16_t* nc2;
   const uint8_t* nc1;
@@ -753,11 +793,11 @@ __device__ __forceinline__ void decodeBlock(
 // descriptors (8 bytes per block, from the L2, in the round trip of the tile's own descriptor), and no tile of an element
 // with a malformed descriptor stores -- a failing element leaves its accumulator as it was.
 // (kReduce: decodeReduceTile, below)
-enum class DecodeForm { kWhole, kRanged, kAccum, kReduce };
+enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats };
 template <int P, uint32_t FT, uint32_t kTileBlocks, DecodeForm kForm>
 __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccum = kForm == DecodeForm::kAccum;
-  static_assert(kForm != DecodeForm::kReduce, "decode-reduce has a body of its own: decodeReduceTile");
+  static_assert(kForm != DecodeForm::kReduce && kForm != DecodeForm::kReduceStats, "decode-reduce has a body of its own: decodeReduceTile");
   static_assert(!kAccum || FT != 0u, "accumulating decode: float archives only");
   using Sink = std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32>, RowSink<FT>>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks);
@@ -1160,6 +1200,15 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
 //    rings and LUT for the rebuild every wave releases at workgroup scope and drains its stores; after it, it acquires,
 //    and only then are the accumulator words of source s + 1 requested (decodePrefetch and everything in decodeBlock).
 //    The workgroup sits on one CU, whose L1 all its waves share: this costs the wait and no cache invalidation.
+//
+// kStats (k_ans_decode_reduce_stats, the first half of reduce-compress): the same, and on the LAST source the sink counts
+// the exponent byte of every sum it stores, rounded to FT as the cast encoder will round it (AccumSink, kSlots), in LDS
+// bins behind the store buffers -- the histogram kernel's bin-major layout, decStatsSlots lane slots per bin, zeroed
+// before the first barrier.  When the tile is done the workgroup folds its bins and adds the non-zero ones to the
+// member's 256 counters a.stats[b] with relaxed agent-scope atomics.  A member's sources must state EXACTLY its capacity
+// (the encoder codes `capacity` words of the accumulator); a member that fails any check returns before the source loop
+// and so adds nothing.  The last source is selected at run time (a wave-uniform test around the counting), the form at
+// compile time: the plain kernel's code does not change.
 struct ReduceSource {  // verdict on one source (LDS)
   uint32_t ok;          // headers and pdf sum
   uint32_t total;       // words the ANS header states (ok)
@@ -1168,10 +1217,11 @@ struct ReduceSource {  // verdict on one source (LDS)
 };
 constexpr uint32_t kMaxReduceSources = 64;
 
-template <int P, uint32_t FT, uint32_t kTileBlocks>
+template <int P, uint32_t FT, uint32_t kTileBlocks, bool kStats = false>
 __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
   static_assert(FT != 0u, "decode-reduce: float archives only");
-  using Sink = AccumSink<FT>;
+  constexpr uint32_t kSlots = kStats ? decStatsSlots(kTileBlocks) : 0u;
+  using Sink = AccumSink<FT, kSlots>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks), kWaves = kDecThreads / 64u;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint2* sLut = (uint2*)(smem + kTileBlocks * kRingBytes);
@@ -1192,6 +1242,11 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
   const uint32_t tileFirst = tile * kTileBlocks;
   // (a rectangle is laid out for the largest capacity: no valid member has blocks past its own)
   if (tile != 0 && (uint64_t)tileFirst * kBlockSize >= capacity) return;  // uniform
+  // kStats: the bins lie behind rings, LUT and store buffers; they are zero after the first barrier below
+  constexpr uint32_t kBinsAt = kTileBlocks * kRingBytes + decLutBytes(P, kTileBlocks) + kTileBlocks * kXpose;
+  if constexpr (kStats) {
+    for (uint32_t i = tid; i < kNumSymbols * kSlots / 4u; i += kDecThreads) ((uint4*)(smem + kBinsAt))[i] = make_uint4(0u, 0u, 0u, 0u);
+  }
 
   // ---- 1. validate every source ----
   for (uint32_t s = wave; s < S; s += kWaves) {  // (everything here is wave-uniform)
@@ -1210,6 +1265,7 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
         bool ok = capacity >= total && header.magicAndVersion == ((kAnsMagic << 16) | kAnsVersion) && (header.options & 0xfu) == (uint32_t)P &&
             fh.size == total && nb == divUp(total, kBlockSize) &&
             (uint64_t)ansOffsetInArchive(FT, total) + ansOverhead(nb) + 2ull * header.totalCompressedWords <= inBytes;
+        if constexpr (kStats) ok = ok && total == capacity;  // the words the encoder codes are the words that are counted
         if (ok && nb != 0u) {
           // the probabilities of a non-empty element sum to 2^P: four per lane, then over the wave
           const uint2 raw = *(const uint2*)(ans + sizeof(AnsHeader) + 8u * lane);
@@ -1309,6 +1365,7 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
     const uint8_t* gwords = ans + ansOverhead(nb) + 2u * (size_t)bwMine.y;
     Sink sink;
     sink.accumulate = (s != 0u || a.accumulate != 0u) ? 1u : 0u;
+    if constexpr (kStats) sink.bins = s + 1u == S ? ldsBase + kBinsAt + (laneS & (kSlots - 1u)) * 4u : 0u;
     sink.init(a.out.ptr(b), archive, total, (size_t)sinkBlock * kBlockSize, hl);
     // uniform per wave (the staging mode is this source's own; full / tail follow the word count, the same for all)
     const uint32_t nFirst = __shfl(n, 0, 64);
@@ -1387,6 +1444,20 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
 #undef DGPU_REDUCE_FULL
 #undef DGPU_REDUCE_TAIL
   }
+  if constexpr (kStats) {
+    // the tile's counts join the member's: bin-major, so a bin's slots are consecutive (histFold)
+    __syncthreads();
+    const uint32_t* bins = (const uint32_t*)(smem + kBinsAt);
+    for (uint32_t c = tid; c < kNumSymbols; c += kDecThreads) {
+      uint32_t sum = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < kSlots / 4u; ++k) {
+        const uint4 v = ((const uint4*)(bins + c * kSlots))[k];
+        sum += v.x + v.y + v.z + v.w;
+      }
+      if (sum) __hip_atomic_fetch_add(a.stats + (size_t)b * kNumSymbols + c, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
 }
 
 // grid = the (element, tile) pairs in the order of DecodeArgs::order
@@ -1414,6 +1485,17 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_accum(De
 template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce(DecodeArgs a) {
   decodeReduceTile<P, FT, kTileBlocks>(a);
+}
+
+// Counting form (reduce-compress): k_ans_decode_reduce that also leaves, in DecodeArgs::stats, the exponent histogram of
+// the sums rounded to FT (decodeReduceTile, kStats).  Built for float16 / bfloat16, 16- and 4-block tiles.
+__host__ __device__ constexpr uint32_t decReduceStatsLdsBytes(int P, uint32_t ft, uint32_t tileBlocks) {
+  return decLdsBytes(P, ft, tileBlocks) + decStatsBinBytes(tileBlocks);
+}
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce_stats(DecodeArgs a) {
+  static_assert(FT == kFloat16 || FT == kBFloat16, "the archive types of a cast");
+  decodeReduceTile<P, FT, kTileBlocks, true>(a);
 }
 
 }  // namespace dgpu

@@ -458,6 +458,32 @@ __device__ __forceinline__ uint32_t histFold(const uint32_t* bins, uint32_t tid)
   return sum;
 }
 
+// float32 -> 16-bit float, round to nearest even, for the cast sources, the cast histogram and the counting
+// decode-reduce (k_ans_decode_reduce_stats) -- one helper, so that they cannot disagree.  `x` are the float32 bits; NaN
+// becomes the canonical quiet NaN of the target with the sign kept (a payload in the low 16 bits alone must not round
+// to infinity).
+//   * bfloat16: integer rounding on the bits, (x + 0x7fff + lsb) >> 16: float32 denormals are not flushed, overflow
+//     carries into infinity.  castRoundHigh leaves the result in the HIGH half (the low half is of no use).
+//   * float16: v_cvt_f16_f32 under the kernel's default mode (round to nearest even, float16 denormals produced; every
+//     float32 denormal is below half the smallest float16 denormal and becomes a zero whether or not it is flushed).
+template <uint32_t AT>
+__device__ __forceinline__ uint32_t castRoundHigh(uint32_t x) {
+  static_assert(AT == kBFloat16, "");
+  const bool nan = (x & 0x7fffffffu) > 0x7f800000u;
+  const uint32_t s = x + 0x7fffu + ((x >> 16) & 1u);
+  return nan ? ((x & 0x80000000u) | 0x7fc00000u) : s;
+}
+template <uint32_t AT>
+__device__ __forceinline__ uint32_t castRound(uint32_t x) {
+  if (AT == kBFloat16) {
+    return castRoundHigh<kBFloat16>(x) >> 16;
+  } else {
+    const bool nan = (x & 0x7fffffffu) > 0x7f800000u;
+    const uint32_t h = (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)__builtin_bit_cast(float, x));
+    return nan ? (((x >> 16) & 0x8000u) | 0x7e00u) : h;
+  }
+}
+
 // Histogram kernel: 16-byte loads with a byte-wise head/tail so any start
 // alignment works (the reference test uses stride size+11,
 // ANSStatisticsTest.cu:52-57).  grid = (xBlocks, B), 256 threads.

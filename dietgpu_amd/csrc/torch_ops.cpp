@@ -598,6 +598,50 @@ std::tuple<at::Tensor, at::Tensor, int64_t> compress_data_cast(
   return {std::move(comp), std::move(sizes), (int64_t)used};
 }
 
+// Reduce-compress (no reference op): decompress_data_reduce into ts_acc and compress_data_cast of ts_acc in one call
+// (dgpu_float_reduce_compress).  ts_in as decompress_data_reduce's; float_type (1 = float16, 2 = bfloat16) is that of the
+// sources and of the archives.  Output conventions of compress_data_cast.
+std::tuple<at::Tensor, at::Tensor, int64_t> decompress_data_reduce_compress(
+    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, bool accumulate,
+    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes,
+    const std::optional<at::Tensor>& outCompressed, const std::optional<at::Tensor>& outCompressedSizes) {
+  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
+  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
+  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tAccs.size();
+  std::vector<at::Tensor> accOfSource(tIns.size());
+  for (size_t i = 0; i < tIns.size(); ++i) accOfSource[i] = tAccs[i / (size_t)numSources];
+  DecodeTensors sources = marshalDecode(true, tIns, accOfSource, dev, [&](size_t i) {
+    TORCH_CHECK(accOfSource[i].scalar_type() == at::ScalarType::Float, "dietgpu: accumulators must be float32");
+  });
+  std::vector<void*> accPtrs(n);
+  std::vector<uint32_t> capacity(n);
+  int64_t maxWords = 0;
+  for (size_t i = 0; i < n; ++i) {
+    accPtrs[i] = sources.outPtrs[i * (size_t)numSources];
+    capacity[i] = sources.outCapacity[i * (size_t)numSources];
+    maxWords = std::max<int64_t>(maxWords, tAccs[i].numel());
+  }
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  at::Tensor comp, sizes;
+  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)maxWords), dev,
+                  tAccs[0].device(), comp, sizes);
+  std::vector<void*> compPtrs(n);
+  for (size_t i = 0; i < n; ++i) compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
+  size_t used = 0;
+  check(dgpu_float_reduce_compress(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
+                                   (uint32_t)numSources, sources.inPtrs.data(), sources.inBytes.data(), accPtrs.data(), capacity.data(),
+                                   compPtrs.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes),
+                                   (uint32_t*)sizes.data_ptr(), streamOf(dev)),
+        "floatReduceCompress", true);
+  return {std::move(comp), std::move(sizes), (int64_t)used};
+}
+
 void set_precision(int64_t probBits) {
   TORCH_CHECK(probBits == 9 || probBits == 10 || probBits == 11, "probBits must be 9, 10 or 11");
   tPrecision = (int)probBits;
@@ -649,6 +693,9 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "compress_data_cast(Tensor[] ts_in, int float_type, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::compress_data_cast);
+  m.def(
+      "decompress_data_reduce_compress(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
+      &dietgpu_amd::decompress_data_reduce_compress);
 }
 
 TORCH_LIBRARY(dietgpu, m) {

@@ -135,6 +135,16 @@ class GpuFloatCodec:
         ops.decompress_data_reduce(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype)
         return status
 
+    def decompress_reduce_compress(self, rows_per_acc, accs, accumulate):
+        """decompress_reduce and compress_cast of the accumulators back to the rows' dtype in ONE call, without the cast's
+        histogram pass over the accumulators -> (status, comp, sizes): as the two calls return them"""
+        from . import ops
+
+        status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
+        comp, sizes, _ = ops.decompress_data_reduce_compress(rows_per_acc, accs, accumulate, self.temp_mem, status, None,
+                                                             dtype=self.dtype)
+        return status, comp, sizes
+
 
 def compressed_all_gather(tensors, codec=None):
     """All-gathers a list of equally-shaped float tensors per rank, moving compressed bytes.
@@ -188,23 +198,9 @@ def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec):
 _MAX_REDUCE_SOURCES = 64  # of one decode-reduce call (dgpu_float_decode_reduce)
 
 
-def compressed_reduce_scatter(tensor, codec=None):
-    """Reduce-scatter (sum) of a flat float tensor, moving compressed bytes and summing in float32.
-
-    `tensor`: this rank's flat fp16 / bf16 / fp32 tensor; its length is a multiple of the world size and the same on
-    every rank.  Shard j of every rank goes to rank j, compressed; rank j decodes the `world` rows it received straight
-    into ONE float32 shard -- no 16-bit scratch tensor, no separate add.  A codec with decompress_reduce(rows_per_acc,
-    accs, accumulate) sums all rows in ONE decode-reduce call (accumulate off: rank 0's row is stored, so the shard needs
-    no memset) with one status read; a codec without it (or a world of more than 64 ranks) stores rank 0's row and makes
-    one decode-accumulate call per further source rank, in ascending rank order on the current stream.  Either way the
-    result is, by construction, the sequential float32 sum in rank order, ((x_0 + x_1) + x_2) + ..., of the exactly
-    widened inputs: bit-identical on every run, between the two paths and to the same sum computed uncompressed.
-    Returns (shard_fp32, stats), stats as `compressed_all_gather`.  RuntimeError if a row fails to decode; on the
-    decode-reduce path the shard was then not partly summed (the call adds all rows or none).
-    `codec` needs compress(list) -> (uint8 [n, cap], int32 [n]) and, for the shard's sum, decompress_reduce(rows_per_acc,
-    accs, accumulate) -> uint8 status [len(accs)] or decompress_accumulate(rows, accs, accumulate) -> uint8 status [n];
-    a world of more than 64 ranks needs decompress_accumulate (RuntimeError without it)."""
-    codec = codec or GpuFloatCodec()
+def _exchange_shard_rows(tensor, codec):
+    """The exchange half of compressed_reduce_scatter: shard j of this rank's flat tensor, compressed, goes to rank j ->
+    (words per shard, recv [source rank, width] uint8, all_sizes [source rank, destination rank] int32, width)."""
     world = dist.get_world_size()
     if tensor.dim() != 1 or tensor.numel() % world != 0:
         raise RuntimeError("compressed_reduce_scatter: the tensor must be flat, its length a multiple of the world size")
@@ -224,7 +220,28 @@ def compressed_reduce_scatter(tensor, codec=None):
     work = _all_to_all_flat(recv.view(-1), send.view(-1), world)
     if work is not None:
         work.wait()
+    return shard_words, recv, all_sizes, width
 
+
+def compressed_reduce_scatter(tensor, codec=None):
+    """Reduce-scatter (sum) of a flat float tensor, moving compressed bytes and summing in float32.
+
+    `tensor`: this rank's flat fp16 / bf16 / fp32 tensor; its length is a multiple of the world size and the same on
+    every rank.  Shard j of every rank goes to rank j, compressed; rank j decodes the `world` rows it received straight
+    into ONE float32 shard -- no 16-bit scratch tensor, no separate add.  A codec with decompress_reduce(rows_per_acc,
+    accs, accumulate) sums all rows in ONE decode-reduce call (accumulate off: rank 0's row is stored, so the shard needs
+    no memset) with one status read; a codec without it (or a world of more than 64 ranks) stores rank 0's row and makes
+    one decode-accumulate call per further source rank, in ascending rank order on the current stream.  Either way the
+    result is, by construction, the sequential float32 sum in rank order, ((x_0 + x_1) + x_2) + ..., of the exactly
+    widened inputs: bit-identical on every run, between the two paths and to the same sum computed uncompressed.
+    Returns (shard_fp32, stats), stats as `compressed_all_gather`.  RuntimeError if a row fails to decode; on the
+    decode-reduce path the shard was then not partly summed (the call adds all rows or none).
+    `codec` needs compress(list) -> (uint8 [n, cap], int32 [n]) and, for the shard's sum, decompress_reduce(rows_per_acc,
+    accs, accumulate) -> uint8 status [len(accs)] or decompress_accumulate(rows, accs, accumulate) -> uint8 status [n];
+    a world of more than 64 ranks needs decompress_accumulate (RuntimeError without it)."""
+    codec = codec or GpuFloatCodec()
+    world = dist.get_world_size()
+    shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec)
     me = dist.get_rank()
     shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
     has_reduce = callable(getattr(codec, "decompress_reduce", None))
@@ -258,13 +275,31 @@ def compressed_all_reduce(tensor, codec=None):
     inputs, rounded ONCE to the input dtype (round to nearest even), bit-identical on every rank.  Returns (summed
     tensor in the input dtype, stats): the stats of the two exchanges added up.  `codec` needs what
     compressed_reduce_scatter and compressed_all_gather need, and compress_cast(list of float32, dtype) -> (uint8
-    [n, cap], int32 [n])."""
+    [n, cap], int32 [n]).
+
+    A codec with decompress_reduce_compress(rows_per_acc, accs, accumulate) -> (status, comp, sizes), in a world of at most
+    64 ranks, makes the middle ONE call: the received rows are summed into the shard and the shard's archive is written
+    by the same call, which counts the exponents while it sums instead of reading the shard again for a histogram.  The
+    result is bit-identical to the three-step path."""
     if tensor.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError("compressed_all_reduce: the tensor must be float16 or bfloat16")
     codec = codec or GpuFloatCodec()
     world = dist.get_world_size()
-    shard, rs = compressed_reduce_scatter(tensor, codec)
-    comp, sizes = codec.compress_cast([shard], tensor.dtype)
+    if callable(getattr(codec, "decompress_reduce_compress", None)) and world <= _MAX_REDUCE_SOURCES:
+        shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec)
+        me = dist.get_rank()
+        shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
+        status, comp, sizes = codec.decompress_reduce_compress([[recv[r, : int(all_sizes[r, me])] for r in range(world)]], [shard], False)
+        if not bool(status.all().item()):
+            raise RuntimeError("reduce-compress of the received rows failed: a row is malformed or the rows differ in length")
+        rs = {
+            "raw_bytes": tensor.numel() * tensor.element_size(),
+            "wire_bytes": world * width,
+            "payload_bytes": int(all_sizes[me].sum().item()),
+        }
+    else:
+        shard, rs = compressed_reduce_scatter(tensor, codec)
+        comp, sizes = codec.compress_cast([shard], tensor.dtype)
     out = torch.empty_like(tensor)
     rows = out.view(world, shard.numel())
     _, ag = _all_gather_archives(comp, sizes, lambda r: [rows[r]], shard.numel() * tensor.element_size(), codec)

@@ -660,6 +660,63 @@ def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_s
     return int(used.value)
 
 
+# ---------------------------------------------------------------- reduce-compress
+# (no reference op: dgpu_float_reduce_compress, include/dietgpu_amd.h)
+def decompress_data_reduce_compress(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
+                                    out_compressed=None, out_compressed_sizes=None, prob_bits=K_DEFAULT_PRECISION, dtype=None):
+    """`decompress_data_reduce(ts_in, ts_acc, accumulate)` and `compress_data_cast(ts_acc, dtype)` in ONE call: the sums
+    land in the float32 accumulators and, rounded to `dtype`, in archives of the sources' own type, without the second
+    read of the accumulators that the cast histogram makes -> (comp [n, maxSize] u8, sizes [n] i32, temp bytes used), as
+    compress_data_cast.  ts_in, ts_acc, accumulate, out_status and out_sizes as in decompress_data_reduce, with one
+    difference: every source must hold EXACTLY ts_acc[i].numel() words (fewer: out_status[i] = 0).  The accumulators
+    and, for members with out_status 1, the archives are bit for bit what the two calls leave.  A failed member keeps
+    its accumulator; its archive is a valid one of whatever the accumulator holds -- look at out_status.  `dtype`:
+    float16 or bfloat16, of the sources and of the archives (given: no host synchronisation; else read from the header
+    of ts_in[0][0])."""
+    _check(len(ts_in) > 0)
+    _check(len(ts_in) == len(ts_acc), "one list of sources per accumulator")
+    sources = len(ts_in[0])
+    _check(1 <= sources <= MAX_REDUCE_SOURCES, "between 1 and 64 sources per accumulator")
+    for srcs in ts_in:
+        _check(len(srcs) == sources, "every accumulator takes the same number of sources")
+    flat = [t for srcs in ts_in for t in srcs]  # member-major
+    _check(flat[0].is_cuda, "tensors must be on the GPU")
+    dev = flat[0].get_device()
+    for ti in flat:
+        _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous() and ti.dtype == torch.uint8)
+    for ta in ts_acc:
+        _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
+        _check(ta.dtype == torch.float32, "accumulators must be float32")
+    _check(dtype is None or dtype in (torch.float16, torch.bfloat16), "dtype (of sources and archives) must be float16 or bfloat16")
+    n = len(ts_acc)
+    _validate_status(out_status, out_sizes, n, dev)
+    with torch.cuda.device(dev):
+        tp, tb = _temp(temp_mem, dev)
+        if dtype is not None:
+            ft = _DTYPE_TO_FT[dtype]
+        else:
+            ft = _header_info(True, flat[:1], tp, tb)[1][0]
+            _check(ft in (_DTYPE_TO_FT[torch.float16], _DTYPE_TO_FT[torch.bfloat16]), "ts_in[0][0] is not a float16 / bfloat16 archive")
+        if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_compress"):
+            torch.ops.dietgpu_amd.set_precision(prob_bits)
+            try:
+                return torch.ops.dietgpu_amd.decompress_data_reduce_compress(flat, sources, ts_acc, ft, bool(accumulate), temp_mem,
+                                                                             out_status, out_sizes, out_compressed, out_compressed_sizes)
+            finally:
+                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+        _, mx = _total_and_max(ts_acc)
+        cols = _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
+        comp, sizes = _validate_out(out_compressed, out_compressed_sizes, n, cols, dev, ts_acc[0].device)
+        row = comp.size(1)
+        out_ptrs = (C.c_void_p * n)(*[comp.data_ptr() + i * row for i in range(n)])
+        used = C.c_size_t(0)
+        check(lib().dgpu_float_reduce_compress(
+            tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
+            _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), out_ptrs, _ptr(out_status), _ptr(out_sizes), _ptr(sizes),
+            _stream()))
+    return comp, sizes, int(used.value)
+
+
 def _check_slice_args(compress_as_float, ts_in, dtype):
     _check(len(ts_in) > 0)
     for t in ts_in:

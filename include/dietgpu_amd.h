@@ -68,7 +68,8 @@ const char* dgpu_version(void);
  * with against the library it finds at run time, so that a stale build fails at load instead of inside a call.  An entry
  * point that is only ADDED leaves every existing one as it was and does not move the version: a library without the new
  * symbol fails at load too, by symbol resolution, in anything that links it (dgpu_float_decode_accumulate,
- * dgpu_float_cast_compress and dgpu_float_decode_reduce were added at version 8). */
+ * dgpu_float_cast_compress, dgpu_float_decode_reduce, dgpu_float_reduce_compress and
+ * dgpu_float_reduce_compress_temp_bytes were added at version 8). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -362,6 +363,45 @@ int dgpu_float_cast_compress(
     uint32_t floatType /* of the ARCHIVE: DGPU_FLOAT16 or DGPU_BFLOAT16 */, int probBits,
     uint32_t numInBatch, const void* const* in /* float32 */, const uint32_t* inSize /* words */,
     void* const* out, uint32_t* outSize_dev, void* stream);
+
+/* ---- reduce-compress (no upstream equivalent) ------------------------------------------
+ * dgpu_float_decode_reduce into the float32 accumulators and dgpu_float_cast_compress of those accumulators in ONE
+ * call: the middle of a compressed all-reduce, where the reduced shard is sent on at once.  The reduce kernel counts
+ * the exponent bytes of the rounded sums while it stores them, so the cast histogram pass -- a second read of the shard --
+ * does not run; the table is normalised from those counts and the cast encoder reads the accumulators once.
+ *   - Accumulators: acc[i], outSuccess_dev[i] and outSize_dev[i] are bit for bit what dgpu_float_decode_reduce leaves
+ *     for the same arguments (layout, order of the adds, widening, all-or-nothing, what outSize_dev reports), with ONE
+ *     exception: every source of member i must state EXACTLY outCapacity[i] words -- the compress side codes
+ *     outCapacity[i] words of the accumulator.  A member whose sources state fewer fails like any other failing member.
+ *   - Archives, successful member: outArchive[i] and outArchiveSize_dev[i] (bytes) are byte for byte what
+ *     dgpu_float_cast_compress(floatType, probBits) writes for acc[i] afterwards (rounding: see there).
+ *   - Archives, failed member (outSuccess_dev[i] = 0): the accumulator keeps every bit; outArchive[i] is a well-formed
+ *     archive of the cast of whatever the accumulator holds, coded with the flat table (every symbol the same
+ *     probability): inside dgpu_float_max_compressed_size(floatType, outCapacity[i]) and decodable.  Look at
+ *     outSuccess_dev before sending it on.
+ *   - floatType is that of the sources AND of the archives: DGPU_FLOAT16 or DGPU_BFLOAT16.  DGPU_FLOAT32 is invalid
+ *     (there is no cast to do: dgpu_float_decode_reduce, then dgpu_float_compress).
+ *   - 1 <= numSources <= 64 (numSources == 1 does not forward anywhere: it is this call), numInBatch * numSources <=
+ *     65535, accumulate 0 or 1, probBits 9, 10 or 11, in[...] and outArchive[i] 16-byte aligned, acc[i] 4-byte aligned,
+ *     outCapacity[i] (words) within the size guard of dgpu_float_compress, no array null when numInBatch > 0
+ *     (outSuccess_dev, outSize_dev and outArchiveSize_dev may be null): DGPU_ERR_INVALID_ARGUMENT otherwise, with a
+ *     dgpu_last_error() text, before anything is enqueued.  An empty batch returns 0 with *tempUsed = 0.
+ *   - outArchive[i] has room for dgpu_float_max_compressed_size(floatType, outCapacity[i]).  The accumulators of
+ *     different members MUST NOT overlap each other or any archive buffer; sources may alias each other.
+ *   - No useChecksum, for the reason its two halves have none.
+ *   - Temp memory: at most dgpu_float_reduce_compress_temp_bytes(floatType, numInBatch, max outCapacity); too little
+ *     behaves as in every other call (library-owned overflow memory).  The counts live in library-owned per-stream
+ *     counters for numInBatch <= 64 and in temp memory beyond.  Nothing synchronises; capturable into a HIP graph after
+ *     one identical warm call on the stream. */
+size_t dgpu_float_reduce_compress_temp_bytes(uint32_t floatType, uint32_t numInBatch, uint32_t maxWords);
+int dgpu_float_reduce_compress(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources,
+    const void* const* in /* [numInBatch * numSources] */, const uint32_t* inBytes /* same shape */,
+    void* const* acc /* float32, [numInBatch] */, const uint32_t* outCapacity /* float words */,
+    void* const* outArchive /* [numInBatch] */,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev /* words */, uint32_t* outArchiveSize_dev /* bytes */,
+    void* stream);
 
 /* ---- float stride batches with capacities (no upstream equivalent) ---------------
  * For exchanging compressed rows at a FIXED width (README.md:68-72,104: compressed collectives): the rows of one

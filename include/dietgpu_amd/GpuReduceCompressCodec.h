@@ -1,0 +1,30 @@
+// Reduce-compress in the style of the dietgpu:: mirror (no reference equivalent): floatDecompressReduce into the float32
+// accumulators and floatCompressCast of those accumulators back to the sources' 16-bit type in ONE call, which counts
+// the exponents of the rounded sums while it stores them instead of reading the accumulators again for a histogram --
+// the middle of a compressed all-reduce.  Inline on top of dgpu_float_reduce_compress of ../dietgpu_amd.h, where the
+// contract is spelled out.  `config.floatType` is the type of the sources AND of the archives (kFloat16 or kBFloat16);
+// sources are member-major (source s of member i is in[i * numSources + s], inBytes of the same shape) and must state
+// exactly outCapacity[i] words; acc, outCapacity (float words), outArchive, outSuccess_dev, outSize_dev (words) and
+// outArchiveSize_dev (bytes) have numInBatch entries; outArchive[i] has room for getMaxFloatCompressedSize of
+// outCapacity[i].  A member with outSuccess_dev[i] = 0 keeps its accumulator; its archive holds whatever the accumulator
+// held.  The config's useChecksum is ignored, as in the two halves.
+#pragma once
+
+#include "GpuFloatCodec.h"
+
+namespace dietgpu {
+
+inline void floatDecompressReduceCompress(
+    StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, uint32_t numSources,
+    const void** in, const uint32_t* inBytes, float** acc, const uint32_t* outCapacity, void** outArchive,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream) {
+  uint32_t maxWords = 0;
+  for (uint32_t i = 0; i < numInBatch; ++i) maxWords = std::max(maxWords, outCapacity[i]);
+  detail::TempRegion t(res, stream, dgpu_float_reduce_compress_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords));
+  detail::checkRc(dgpu_float_reduce_compress(t.ptr, t.bytes, &t.used, (uint32_t)config.floatType, config.ansConfig.probBits,
+                                             accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, (void* const*)acc,
+                                             outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, stream),
+                  "floatDecompressReduceCompress");
+}
+
+}  // namespace dietgpu
