@@ -1038,6 +1038,12 @@ bool histogramLoadsNonTemporal(uint32_t ft) {
 // ticket for the encode kernel.
 // (DGPU_TWO_LEVEL_LOOKBACK=0: the single level everywhere -- A/B runs and tests)
 std::atomic<int> g_twoLevelLookback{envInt("DGPU_TWO_LEVEL_LOOKBACK", 1)};
+// dgpu_float_rolling_compress: last call's counts instead of a histogram pass (smoothed, NormalizeArgs::smoothCounts;
+// every element then has its own capacity, EncodeArgs::capAtMax) and / or this call's counts from the counting encoder.
+struct RollingCounts {
+  const uint32_t* countsIn = nullptr;
+  uint32_t* countsOut = nullptr;
+};
 struct EncodeShared {
   uint32_t* checksumTemp = nullptr;  // [B] the batch's checksums (computed by the first class's call)
   uint4* table = nullptr;            // [B][256] encoder tables, indexed by the element's own index
@@ -1051,7 +1057,13 @@ int encodeCommon(
     EncodeShared& shared /* what the groups of one call share */, const uint32_t* hist_dev /*may be null*/, uint32_t* outSize_dev,
     uint32_t outCapacity /* bytes at every archive pointer; block data beyond it is dropped */,
     uint32_t* histAcc_dev = nullptr /* the histogram in the stream's zero-at-rest counters instead of hist_dev (reduce-compress):
-                                       the normalisation reads them and puts them back to zero */) {
+                                       the normalisation reads them and puts them back to zero */,
+    const RollingCounts& rolling = RollingCounts{}) {
+  // (kCountingSource is the planner's: from here on the source is what the kernels are instantiated for)
+  sourceType &= ~kCountingSource;
+  // (rolling.countsIn arrives as hist_dev -- encodeBatch passes it as the call's histogram; here it only says that the
+  // histogram is another call's: smoothed, and every element clipped at its own maximum)
+  const bool counting = rolling.countsOut != nullptr, foreignTable = rolling.countsIn != nullptr;
   const uint32_t floatType = encArchiveType(sourceType);
   const uint32_t wordBytes = floatType ? floatWordBytes(floatType) : 1u;
   const uint32_t tileBlocks = group.tileBlocks, maxTiles = group.maxTiles, maxSize = group.maxSize;
@@ -1108,8 +1120,9 @@ int encodeCommon(
   const uint32_t numTickets = lists ? numListedTiles : (elemMap ? numElems : B * maxTiles);
   const uint32_t numWorkgroups = pairs ? (numTickets + 1u) / 2u : numTickets;  // (one per pair of elements / per tile)
   const bool wideStage = maxTiles <= kWideStageMaxTiles;
-  const EncodeVariant persistent = encoderVariant(P, sourceType, tileBlocks, false, wideStage);
-  const EncodeVariant hardware = encoderVariant(P, sourceType, tileBlocks, true, wideStage);
+  // (the counting form is persistent whatever dgpu_debug_set_encoder_dispatch says: it exists in that form only)
+  const EncodeVariant persistent = counting ? encoderVariantCounting(P, sourceType, tileBlocks) : encoderVariant(P, sourceType, tileBlocks, false, wideStage);
+  const EncodeVariant hardware = counting ? persistent : encoderVariant(P, sourceType, tileBlocks, true, wideStage);
   const bool bothForms = hardware.fn != persistent.fn;
   // The persistent grid is the persistent variant's own occupancy.  The spill pool must cover whichever form is
   // launched and the policy is decided before the form is: where both forms exist the larger occupancy counts there
@@ -1170,6 +1183,8 @@ int encodeCommon(
   n.tileSymbols = tileBlocks * kBlockSize;
   n.groupWords = groupWords;
   n.groupWordsPerElement = lookbackGroups * (kGroupArriveStride + 1u);
+  n.smoothCounts = foreignTable ? 1u : 0u;
+  n.countsOut = rolling.countsOut;
 
   const bool haveHist = hist_dev || histAcc_dev;
   if (!haveHist && tileBlocks == kBlocksPerSingleTile && maxTiles > 0 && floatType != kFloat32) {
@@ -1238,6 +1253,8 @@ int encodeCommon(
     e.outCapacity = outCapacity;
     e.useChecksum = (useChecksum && floatType) ? 1 : 0;
     e.checksum = (useChecksum && floatType) ? checksumTemp : nullptr;
+    e.capAtMax = foreignTable ? 1u : 0u;
+    e.countsOut = rolling.countsOut;
     int rc = launchVariant(enc, dim3(grid), stream, e);
     if (rc) return rc;
   }
@@ -1249,7 +1266,10 @@ int encodeCommon(
 int encodeBatch(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b,
     const uint32_t* histogram_dev /*may be null*/, uint32_t* outSize_dev, hipStream_t stream,
-    uint32_t outCapacity = 0xffffffffu /* as encodeCommon's */) {
+    uint32_t outCapacity = 0xffffffffu /* as encodeCommon's */, const RollingCounts& rolling = RollingCounts{}) {
+  // a counting call is planned without single-block kernels, one with last call's counts as one with a caller's histogram
+  if (rolling.countsOut) ft |= kCountingSource;
+  if (rolling.countsIn) histogram_dev = rolling.countsIn;
   StreamLease streamLease(stream);
   TempArena arena(temp_dev, tempBytes, streamLease);
   DeviceBatch d;
@@ -1260,7 +1280,7 @@ int encodeBatch(
   // every group on the kernels of its own geometry, one after the other
   EncodeShared shared;
   for (const LaunchGroup& g : groups) {
-    rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, g, d.work, shared, histogram_dev, outSize_dev, outCapacity);
+    rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, g, d.work, shared, histogram_dev, outSize_dev, outCapacity, nullptr, rolling);
     if (rc) break;
   }
   if (tempUsed) *tempUsed = arena.requested();
@@ -1280,13 +1300,13 @@ int ansEncodeImpl(
 // (cast: the batch holds float32 words and ft is the archive's 16-bit type)
 int floatCompressImpl(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b, uint32_t* outSize_dev,
-    hipStream_t stream, bool cast = false) {
+    hipStream_t stream, bool cast = false, const RollingCounts& rolling = RollingCounts{}) {
   bool done;
   int rc = checkCall(P, b.n, ft, tempUsed, /*errBatch*/ nullptr, &done,
                      "tensor larger than 1717538816 words: the maximum compressed size of its exponent plane exceeds INT32_MAX (GpuANSEncode.cu:22)",
                      b.maxSize);
   if (done) return rc;
-  return encodeBatch(temp_dev, tempBytes, tempUsed, cast ? (ft | kCastSource) : ft, P, useChecksum, b, nullptr, outSize_dev, stream);
+  return encodeBatch(temp_dev, tempBytes, tempUsed, cast ? (ft | kCastSource) : ft, P, useChecksum, b, nullptr, outSize_dev, stream, 0xffffffffu, rolling);
 }
 
 // Order of k_ans_decode's workgroups (kernels_decode.h: decodeTileOf).  Measured on MI355X, cold round trip
@@ -2036,6 +2056,36 @@ int dgpu_float_cast_compress(
   return floatCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, 0, b, outSize_dev, (hipStream_t)stream, true);
 }
 
+// ---- rolling-table compress (no upstream equivalent) ------------------------------------
+// The table of this call from the counts of the last one (countsIn_dev: no histogram pass), the counts of this call for
+// the next one (countsOut_dev: the counting encoder).  float16 / bfloat16 archives only: the float32 encoder has no
+// counting form.
+int dgpu_float_rolling_compress(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, uint32_t sourceFloat32, int probBits,
+    uint32_t numInBatch, const void* const* in, const uint32_t* inSize, const uint32_t* countsIn_dev,
+    uint32_t* countsOut_dev, void* const* out, uint32_t* outSize_dev, void* stream) {
+  DGPU_REQUIRE(floatType == kFloat16 || floatType == kBFloat16,
+               "rolling compress: floatType of the archive must be float16 or bfloat16 (float32 archives: dgpu_float_compress)");
+  DGPU_REQUIRE(sourceFloat32 <= 1u, "rolling compress: sourceFloat32 must be 0 or 1");
+  DGPU_REQUIRE((uintptr_t)countsIn_dev % 4 == 0 && (uintptr_t)countsOut_dev % 4 == 0, "rolling compress: counts must be 4-byte aligned");
+  if (!countsIn_dev && !countsOut_dev) {
+    return sourceFloat32 ? dgpu_float_cast_compress(temp_dev, tempBytes, tempUsed, floatType, probBits, numInBatch, in, inSize, out, outSize_dev, stream)
+                         : dgpu_float_compress(temp_dev, tempBytes, tempUsed, floatType, probBits, 0, numInBatch, in, inSize, out, outSize_dev, stream);
+  }
+  if (countsIn_dev && countsOut_dev && countsIn_dev != countsOut_dev) {
+    const uintptr_t a = (uintptr_t)countsIn_dev, c = (uintptr_t)countsOut_dev, bytes = (uintptr_t)numInBatch * kNumSymbols * 4u;
+    DGPU_REQUIRE(a + bytes <= c || c + bytes <= a, "rolling compress: countsIn_dev and countsOut_dev must be the same buffer or not overlap");
+  }
+  Batch b;
+  int rc = pointerBatch(&b, numInBatch, sourceFloat32 ? ptrSide(in, 4, "float32 input must be 4-byte aligned") : ptrSide(in, 2, kMsgFloatIn),
+                        ptrSide(out, 16, kMsgCompOut), inSize);
+  if (rc) return rc;
+  RollingCounts rolling;
+  rolling.countsIn = countsIn_dev;
+  rolling.countsOut = countsOut_dev;
+  return floatCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, 0, b, outSize_dev, (hipStream_t)stream, sourceFloat32 != 0u, rolling);
+}
+
 int dgpu_float_compress_split_size(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits,
     int useChecksum, uint32_t numInBatch, const void* in_dev, const uint32_t* inSplitSizes,
@@ -2099,6 +2149,8 @@ int dgpu_ans_calc_weights(
   NormalizeArgs n;
   n.sizes = viewPointers(nullptr, sizes_dev, uniformSize);
   n.hist = histogram_dev;
+  n.smoothCounts = 0;
+  n.countsOut = nullptr;
   n.histAcc = nullptr;
   n.histParts = 1;
   n.probBits = probBits;

@@ -96,6 +96,28 @@ inline EncodeVariant encoderVariantCast(int P, uint32_t archiveType, uint32_t ti
   });
 }
 
+// The counting form (kernels_encode.h, kCount): persistent tiled encoders of 2, 4 and 8 blocks for float16 / bfloat16
+// sources and their cast sources.  There is no hardware-dispatched, wide-stage or single-block form: single-block
+// members run on 2-block tiles (the plan of a counting call has no single-block class, work_plan.h).
+inline EncodeVariant encoderVariantCounting(int P, uint32_t ft, uint32_t tileBlocks) {
+  auto of = [&](auto p, auto f) -> EncodeVariant {
+    constexpr int kP = decltype(p)::value;
+    constexpr uint32_t kFT = decltype(f)::value;
+    auto tiled = [](auto tb) -> EncodeVariant {
+      constexpr uint32_t kTB = decltype(tb)::value;
+      return {k_ans_encode<kP, kFT, true, kTB, true, false, true>, encThreads(kTB), encCountLdsBytes(kP, kFT, kTB),
+              encIsCast(kFT) ? "k_ans_encode_cast_count" : "k_ans_encode_count"};
+    };
+    if (tileBlocks <= kBlocksPerTinyTile) return tiled(UintC<kBlocksPerTinyTile>{});
+    if (tileBlocks == kBlocksPerSmallTile) return tiled(UintC<kBlocksPerSmallTile>{});
+    return tiled(UintC<kBlocksPerTile>{});
+  };
+  return withProbBits(P, [&](auto p) {
+    if (encIsCast(ft)) return encArchiveType(ft) == kFloat16 ? of(p, UintC<kFloat16 | kCastSource>{}) : of(p, UintC<kBFloat16 | kCastSource>{});
+    return encArchiveType(ft) == kFloat16 ? of(p, UintC<kFloat16>{}) : of(p, UintC<kBFloat16>{});
+  });
+}
+
 // The encoder of tiles of `tileBlocks` blocks; ft: the archive's float type, with kCastSource for a cast source.
 //   * single-block tiles go to k_ans_encode_pair: two ELEMENTS per wavefront, always one workgroup per pair;
 //   * hwDispatch: one workgroup per tile, dispatched by the hardware in ticket order, instead of persistent workgroups

@@ -100,6 +100,24 @@ __host__ __device__ constexpr uint32_t encLdsBytes(int P, bool spill, uint32_t f
       + tileBlocks * 512u;                           // symbol ring, 16 rows per half-wave
 }
 
+// Counting form (k_ans_encode, kCount): the encoder also counts the exponent bytes it codes, in LDS bins behind the
+// symbol rings -- the histogram kernel's bin-major layout with lane slots (kernels_stats.h: a third of all exponents
+// are one value and same-address ds_add serialises).  Lane slots per bin, NOT measured: 8 for tiles of 8 and 4 blocks
+// (8 KiB: the 8-block 16-bit forms come to 32.1 KiB (bf16) / 36.1 KiB (fp16) per workgroup, four workgroups per CU where
+// the plain forms have six / five), 4 for the single wavefront of a 2-block tile (4 KiB).
+__host__ __device__ constexpr uint32_t encCountSlots(uint32_t tileBlocks) { return tileBlocks <= kBlocksPerTinyTile ? 4u : 8u; }
+__host__ __device__ constexpr uint32_t encCountBinBytes(uint32_t tileBlocks) { return kNumSymbols * encCountSlots(tileBlocks) * 4u; }
+__host__ __device__ constexpr uint32_t encCountLdsBytes(int P, uint32_t ft, uint32_t tileBlocks) {
+  return encLdsBytes(P, true, ft, tileBlocks) + encCountBinBytes(tileBlocks);
+}
+static_assert(4u * encCountLdsBytes(11, kFloat16, kBlocksPerTile) <= 160u * 1024u && 4u * encCountLdsBytes(11, kBFloat16, kBlocksPerTile) <= 160u * 1024u,
+              "four workgroups of the 8-block counting form per CU");
+
+// dgpu_float_max_compressed_size on the device (capi.hip: maxCompressedSizeHost; sizes the encode entry points accept)
+__host__ __device__ inline uint32_t encMaxArchiveBytes(uint32_t ft, uint32_t n) {
+  return ansOffsetInArchive(ft, n) + roundUp(ansOverhead(kBlockSize) + (kBlockSize + kBlockSize / 4u) * divUp(n, kBlockSize), 16u);
+}
+
 // descriptors a lane reads per look-back step (one round trip covers 64 x this many predecessor tiles)
 constexpr uint32_t kLookbackPerLane = 1;
 constexpr uint64_t kDescAggregate = 1ull << 62;
@@ -137,6 +155,10 @@ struct EncodeArgs {
                              // The host guarantees that header, tables and non-compressed planes fit.
   uint32_t useChecksum;      // float header only
   const uint32_t* checksum;  // [B] nullable (float header only)
+  uint32_t capAtMax;         // != 0 (a table that was not made from this data, dgpu_float_rolling_compress): element b's capacity
+                             // is encMaxArchiveBytes(its size) instead of outCapacity
+  uint32_t* countsOut;       // counting form only: [B][256], zeroed before launch (by the normalisation step); a tile's
+                             // exponent-byte counts are added with relaxed agent-scope atomics
 };
 
 struct TileShared {
@@ -625,6 +647,16 @@ __device__ __forceinline__ uint4 coherentLoad16(const uint4* p) {
   return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
 }
 
+// Counting form: the half-wave's own spill slot among its persistent workgroup's (`first`: the workgroup's first slot),
+// located where this rare path needs it -- as a per-lane pointer held from the kernel's prologue it is two registers the
+// counting row loop does not have.
+template <int P>
+__device__ __forceinline__ uint16_t* encOwnSpillSlot(uint16_t* first) {
+  uint32_t t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return first + (size_t)(t >> 5) * encSpillSlotWords(P);
+}
+
 // Encodes the rows of one block per half-wave.  Returns the words left in the LDS stage; `spilledOut` = words
 // flushed to the spill slot (kSpill), `stateOut` = the lane's final state, `overrunOut` = the block emitted more
 // words than stage (+ spill slot) can hold.  That cannot happen with a table made from this data's histogram (the
@@ -651,7 +683,13 @@ static_assert(encGuardLimit(9, 120) + 256u <= encStageWords(9) + kEncGuardSlackW
 // trip per eight rows (bf16, 256 x 530 000: encode 120 -> 112 us, 32768 x 4000: 237 -> 138 us;
 // profiles/r05_ab_partial_blocks.txt).
 // kWide (with kSpill): the stage holds encStageCap(P, true, FT, true) words.
-template <int P, uint32_t FT, bool kFull, bool kSpill, bool kGuard = false, bool kPool = false, bool kTail = false, bool kWide = false>
+// kCountSlots != 0 (counting form): every symbol coded is also added to the workgroup's LDS bins at `countBins` (an LDS
+// address; bin c, slot s at countBins + (c * kCountSlots + s) * 4): the full-block path from the exponent bytes the
+// split leaves in registers, one ds_add per row; tail chunks from the ring, bounded by n; the scalar path per symbol.
+// A half without a block (n == 0: idle, or the shadow of a wave's single full block) counts nothing.
+typedef __attribute__((address_space(3))) uint32_t LdsU32e;
+template <int P, uint32_t FT, bool kFull, bool kSpill, bool kGuard = false, bool kPool = false, bool kTail = false, bool kWide = false,
+          uint32_t kCountSlots = 0>
 __device__ __forceinline__ uint32_t encodeRows(
     const ChunkSource<FT>& src,
     uint32_t n,                           // symbols in this half's block (0 = idle half)
@@ -665,8 +703,27 @@ __device__ __forceinline__ uint32_t encodeRows(
     uint32_t& spilledOut,                 // words flushed to it (multiple of 8)
     uint32_t& stateOut,
     bool& overrunOut,
-    SpillPool* pool = nullptr) {
+    SpillPool* pool = nullptr,
+    uint32_t countBins = 0,
+    bool countUpper = true /* wave-uniform, full blocks: false = the upper half shadows the lower half's block */) {
   static_assert(!kPool || kSpill, "");
+  constexpr bool kCount = kCountSlots != 0u;
+  // this lane's slot column (the two halves of a wavefront share the slots: ds_add is atomic), formed where it is used
+  // from a laundered lane index: held across the row loop it costs a register that loop does not have
+  [[maybe_unused]] auto binsColumn = [&]() -> uint32_t {
+    uint32_t slot = hl;
+    asm volatile("" : "+v"(slot));
+    return countBins + (slot & (kCountSlots ? kCountSlots - 1u : 0u)) * 4u;
+  };
+  // (the addend lives in a register, ds_add_u32 takes no literal: made where it is used, for the same reason)
+  [[maybe_unused]] auto countSym = [&](uint32_t column, uint32_t sym, uint32_t one) {
+    __hip_atomic_fetch_add((LdsU32e*)(uintptr_t)(column + sym * (kCountSlots * 4u)), one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  };
+  [[maybe_unused]] auto countOne = []() -> uint32_t {
+    uint32_t one;
+    asm volatile("v_mov_b32 %0, 1" : "=v"(one));
+    return one;
+  };
   static_assert(!kTail || kFull, "kTail is a mode of the chunked path");
   const uint32_t laneMaskLt = (1u << hl) - 1u;
   uint32_t state = kStartState;
@@ -693,6 +750,8 @@ __device__ __forceinline__ uint32_t encodeRows(
     if constexpr (kPool) {
       if (pool->pair == kNoSpillPair) pool->pair = spillAcquire(*pool, blockIdx.x);  // wave-uniform
       spill = pool->base + ((size_t)pool->pair * 2u + (upper ? 1u : 0u)) * encSpillSlotWords(P);
+    } else if constexpr (kCount && kSpill) {
+      spill = encOwnSpillSlot<P>(pool->base);  // (pool->base: the workgroup's first slot)
     }
     uint4* dst = (uint4*)(spill + spilled);
     uint32_t hlf = hl;  // (kPool: laundered, so that the 64-bit slot offsets of this rare path are computed here)
@@ -763,7 +822,26 @@ __device__ __forceinline__ uint32_t encodeRows(
     typename ChunkSource<FT>::Raw cur = kTail ? src.loadTail(0, hl, n) : src.load(0, hl);
 #pragma unroll 1
     for (uint32_t c = 0; c < numChunks; ++c) {
-      if (kTail) src.consumeTail(cur, c, hl, ring, n);
+      if constexpr (kCount && kTail) {
+        src.consumeTail(cur, c, hl, ring, n);
+        // the lane's own slice of the chunk, read back from the ring (LDS operations of one wave execute in order)
+        const uint32_t first = (c * 32u + hl) * kChunkRows;
+        const uint32_t valid = n > first ? (n - first < kChunkRows ? n - first : kChunkRows) : 0u;
+        const uint32_t column = binsColumn(), one = countOne();
+        for (uint32_t j = 0; j < valid; ++j) countSym(column, (uint32_t)ring[hl * kChunkRows + j], one);
+      } else if constexpr (kCount) {
+        constexpr uint32_t kCompRegs = ChunkSource<FT>::kCompRegs;
+        static_assert(kCompRegs * 4u == kChunkRows, "a lane splits one symbol per row of the chunk");
+        uint32_t comp[kCompRegs];
+        src.splitStore(cur, c, hl, comp);
+        if constexpr (kCompRegs == 4u) *(uint4*)(ring + hl * 16u) = make_uint4(comp[0], comp[1], comp[2], comp[3]);
+        else *(uint2*)(ring + hl * 8u) = make_uint2(comp[0], comp[1]);
+        if (countUpper || !upper) {
+          const uint32_t column = binsColumn(), one = countOne();
+#pragma unroll
+          for (uint32_t j = 0; j < kChunkRows; ++j) countSym(column, (comp[j / 4u] >> (8u * (j % 4u))) & 0xffu, one);
+        }
+      } else if (kTail) src.consumeTail(cur, c, hl, ring, n);
       else src.consume(cur, c, hl, ring);
       if (c + 1 < numChunks) cur = kTail ? src.loadTail(c + 1, hl, n) : src.load(c + 1, hl);
       auto symAt = [&](int r) -> uint32_t { return (uint32_t)ring[r * 32 + hl]; };
@@ -805,7 +883,11 @@ __device__ __forceinline__ uint32_t encodeRows(
 #pragma unroll
       for (uint32_t j = 0; j < kFlushRows; ++j) {
         const uint32_t i = (row0 + j) * 32u + hl;
-        taddr[j] = tableLds + ((src.splitAt(i, word[j], i < n) & 0xffu) << 4);
+        const uint32_t sym = src.splitAt(i, word[j], i < n) & 0xffu;
+        if constexpr (kCount) {
+          if (i < n) countSym(binsColumn(), sym, countOne());
+        }
+        taddr[j] = tableLds + (sym << 4);
       }
       uint4 ent[2] = {ldsTableEntry(taddr[0]), ldsTableEntry(taddr[1])};
 #pragma unroll
@@ -964,9 +1046,18 @@ __device__ __forceinline__ uint32_t lookBackTwoLevel(const uint64_t* desc, uint6
 // histogram that does not cover the data, see encodeRows).  The element's last tile finds the flag in its inclusive
 // prefix and reports the element as FAILED -- outSize[b] = 0, archive magic cleared -- instead of as a success with
 // a corrupt archive.  (Upstream has no such outcome: its per-block scratch is simply overrun, GpuANSEncode.cuh:355-358.)
-template <int P, uint32_t FT, bool kSpill, uint32_t kTB, bool kPersistent, bool kWide = false>
+//
+// kCount (the counting form, dgpu_float_rolling_compress with countsOut): the workgroup also counts the exponent bytes
+// of the symbols it codes (encodeRows, kCountSlots) in LDS bins behind the rings, and at the end of every tile folds the
+// bins, puts them back to zero and adds the non-zero totals to a.countsOut[b] with relaxed agent-scope atomics.  A tile
+// is encoded by exactly one workgroup (the claim words decide), so it is counted exactly once, stolen or not.  Exists
+// for persistent spilling tiles of float16 / bfloat16 archives (plain and cast sources), without the wide stage.
+template <int P, uint32_t FT, bool kSpill, uint32_t kTB, bool kPersistent, bool kWide = false, bool kCount = false>
 __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_ans_encode(EncodeArgs a) {
   static_assert(kTB >= 2u, "single-block elements are k_ans_encode_pair's");
+  static_assert(!kCount || (kSpill && kPersistent && !kWide && (encArchiveType(FT) == kFloat16 || encArchiveType(FT) == kBFloat16)),
+                "the counting form exists for persistent 16-bit float tiles");
+  constexpr uint32_t kCountSlots = kCount ? encCountSlots(kTB) : 0u;
   static_assert(!kWide || (kSpill && encArchiveType(FT) != kFloat16 && kTB == kBlocksPerTile && kPersistent), "the wide stage exists for persistent 8-block bf16 / fp32 tiles");
   constexpr uint32_t AT = encArchiveType(FT);  // the archive's float type (FT: the source's, see kCastSource)
   constexpr uint32_t kThreads = encThreads(kTB);
@@ -977,6 +1068,7 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
   TileShared* sh = (TileShared*)(smem + 4096);
   uint16_t* sStage = (uint16_t*)(smem + 4096 + 128);
   uint8_t* sRing = smem + 4096 + 128 + kTB * kCap * 2u;
+  [[maybe_unused]] uint32_t* sBins = (uint32_t*)(sRing + kTB * 512u);  // kCount: [256][kCountSlots]
 
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
@@ -992,12 +1084,18 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
   // blockIdx.x does not bound what is resident and a wavefront takes a pair from the pool when it has to (SpillPool)
   constexpr bool kPool = kSpill && !kPersistent;
   static_assert(!kPool || kTB < kBlocksPerTile, "8-block float tiles run persistent (hardware dispatch measured no gain there)");
-  uint16_t* spillSlot = (kSpill && !kPool) ? a.spill + ((size_t)blockIdx.x * kTB + hw) * encSpillSlotWords(P) : nullptr;
+  uint16_t* spillSlot = (kSpill && !kPool && !kCount) ? a.spill + ((size_t)blockIdx.x * kTB + hw) * encSpillSlotWords(P) : nullptr;
   SpillPool pool;
-  pool.base = a.spill;
+  pool.base = kCount ? a.spill + (size_t)blockIdx.x * kTB * encSpillSlotWords(P) : a.spill;  // (kCount: see encOwnSpillSlot)
   pool.flags = a.spillFlags;
   pool.pairs = a.spillPairs;
   pool.pair = kNoSpillPair;
+  [[maybe_unused]] uint32_t binsLds = 0;
+  if constexpr (kCount) {
+    // (every path to the first row step crosses a workgroup barrier)
+    for (uint32_t i = tid; i < kNumSymbols * kCountSlots / 4u; i += kThreads) ((uint4*)sBins)[i] = make_uint4(0, 0, 0, 0);
+    binsLds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)sBins;
+  }
 
   if (a.absentModulo && blockIdx.x % a.absentModulo == 1u) {
     // test hook: a workgroup that becomes resident late (~0.5 ms after the others)
@@ -1091,7 +1189,9 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
           if (size + tid < roundUp(size, 16u)) nc1[size + tid] = 0;
         } else {
           uint8_t* nc = archive + 16u;
-          if (size + tid < roundUp(size, 16u)) nc[size + tid] = 0;
+          uint32_t t = tid;  // (counting form: laundered, the pad's address is not worth a register pair across the tile loop)
+          if constexpr (kCount) asm volatile("" : "+v"(t));
+          if (size + t < roundUp(size, 16u)) nc[size + t] = 0;
         }
       }
 
@@ -1123,8 +1223,8 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
       uint32_t spilled = 0;  // words already in the spill slot
       bool overrun = false;
       if (waveFull || waveHalf) {
-        words = encodeRows<P, FT, true, kSpill, false, kPool, false, kWide>(src, n, kRowsPerBlock, tableLds, stageLds, sRing + hw * 512u, hl, upper,
-                                                              spillSlot, spilled, state, overrun, &pool);
+        words = encodeRows<P, FT, true, kSpill, false, kPool, false, kWide, kCountSlots>(src, n, kRowsPerBlock, tableLds, stageLds, sRing + hw * 512u, hl, upper,
+                                                              spillSlot, spilled, state, overrun, &pool, binsLds, waveFull);
       } else {
         // rows needed by the larger of the two halves (uniform)
         uint32_t nA = 0;
@@ -1133,11 +1233,11 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
           nA = size - beginA < kBlockSize ? size - beginA : kBlockSize;  // first half is never smaller than the second
         }
         if (aligned) {  // uniform: the chunked path bounded by n (kTail); else the scalar path
-          words = encodeRows<P, FT, true, kSpill, false, kPool, true, kWide>(src, n, divUp(nA, 32u), tableLds, stageLds, sRing + hw * 512u, hl,
-                                                                      upper, spillSlot, spilled, state, overrun, &pool);
+          words = encodeRows<P, FT, true, kSpill, false, kPool, true, kWide, kCountSlots>(src, n, divUp(nA, 32u), tableLds, stageLds, sRing + hw * 512u, hl,
+                                                                      upper, spillSlot, spilled, state, overrun, &pool, binsLds);
         } else {
-          words = encodeRows<P, FT, false, kSpill, false, kPool, false, kWide>(src, n, divUp(nA, 32u), tableLds, stageLds, nullptr, hl, upper, spillSlot,
-                                                                 spilled, state, overrun, &pool);
+          words = encodeRows<P, FT, false, kSpill, false, kPool, false, kWide, kCountSlots>(src, n, divUp(nA, 32u), tableLds, stageLds, nullptr, hl, upper, spillSlot,
+                                                                 spilled, state, overrun, &pool, binsLds);
         }
       }
 
@@ -1241,12 +1341,15 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
         const uint64_t dataOff = (uint64_t)ansOffsetInArchive(AT, size) + ansOverhead(nb) + 2ull * (sh->tileBase + sh->localOff[hw]);
         uint4* dst = (uint4*)(archive + dataOff);
         // 16-byte vectors of this block that still fit the caller's capacity (all of them under the reference's contract)
-        const uint64_t room = (uint64_t)a.outCapacity > dataOff ? ((uint64_t)a.outCapacity - dataOff) / 16u : 0u;
+        // (a.capAtMax: the element's own maximum -- only a table that was not made from this data can reach it)
+        const uint64_t capacity = (FT != 0u && a.capAtMax) ? (uint64_t)encMaxArchiveBytes(AT, size) : (uint64_t)a.outCapacity;
+        const uint64_t room = capacity > dataOff ? (capacity - dataOff) / 16u : 0u;
         uint32_t fit = room > 0xffffffffull ? 0xffffffffu : (uint32_t)room;
         if (kSpill && spilled) {
           // spilled vectors first (written by this wave; its stores must have been performed)
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          const uint4* sp = (const uint4*)(kPool ? pool.base + ((size_t)pool.pair * 2u + (upper ? 1u : 0u)) * encSpillSlotWords(P) : spillSlot);
+          const uint4* sp = (const uint4*)(kPool ? pool.base + ((size_t)pool.pair * 2u + (upper ? 1u : 0u)) * encSpillSlotWords(P)
+                                                 : (kCount ? encOwnSpillSlot<P>(pool.base) : spillSlot));
           uint32_t sv = spilled / kBlockAlignWords;
           const uint32_t svFit = sv < fit ? sv : fit;
           // (the lane index is laundered: what this rare block derives from it -- 64-bit slot offsets -- is then computed
@@ -1260,9 +1363,31 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
         uint32_t vecs = roundUp(words, kBlockAlignWords) / kBlockAlignWords;
         vecs = vecs < fit ? vecs : fit;
         const uint4* s4 = (const uint4*)stage;
+        if constexpr (kCount) {  // (laundered like the pad and the spill slot: one register less across the row loop)
+          uint32_t t = tid;
+          asm volatile("" : "+v"(t));
+          s4 = (const uint4*)(sStage + (size_t)(t >> 5) * kCap);
+        }
         for (uint32_t i = hl; i < vecs; i += 32u) streamStore<kNtEncStores>(&dst[i], s4[i]);
       }
       if (kPool && pool.pair != kNoSpillPair) spillRelease(pool);  // wave-uniform
+      if constexpr (kCount) {
+        // The tile's counts join the element's.  Every wave added its last count before the two barriers above; the
+        // bins are zero again before the next tile's first count, which lies behind that tile's first barrier.
+        uint32_t first = tid;  // (laundered: the bin's address in a.countsOut is formed here, not in the kernel's prologue)
+        asm volatile("" : "+v"(first));
+        for (uint32_t c = first; c < kNumSymbols; c += kThreads) {
+          uint4* slots = (uint4*)(sBins + c * kCountSlots);  // bin-major: a bin's slots are consecutive (histFold)
+          uint32_t sum = 0;
+#pragma unroll
+          for (uint32_t k = 0; k < kCountSlots / 4u; ++k) {
+            const uint4 v = slots[k];
+            sum += v.x + v.y + v.z + v.w;
+            slots[k] = make_uint4(0, 0, 0, 0);
+          }
+          if (sum) __hip_atomic_fetch_add(a.countsOut + (size_t)b * kNumSymbols + c, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
     }  // tiles [tileLo, tile0] of element b
   }
 }

@@ -199,6 +199,13 @@ struct NormalizeArgs {
   // second level of the encoder's look-back (EncodeArgs::groupWords), cleared here too; null / 0: none
   uint64_t* groupWords;      // [numInBatch][groupWordsPerElement]
   uint32_t groupWordsPerElement;
+  // dgpu_float_rolling_compress.  smoothCounts: `hist` holds counts of OTHER data (last call's): every count c becomes
+  // min(max(c, 1), size(b)), so every symbol has a probability >= 1 -- any data can be coded and no block can emit more
+  // than the proven worst case (encStageWords) -- and the arithmetic below stays in range whatever the buffer holds.
+  // countsOut (nullable, [numInBatch][256]): put to zero here, after the counts were read (it may BE `hist`), for the
+  // counting encoder that follows on the stream.
+  uint32_t smoothCounts;
+  uint32_t* countsOut;
 };
 
 // The static part of the ANS archive header of element b (the fields ansEncodeCoalesce writes at
@@ -305,6 +312,10 @@ __device__ __forceinline__ void normalizeElement(const NormalizeArgs& a, const u
       }
       for (; x < histParts; ++x) count += part(x);
     }
+    if (a.smoothCounts) {
+      count = count < 1u ? 1u : count;
+      count = count > total ? total : count;
+    }
     // :215  qProb = kProbWeight * ((float)count / (float)totalNum), truncated.
     // Explicit round-to-nearest divide and multiply: no fma contraction, no
     // approximate reciprocal.
@@ -347,6 +358,7 @@ __device__ __forceinline__ void normalizeElement(const NormalizeArgs& a, const u
 
   }
 
+  if (a.countsOut) a.countsOut[(size_t)b * kNumSymbols + tid] = 0u;
   if (a.encTable) a.encTable[b * kNumSymbols + tid] = encTableEntry(pdf, cdf, P);
   if (a.refTable) {
     // the reference's table (pdf, cdf, 33-bit magic, shift), :349-358

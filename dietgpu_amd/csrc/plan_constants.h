@@ -24,7 +24,12 @@ DGPU_HD inline uint32_t floatWordBytes(uint32_t ft) { return ft == kFloat32 ? 4u
 // kCastSource set.  Everything about the ARCHIVE (layout, header, stage size) goes by encArchiveType(FT).
 constexpr uint32_t kCastSource = 0x100u;
 DGPU_HD constexpr bool encIsCast(uint32_t ft) { return (ft & kCastSource) != 0u; }
-DGPU_HD constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~kCastSource; }
+// kCountingSource (a PLANNING flag only, never a template parameter): the call runs the counting form of the encoder
+// (kernels_encode.h, kCount), which like the cast sources exists as tiles of 2, 4 and 8 blocks only.
+constexpr uint32_t kCountingSource = 0x200u;
+DGPU_HD constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~(kCastSource | kCountingSource); }
+// whether single-block elements of such a call have kernels of their own (k_ans_encode_pair, k_stats_single)
+DGPU_HD constexpr bool encHasSingleBlockKernels(uint32_t ft) { return (ft & (kCastSource | kCountingSource)) == 0u && ft != kFloat32; }
 
 // Encoder: blocks per tile = per workgroup.  8 (256 threads: 4 wave64 x 2 half-waves); 4 (128 threads) for batches whose
 // elements have at most 4 blocks -- an 8-block tile would leave half of its waves without a block there; a single

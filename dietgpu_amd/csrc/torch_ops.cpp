@@ -598,6 +598,54 @@ std::tuple<at::Tensor, at::Tensor, int64_t> compress_data_cast(
   return {std::move(comp), std::move(sizes), (int64_t)used};
 }
 
+// Rolling-table compress (no reference op): compress_data / compress_data_cast with the tables made from the counts the
+// last call left (counts_in) and this call's counts taken by the encoder (counts_out): dgpu_float_rolling_compress.
+// float_type (1 = float16, 2 = bfloat16) is that of the archives; source_float32: ts_in are float32 and are rounded.
+std::tuple<at::Tensor, at::Tensor, int64_t> compress_data_rolling(
+    const std::vector<at::Tensor>& tIns, const std::optional<at::Tensor>& countsIn, const std::optional<at::Tensor>& countsOut,
+    int64_t floatType, bool sourceFloat32, const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outCompressed,
+    const std::optional<at::Tensor>& outCompressedSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tIns.size();
+  const at::ScalarType want = sourceFloat32 ? at::ScalarType::Float : dtypeFromFloatType((uint32_t)floatType);
+  int64_t maxWords = 0;
+  for (auto& t : tIns) {
+    TORCH_CHECK(t.device().is_cuda());
+    TORCH_CHECK(t.is_contiguous());
+    TORCH_CHECK(t.get_device() == dev);
+    TORCH_CHECK(t.scalar_type() == want, "dietgpu: the inputs must be float32 (source_float32) or of the archives' type");
+    maxWords = std::max<int64_t>(maxWords, t.numel());
+  }
+  for (const std::optional<at::Tensor>* c : {&countsIn, &countsOut}) {
+    if (!*c) continue;
+    TORCH_CHECK((*c)->device().is_cuda() && (*c)->get_device() == dev && (*c)->is_contiguous() && (*c)->scalar_type() == at::kInt,
+                "dietgpu: counts must be contiguous int32 tensors on the tensors' GPU");
+    TORCH_CHECK((*c)->dim() == 2 && (*c)->size(0) == (int64_t)n && (*c)->size(1) == 256, "dietgpu: counts must be [len(ts_in), 256]");
+  }
+  at::Tensor comp, sizes;
+  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)maxWords), dev,
+                  tIns[0].device(), comp, sizes);
+  std::vector<const void*> inPtrs(n);
+  std::vector<uint32_t> inSize(n);
+  std::vector<void*> compPtrs(n);
+  for (size_t i = 0; i < n; ++i) {
+    inPtrs[i] = tIns[i].data_ptr();
+    inSize[i] = (uint32_t)tIns[i].numel();
+    compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
+  }
+  size_t used = 0;
+  check(dgpu_float_rolling_compress(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, sourceFloat32 ? 1u : 0u, precision(), (uint32_t)n,
+                                    inPtrs.data(), inSize.data(), ptrOrNull<const uint32_t>(countsIn), ptrOrNull<uint32_t>(countsOut),
+                                    compPtrs.data(), (uint32_t*)sizes.data_ptr(), streamOf(dev)),
+        "floatCompressRolling", true);
+  return {std::move(comp), std::move(sizes), (int64_t)used};
+}
+
 // Reduce-compress (no reference op): decompress_data_reduce into ts_acc and compress_data_cast of ts_acc in one call
 // (dgpu_float_reduce_compress).  ts_in as decompress_data_reduce's; float_type (1 = float16, 2 = bfloat16) is that of the
 // sources and of the archives.  Output conventions of compress_data_cast.
@@ -693,6 +741,9 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "compress_data_cast(Tensor[] ts_in, int float_type, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::compress_data_cast);
+  m.def(
+      "compress_data_rolling(Tensor[] ts_in, Tensor? counts_in, Tensor? counts_out, int float_type, bool source_float32=False, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
+      &dietgpu_amd::compress_data_rolling);
   m.def(
       "decompress_data_reduce_compress(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::decompress_data_reduce_compress);

@@ -38,11 +38,11 @@ struct LaunchGroup {
 
 // ---- Geometry ----
 // blocks per encoder tile for a batch whose largest element has `maxSize` symbols; ft: what is encoded (0: raw bytes; a
-// float type, with kCastSource for a cast call, which has no single-block kernels: its single-block elements run on
-// 2-block tiles)
+// float type, with kCastSource for a cast call or kCountingSource for a counting one, which have no single-block
+// kernels: their single-block elements run on 2-block tiles)
 inline uint32_t encTileBlocksFor(uint32_t maxSize, uint32_t ft = 0) {
   const uint32_t blocks = divUp(maxSize, kBlockSize);
-  if (encIsCast(ft) && blocks <= kBlocksPerTinyTile) return kBlocksPerTinyTile;
+  if ((ft & (kCastSource | kCountingSource)) != 0u && blocks <= kBlocksPerTinyTile) return kBlocksPerTinyTile;
   return blocks <= kBlocksPerSingleTile ? kBlocksPerSingleTile
       : blocks <= kBlocksPerTinyTile    ? kBlocksPerTinyTile
       : blocks <= kBlocksPerSmallTile   ? kBlocksPerSmallTile
@@ -294,9 +294,9 @@ bool planClassesCached(const PlanPolicy& policy, const std::vector<uint32_t>& si
 // ft: as encTileBlocksFor's; a call with a caller's histogram is never split into classes and lists no histogram parts.
 inline void planEncodeCall(const PlanPolicy& policy, const std::vector<uint32_t>& sizes, uint32_t ft, uint32_t maxSize, bool callerHist,
                            std::vector<LaunchGroup>* groups, std::vector<uint32_t>* work) {
-  // (cast calls and float32 have no single-block kernels)
+  // (cast calls, counting calls and float32 have no single-block kernels)
   auto classes = [&](std::vector<LaunchGroup>* gr, std::vector<uint32_t>* wk) {
-    return planClasses(policy, sizes, [](uint32_t sz) { return encTileBlocksFor(sz); }, ft != kFloat32 && !encIsCast(ft), true, ft, gr, wk);
+    return planClasses(policy, sizes, [](uint32_t sz) { return encTileBlocksFor(sz); }, encHasSingleBlockKernels(ft), true, ft, gr, wk);
   };
   if (!callerHist && planClassesCached(policy, sizes, ft, classes, groups, work)) return;
   LaunchGroup g = encodeRectangle(maxSize, ft);

@@ -91,16 +91,50 @@ def max_over_ranks(seconds, device):
 class GpuFloatCodec:
     """Default codec of the compressed collectives: the HIP float codec through `torch.ops.dietgpu.*`
     (csrc/torch_ops.cpp over the C ABI: no per-call Python marshalling of pointer arrays).  `temp_mem`
-    (optional uint8 tensor) is handed to every call, as the reference's ops take it."""
+    (optional uint8 tensor) is handed to every call, as the reference's ops take it.
 
-    def __init__(self, temp_mem=None):
+    `rolling=True`: `compress` / `compress_cast` go through `ops.compress_data_rolling`.  The codec keeps one counts
+    tensor per (archive dtype, cast or not, number of tensors, their sizes); the first call for such a key counts the
+    usual way, every later one makes its tables from the counts the call before it left and leaves its own -- no
+    histogram pass in steady state.  Any table is lossless, so what the collectives deliver is bit for bit the same;
+    only the archive sizes depend on how far the tensors moved since the last call (and they are a few per cent above
+    the plain codec's even then: every symbol keeps a probability).  Every rolling call after a
+    key's first reads one flag back from the device ("a row is larger than its capacity": that call is then repeated
+    with tables of the tensors' own), so `compress` synchronises with the stream once per call."""
+
+    def __init__(self, temp_mem=None, rolling=False):
         from . import load_torch_ops
 
         self.ops = load_torch_ops()
         self.temp_mem = temp_mem
         self.dtype = None
+        self.rolling = bool(rolling)
+        self._rolling_state = {}  # key -> (counts int32 [n, 256], row capacities int64 [n])
+
+    def _compress_rolling(self, tensors, dtype, cast):
+        from . import ops
+
+        key = (dtype, cast, len(tensors), tuple(t.numel() for t in tensors))
+        state = self._rolling_state.get(key)
+        first = state is None
+        if first:
+            dev = tensors[0].device
+            caps = torch.tensor([ops.max_float_compressed_size(torch.empty(0, dtype=dtype), t.numel()) for t in tensors],
+                                dtype=torch.int64, device=dev)
+            state = self._rolling_state[key] = (torch.empty((len(tensors), 256), dtype=torch.int32, device=dev), caps)
+        counts, caps = state
+        comp, sizes, _ = ops.compress_data_rolling(tensors, None if first else counts, counts, dtype if cast else None, self.temp_mem)
+        # a row larger than its capacity is incomplete (counts that fit nothing, tensors of millions of words): once more,
+        # with tables of the tensors' own
+        # (sizes are uint32 in an int32 tensor, and both they and the capacities can pass 2^31: compared as int64)
+        if not first and bool(((sizes[: len(tensors)].to(torch.int64) & 0xFFFFFFFF) > caps).any().item()):
+            comp, sizes, _ = ops.compress_data_rolling(tensors, None, counts, dtype if cast else None, self.temp_mem)
+        return comp, sizes
 
     def compress(self, tensors):
+        if self.rolling and tensors[0].dtype in (torch.float16, torch.bfloat16):
+            self.dtype = tensors[0].dtype
+            return self._compress_rolling(tensors, tensors[0].dtype, False)
         comp, sizes, _ = self.ops.compress_data(True, tensors, False, self.temp_mem)
         self.dtype = tensors[0].dtype  # (what decompress_accumulate's rows hold: the collectives exchange one dtype)
         return comp, sizes
@@ -109,8 +143,10 @@ class GpuFloatCodec:
         """float32 tensors -> archives of `dtype` (float16 / bfloat16), rounded in registers: no 16-bit scratch tensor"""
         from . import ops
 
-        comp, sizes, _ = ops.compress_data_cast(tensors, dtype, self.temp_mem)
         self.dtype = dtype
+        if self.rolling:
+            return self._compress_rolling(tensors, dtype, True)
+        comp, sizes, _ = ops.compress_data_cast(tensors, dtype, self.temp_mem)
         return comp, sizes
 
     def decompress(self, rows, outs):

@@ -355,6 +355,64 @@ def compress_data_cast(ts_in, dtype, temp_mem=None, out_compressed=None, out_com
     return comp, sizes, int(used.value)
 
 
+# ------------------------------------------------------- rolling-table compress
+# (no reference op: dgpu_float_rolling_compress, include/dietgpu_amd.h)
+def _validate_counts(counts, rows, dev, name):
+    if counts is None:
+        return
+    _check(counts.dtype == torch.int32 and counts.is_cuda and counts.is_contiguous() and counts.get_device() == dev,
+           f"{name} must be a contiguous int32 tensor on the tensors' GPU")
+    _check(counts.dim() == 2 and counts.size(0) == rows and counts.size(1) == 256, f"{name} must be [len(ts_in), 256]")
+
+
+def compress_data_rolling(ts_in, counts_in, counts_out, dtype=None, temp_mem=None, out_compressed=None,
+                          out_compressed_sizes=None, prob_bits=K_DEFAULT_PRECISION):
+    """compress_data(True, ts_in) -- or, with `dtype` given for float32 tensors, compress_data_cast(ts_in, dtype) -- for
+    tensors that come back step after step.  `counts_in` (int32 [n, 256] on the GPU, or None): the exponent counts the
+    last call left; the tables are made from them and no histogram pass reads the tensors.  `counts_out` (the same, or
+    None): receives this call's counts, which the encoder takes while it codes.  The same tensor may be passed as both.
+    Any counts give a lossless archive every decoder reads; only its size depends on how well they fit (and it is a few
+    per cent above compress_data's even when they fit: every symbol keeps a probability).  With
+    `counts_in` a size above `max_float_compressed_size` can be reported for tensors of millions of words whose counts
+    fit nothing: that row is incomplete, compress again with counts_in=None.
+    -> (comp [n, maxSize] u8, sizes [n] i32, temp bytes used), as compress_data."""
+    _check(len(ts_in) > 0)
+    _check(ts_in[0].is_cuda, "tensors must be on the GPU")
+    cast = dtype is not None
+    if cast:
+        _check(dtype in (torch.float16, torch.bfloat16), "dtype (of the archives) must be float16 or bfloat16")
+    else:
+        _check(ts_in[0].dtype in (torch.float16, torch.bfloat16), "tensors must be float16 or bfloat16 (float32: give dtype)")
+    ft = _DTYPE_TO_FT[dtype if cast else ts_in[0].dtype]
+    dev = ts_in[0].get_device()
+    for t in ts_in:
+        _check(t.is_cuda and t.is_contiguous() and t.get_device() == dev)
+        _check(t.dtype == (torch.float32 if cast else ts_in[0].dtype),
+               "the inputs of a cast call must be float32" if cast else "tensors must share one dtype")
+    rows = len(ts_in)
+    _validate_counts(counts_in, rows, dev, "counts_in")
+    _validate_counts(counts_out, rows, dev, "counts_out")
+    if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "compress_data_rolling"):
+        torch.ops.dietgpu_amd.set_precision(prob_bits)
+        try:
+            return torch.ops.dietgpu_amd.compress_data_rolling(ts_in, counts_in, counts_out, ft, cast, temp_mem, out_compressed,
+                                                               out_compressed_sizes)
+        finally:
+            torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+    _, mx = _total_and_max(ts_in)
+    cols = _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
+    with torch.cuda.device(dev):
+        comp, sizes = _validate_out(out_compressed, out_compressed_sizes, rows, cols, dev, ts_in[0].device)
+        tp, tb = _temp(temp_mem, dev)
+        row = comp.size(1)
+        out_ptrs = (C.c_void_p * rows)(*[comp.data_ptr() + i * row for i in range(rows)])
+        used = C.c_size_t(0)
+        check(lib().dgpu_float_rolling_compress(
+            tp, tb, C.byref(used), ft, int(cast), prob_bits, rows, _ptr_array(ts_in), _u32_array([t.numel() for t in ts_in]),
+            _ptr(counts_in), _ptr(counts_out), out_ptrs, _ptr(sizes), _stream()))
+    return comp, sizes, int(used.value)
+
+
 # ------------------------------------------------------------------ decompress
 def _validate_status(out_status, out_sizes, n, dev):
     if out_status is not None:

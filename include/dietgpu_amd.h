@@ -68,8 +68,8 @@ const char* dgpu_version(void);
  * with against the library it finds at run time, so that a stale build fails at load instead of inside a call.  An entry
  * point that is only ADDED leaves every existing one as it was and does not move the version: a library without the new
  * symbol fails at load too, by symbol resolution, in anything that links it (dgpu_float_decode_accumulate,
- * dgpu_float_cast_compress, dgpu_float_decode_reduce, dgpu_float_reduce_compress and
- * dgpu_float_reduce_compress_temp_bytes were added at version 8). */
+ * dgpu_float_cast_compress, dgpu_float_decode_reduce, dgpu_float_reduce_compress,
+ * dgpu_float_reduce_compress_temp_bytes and dgpu_float_rolling_compress were added at version 8). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -362,6 +362,54 @@ int dgpu_float_cast_compress(
     void* temp_dev, size_t tempBytes, size_t* tempUsed,
     uint32_t floatType /* of the ARCHIVE: DGPU_FLOAT16 or DGPU_BFLOAT16 */, int probBits,
     uint32_t numInBatch, const void* const* in /* float32 */, const uint32_t* inSize /* words */,
+    void* const* out, uint32_t* outSize_dev, void* stream);
+
+/* ---- rolling-table compress (no upstream equivalent) ------------------------------------
+ * (Named like its siblings dgpu_float_cast_compress and dgpu_float_reduce_compress: the call is a compress with a
+ * qualifier in front.)
+ * dgpu_float_compress / dgpu_float_cast_compress for tensors that come back step after step (gradient buckets, weight
+ * shards): the probability table of this call is made from the exponent counts of the LAST call, so no histogram pass
+ * reads the input, and the encoder counts the exponent bytes it codes, which leaves the counts for the NEXT call.
+ *   - countsIn_dev / countsOut_dev: device arrays [numInBatch][256] of uint32, 4-byte aligned, either may be NULL.
+ *     Both NULL: the call forwards to dgpu_float_compress(useChecksum = 0) / dgpu_float_cast_compress.
+ *   - countsOut_dev: after the call countsOut_dev[i][s] is the exact number of words of element i whose exponent byte
+ *     -- the byte the format entropy-codes: w >> 8 for float16, bits 14..7 for bfloat16, of the ROUNDED word when
+ *     sourceFloat32 -- is s.  A row sums to inSize[i]; an empty element's is 256 zeros.  The library zeroes the rows
+ *     itself (nothing is required of what the buffer held) and the encoder adds to them while it codes: the counting
+ *     form of the tiled encoder, persistent workgroups on tiles of 2, 4 or 8 blocks whatever
+ *     dgpu_debug_set_encoder_dispatch says; elements of a single block run on the 2-block tiles.
+ *   - countsIn_dev NULL: the histogram pass runs and the archive is byte for byte the plain call's.
+ *   - countsIn_dev given: no histogram kernel runs.  Element i is coded with the table the library's normalisation
+ *     yields for c'[s] = min(max(countsIn_dev[i][s], 1), inSize[i]) against a total of inSize[i].  Every symbol then
+ *     has a probability >= 1: no element can fail whatever the counts are (stale, of other data, garbage), and the
+ *     archive is an ordinary float archive of that table, which every decoder reads.  Only its SIZE depends on how well
+ *     the counts fit -- and it is never quite the plain call's: the symbols the data does not use keep a probability
+ *     of 2^-probBits each (measured at probBits 10 on N(0, 1) data: bfloat16 archives 4.8 % larger, float16 1.6 %).  (dgpu_ans_encode_* with histogram_dev keep failing data their histogram does not cover.)
+ *   - countsIn_dev == countsOut_dev, exactly, is allowed and is the intended use: one buffer, which after each call
+ *     holds that call's counts.  Any other overlap of the two is invalid.
+ *   - Size: with counts of other data an archive can exceed dgpu_float_max_compressed_size (worst case probBits bits
+ *     per symbol).  Nothing is stored beyond dgpu_float_max_compressed_size(floatType, inSize[i]) bytes of out[i], and
+ *     outSize_dev[i] reports the FULL size: a value above that maximum means the archive is incomplete, and the caller
+ *     compresses that call again with countsIn_dev = NULL.  The maximum allows 5120 bytes per 4096-word block plus the
+ *     header of a 4096-block archive; a table that covers nothing costs about 623 bytes per block more at probBits 11,
+ *     so this can happen from about 894 blocks (3.66 M words) at probBits 11 and from about 4900 blocks at probBits
+ *     10, never below; tables of data whose distribution merely drifted are nowhere near it.
+ *   - floatType is the type of the ARCHIVE, DGPU_FLOAT16 or DGPU_BFLOAT16 (float32 archives are out of scope: the
+ *     float32 encoder has no counting form); sourceFloat32 0: in[i] holds floatType words, 2-byte aligned; 1: float32
+ *     words, 4-byte aligned, rounded as by dgpu_float_cast_compress.  probBits 9 / 10 / 11, numInBatch <= 65535,
+ *     out[i] 16-byte aligned, inSize[i] within the size guard of dgpu_float_compress: DGPU_ERR_INVALID_ARGUMENT
+ *     otherwise, with a dgpu_last_error() text, before anything is enqueued.  An empty batch returns 0, *tempUsed = 0.
+ *   - Temp memory: at most dgpu_float_compress_temp_bytes(floatType, numInBatch, max inSize).  Nothing synchronises;
+ *     the call can be captured into a HIP graph after one identical warm call.  Stride detection, parameter cache and
+ *     work lists are the plain call's; with countsIn_dev the batch is not split into size classes (as with a caller's
+ *     histogram). */
+int dgpu_float_rolling_compress(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed,
+    uint32_t floatType /* of the ARCHIVE: DGPU_FLOAT16 or DGPU_BFLOAT16 */,
+    uint32_t sourceFloat32 /* 0: in[i] holds floatType words; 1: float32 words */,
+    int probBits, uint32_t numInBatch, const void* const* in, const uint32_t* inSize /* words */,
+    const uint32_t* countsIn_dev /* [numInBatch][256], nullable */,
+    uint32_t* countsOut_dev /* [numInBatch][256], nullable */,
     void* const* out, uint32_t* outSize_dev, void* stream);
 
 /* ---- reduce-compress (no upstream equivalent) ------------------------------------------
