@@ -20,6 +20,8 @@ from .ops import (  # noqa: F401
     decompress_data_range,
     decompress_data_reduce,
     decompress_data_reduce_compress,
+    decompress_data_reduce_compress_mixed,
+    decompress_data_reduce_mixed,
     decompress_data_simple,
     decompress_data_slice,
     decompress_data_split_size,

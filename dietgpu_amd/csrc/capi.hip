@@ -1501,26 +1501,63 @@ int decodeAccumulateImpl(
   return launchDecode(d, groups[0], dev.work, DecodeForm::kAccum, P, stream);
 }
 
+// The sources of a mixed call (dgpu_float_decode_reduce_mixed, dgpu_float_reduce_compress_mixed): kinds[k] == 0, an
+// archive, 16-byte aligned like every compressed input; 1, a raw row of inBytes[k] / wordBytes words of the float type,
+// word-aligned like a compress input.  A raw row's address enters the parameter block with kReduceRawTag set, which is
+// how the kernel tells the two apart (kernels_decode.h) and why a call that differs from a warm one in its kinds alone
+// hashes to another block.  *anyRaw: false = the batch, and its block, are those of the plain call.
+int mixedSourceAddresses(const char* nullMsg, const void* const* in, const uint32_t* inBytes, const uint8_t* kinds, uint32_t n, uint32_t wordBytes,
+                         std::vector<uint64_t>* addr, bool* anyRaw) {
+  DGPU_REQUIRE(kinds, nullMsg);
+  addr->resize(n);
+  *anyRaw = false;
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint64_t at = (uint64_t)(uintptr_t)in[k];
+    DGPU_REQUIRE(kinds[k] <= 1u, "sourceKind must be 0 (archive) or 1 (raw row)");
+    if (kinds[k] == 0u) {
+      DGPU_REQUIRE(at % 16u == 0u, kMsgCompIn);
+      (*addr)[k] = at;
+    } else {
+      DGPU_REQUIRE(at % wordBytes == 0u, "raw source must be float-word aligned");
+      DGPU_REQUIRE(inBytes[k] % wordBytes == 0u, "inBytes of a raw source must be a multiple of the float word size");
+      (*addr)[k] = at | kReduceRawTag;
+      *anyRaw = true;
+    }
+  }
+  return DGPU_OK;
+}
+
 // Decode-reduce (k_ans_decode_reduce): S = numSources archives per float32 accumulator, summed left to right in one
 // launch, all or nothing per member.  The batch carries B * S archive pointers and inBytes (member-major) beside B
 // accumulators and capacities; the parameter block holds every one of them, so its hash -- the parameter-cache key --
 // covers each source pointer and size, and S through the block's length and layout.  The launch plan is that of a
 // decode-accumulate call with the same capacities.  No temp memory, no host synchronisation.
+// mixed (dgpu_float_decode_reduce_mixed): `kinds` says which sources are raw rows (mixedSourceAddresses); with one
+// among them the launch is k_ans_decode_reduce_mixed, for S == 1 too; with none the call is the plain one from here on.
 int decodeReduceImpl(
     size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, uint32_t S, const void* const* in, const uint32_t* inBytes,
-    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream, bool mixed = false,
+    const uint8_t* kinds = nullptr) {
   DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
   DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "decode-reduce: accumulate must be 0 or 1");
   DGPU_REQUIRE(S >= 1u && S <= kMaxReduceSources, "decode-reduce: numSources must be between 1 and 64");
   DGPU_REQUIRE((uint64_t)B * S <= 65535u, "decode-reduce: numInBatch * numSources must be <= 65535");
-  if (S == 1u) return decodeAccumulateImpl(tempUsed, ft, P, accumulate, B, in, inBytes, out, outCapacity, outSuccess_dev, outSize_dev, stream);
+  if (S == 1u && !mixed) return decodeAccumulateImpl(tempUsed, ft, P, accumulate, B, in, inBytes, out, outCapacity, outSuccess_dev, outSize_dev, stream);
   bool done;
   int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
   if (done) return rc;
   DGPU_REQUIRE(in && inBytes && out && outCapacity, "decode-reduce: null array with numInBatch > 0");
   Batch b;
+  bool anyRaw = false;
   // (pointerBatch, with S inputs per output)
-  rc = sideAddresses(ptrSide(in, 16, kMsgCompIn), B * S, &b.inPtrs);
+  if (mixed) {
+    rc = mixedSourceAddresses("decode-reduce: sourceKind is null with numInBatch > 0", in, inBytes, kinds, B * S, floatWordBytes(ft), &b.inPtrs, &anyRaw);
+    if (!rc && !anyRaw && S == 1u) {
+      return decodeAccumulateImpl(tempUsed, ft, P, accumulate, B, in, inBytes, out, outCapacity, outSuccess_dev, outSize_dev, stream);
+    }
+  } else {
+    rc = sideAddresses(ptrSide(in, 16, kMsgCompIn), B * S, &b.inPtrs);
+  }
   if (!rc) rc = sideAddresses(ptrSide(out, 4, "decode-reduce: accumulators must be 4-byte aligned"), B, &b.outPtrs);
   if (rc) return rc;
   b.n = B;
@@ -1537,7 +1574,7 @@ int decodeReduceImpl(
   DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
   d.accumulate = (uint32_t)accumulate;
   d.numSources = S;
-  return launchDecode(d, groups[0], dev.work, DecodeForm::kReduce, P, stream);
+  return launchDecode(d, groups[0], dev.work, anyRaw ? DecodeForm::kReduceMixed : DecodeForm::kReduce, P, stream);
 }
 
 // Reduce-compress: decode-reduce into the accumulators, then cast-compress of the accumulators, without the cast
@@ -1547,10 +1584,12 @@ int decodeReduceImpl(
 // histogram counters (held under the stream lease; k_normalize reads them and puts them back to zero), otherwise a
 // region of temp memory cleared by one memset on the stream.  A member that fails the reduce has no counts: its table is
 // the flat one, which codes any data.  Everything is validated before the first enqueue; nothing synchronises.
+// mixed (dgpu_float_reduce_compress_mixed): as in decodeReduceImpl; the reduce kernel is k_ans_decode_reduce_mixed_stats.
 int reduceCompressImpl(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, uint32_t S,
     const void* const* in, const uint32_t* inBytes, void* const* acc, const uint32_t* outCapacity, void* const* outArchive,
-    uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream) {
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream, bool mixed = false,
+    const uint8_t* kinds = nullptr) {
   DGPU_REQUIRE(ft == kFloat16 || ft == kBFloat16, "reduce-compress: floatType must be float16 or bfloat16 (float32: decode-reduce, then dgpu_float_compress)");
   DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "reduce-compress: accumulate must be 0 or 1");
   DGPU_REQUIRE(S >= 1u && S <= kMaxReduceSources, "reduce-compress: numSources must be between 1 and 64");
@@ -1561,7 +1600,12 @@ int reduceCompressImpl(
   DGPU_REQUIRE(in && inBytes && acc && outCapacity && outArchive, "reduce-compress: null array with numInBatch > 0");
   // the reduce side: B * S archives into B accumulators (decodeReduceImpl); the compress side: the accumulators into B archives
   Batch bd, be;
-  rc = sideAddresses(ptrSide(in, 16, kMsgCompIn), B * S, &bd.inPtrs);
+  bool anyRaw = false;
+  if (mixed) {
+    rc = mixedSourceAddresses("reduce-compress: sourceKind is null with numInBatch > 0", in, inBytes, kinds, B * S, floatWordBytes(ft), &bd.inPtrs, &anyRaw);
+  } else {
+    rc = sideAddresses(ptrSide(in, 16, kMsgCompIn), B * S, &bd.inPtrs);
+  }
   if (!rc) rc = sideAddresses(ptrSide(acc, 4, "reduce-compress: accumulators must be 4-byte aligned"), B, &bd.outPtrs);
   if (!rc) rc = pointerBatch(&be, B, ptrSide(acc, 4, "reduce-compress: accumulators must be 4-byte aligned"), ptrSide(outArchive, 16, kMsgCompOut), outCapacity);
   if (rc) return rc;
@@ -1599,7 +1643,7 @@ int reduceCompressImpl(
   d.accumulate = (uint32_t)accumulate;
   d.numSources = S;
   d.stats = counts;
-  rc = launchDecode(d, groupsD[0], devD.work, DecodeForm::kReduceStats, P, stream);
+  rc = launchDecode(d, groupsD[0], devD.work, anyRaw ? DecodeForm::kReduceMixedStats : DecodeForm::kReduceStats, P, stream);
   if (!rc) {
     EncodeShared shared;
     rc = encodeCommon(arena, streamLease, stream, P, false, B, devE.in, devE.out, castType, groupsE[0], devE.work, shared,
@@ -1932,6 +1976,26 @@ int dgpu_float_reduce_compress(
     uint32_t* outArchiveSize_dev, void* stream) {
   return reduceCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, acc,
                             outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream);
+}
+
+// ---- mixed sources: archives and raw rows of floatType words (no upstream equivalent) ----------------
+int dgpu_float_decode_reduce_mixed(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, const uint8_t* sourceKind,
+    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream) {
+  (void)temp_dev;
+  (void)tempBytes;
+  return decodeReduceImpl(tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, out, outCapacity,
+                          outSuccess_dev, outSize_dev, (hipStream_t)stream, true, sourceKind);
+}
+
+int dgpu_float_reduce_compress_mixed(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, const uint8_t* sourceKind,
+    void* const* acc, const uint32_t* outCapacity, void* const* outArchive, uint8_t* outSuccess_dev, uint32_t* outSize_dev,
+    uint32_t* outArchiveSize_dev, void* stream) {
+  return reduceCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, acc,
+                            outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream, true, sourceKind);
 }
 
 // ---- float stride batches with capacities on both sides (the compressed collectives) --------------------

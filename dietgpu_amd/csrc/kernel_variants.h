@@ -166,7 +166,9 @@ inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, boo
 //   * DecodeForm::kReduce: k_ans_decode_reduce, the same with DecodeArgs::numSources archives per accumulator;
 //   * DecodeForm::kReduceStats: k_ans_decode_reduce_stats, which also counts the exponent bytes of the rounded sums
 //     (DecodeArgs::stats); float16 and bfloat16 only (anything else: the bfloat16 form), 16- and 4-block tiles, with
-//     the LDS of the bins behind that of the plain form.
+//     the LDS of the bins behind that of the plain form;
+//   * DecodeForm::kReduceMixed / kReduceMixedStats: k_ans_decode_reduce_mixed / k_ans_decode_reduce_mixed_stats, the two
+//     above with sources that are archives or raw rows (DecodeArgs::sourceKind); the same types, tiles and LDS.
 inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, DecodeForm form = DecodeForm::kWhole) {
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> DecodeVariant {
     constexpr int kP = decltype(p)::value;
@@ -192,6 +194,23 @@ inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, Dec
         constexpr uint32_t kTB = decltype(tb)::value;
         constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
         return {k_ans_decode_reduce_stats<kP, kCastFT, kTB>, decThreads(kTB), decReduceStatsLdsBytes(kP, kCastFT, kTB), "k_ans_decode_reduce_stats"};
+      };
+      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
+    }
+    if (form == DecodeForm::kReduceMixed) {
+      auto tiled = [](auto tb) -> DecodeVariant {
+        constexpr uint32_t kTB = decltype(tb)::value;
+        constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
+        return {k_ans_decode_reduce_mixed<kP, kAccFT, kTB>, decThreads(kTB), decLdsBytes(kP, kAccFT, kTB), "k_ans_decode_reduce_mixed"};
+      };
+      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
+    }
+    if (form == DecodeForm::kReduceMixedStats) {
+      auto tiled = [](auto tb) -> DecodeVariant {
+        constexpr uint32_t kTB = decltype(tb)::value;
+        constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
+        return {k_ans_decode_reduce_mixed_stats<kP, kCastFT, kTB>, decThreads(kTB), decReduceStatsLdsBytes(kP, kCastFT, kTB),
+                "k_ans_decode_reduce_mixed_stats"};
       };
       return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
     }

@@ -348,6 +348,7 @@ template <uint32_t FT, uint32_t kSlots = 0>
 struct AccumSink : AccumBins<kSlots != 0u> {  // kFloat16 / kBFloat16
   static_assert(FT == kFloat16 || FT == kBFloat16, "");
   static constexpr bool kStats = kSlots != 0u;
+  static constexpr uint32_t kStatSlots = kSlots;
   float* out;
   const uint8_t* nc;
   uint32_t accumulate;
@@ -364,37 +365,63 @@ struct AccumSink : AccumBins<kSlots != 0u> {  // kFloat16 / kBFloat16
   }
   typedef AccumPre Pre;
   typedef AccumGroupPre GroupPre;
+  // (prefetchAcc / storeWord, prefetchGroupAcc / flushWords: the halves of prefetch / store and prefetchGroup /
+  // flushGroup that do not touch the archive -- a raw source of the mixed reduce hands its words in here)
+  __device__ __forceinline__ AccumPre prefetchAcc(uint32_t row) const {
+    AccumPre p(0);
+    if (accumulate) p.acc = *(const uint32_t*)&out[row * 32u];
+    return p;
+  }
+  // (its own text: forwarding to prefetchAcc puts the accumulator's load in front of the byte's and reschedules the row loops)
   __device__ __forceinline__ AccumPre prefetch(uint32_t row) const {
     AccumPre p(0);
     p.r = nc[row * 32u];
     if (accumulate) p.acc = *(const uint32_t*)&out[row * 32u];
     return p;
   }
-  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, const AccumPre& p) const {
-    const float v = accWiden16<FT>(RowSink<FT>::joinWord(e0, p.r) >> 16);
+  // h: the 16-bit word of FT in the LOW half
+  __device__ __forceinline__ void storeWord(uint32_t row, uint32_t h, const AccumPre& p) const {
+    const float v = accWiden16<FT>(h);
     const uint32_t o = accumulate ? accAdd(p.acc, v) : __builtin_bit_cast(uint32_t, v);
     streamStore<kNtDecStores>((uint32_t*)&out[row * 32u], o);
     if constexpr (kStats) {
       if (this->bins) count(o);
     }
   }
+  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, const AccumPre& p) const {
+    storeWord(row, RowSink<FT>::joinWord(e0, p.r) >> 16, p);
+  }
   static constexpr uint32_t kXposeBytes = 512;
-  __device__ __forceinline__ AccumGroupPre prefetchGroup(uint32_t g, uint32_t hl) const {
-    AccumGroupPre p;
-    p.nc = decLoad8(nc - hl + g * 256u + hl * 8u);
+  __device__ __forceinline__ void prefetchGroupAcc(uint32_t g, uint32_t hl, AccumGroupPre& p) const {
     p.a0 = p.a1 = u32x4w{0u, 0u, 0u, 0u};
     if (accumulate) {
       const u32x4w4* src = (const u32x4w4*)(out - hl + g * 256u + hl * 8u);
       p.a0 = src[0];
       p.a1 = src[1];
     }
+  }
+  __device__ __forceinline__ AccumGroupPre prefetchGroup(uint32_t g, uint32_t hl) const {
+    AccumGroupPre p;
+    p.nc = decLoad8(nc - hl + g * 256u + hl * 8u);
+    prefetchGroupAcc(g, hl, p);
     return p;
   }
   __device__ __forceinline__ void stageRow(uint32_t xpose, uint32_t j, uint32_t hl, uint32_t e0) const {
     *(LdsU16w*)(uintptr_t)(xpose + (j * 32u + hl) * 2u) = (uint16_t)(e0 >> 16);
   }
   __device__ __forceinline__ void flushGroup(uint32_t xpose, uint32_t g, uint32_t hl, const AccumGroupPre& p) const {
-    const u32x4w w = RowSink<FT>::joinGroup(xpose, hl, p.nc);
+    flushFrom<false>(xpose, g, hl, p, u32x4w{0u, 0u, 0u, 0u});
+  }
+  // given: the lane's 8 consecutive words of group g, two per dword (joinGroup's layout)
+  __device__ __forceinline__ void flushWords(uint32_t g, uint32_t hl, const u32x4w& given, const AccumGroupPre& p) const {
+    flushFrom<true>(0u, g, hl, p, given);
+  }
+  // (one body, the origin of the words a compile-time choice: the decoders' instantiation is flushGroup's text as it was)
+  template <bool kGiven>
+  __device__ __forceinline__ void flushFrom(uint32_t xpose, uint32_t g, uint32_t hl, const AccumGroupPre& p, const u32x4w& given) const {
+    u32x4w w;
+    if constexpr (kGiven) w = given;
+    else w = RowSink<FT>::joinGroup(xpose, hl, p.nc);
     float v[8];
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
@@ -430,6 +457,7 @@ struct AccumSink : AccumBins<kSlots != 0u> {  // kFloat16 / kBFloat16
 template <uint32_t kSlots>
 struct AccumSink<kFloat32, kSlots> {  // row-wise, as RowSink<kFloat32>: 128-byte pieces already
   static_assert(kSlots == 0u, "counting sinks: the 16-bit archive types only");
+  static constexpr bool kStats = false;
   float* out;
   const uint16_t* nc2;
   const uint8_t* nc1;
@@ -447,10 +475,17 @@ struct AccumSink<kFloat32, kSlots> {  // row-wise, as RowSink<kFloat32>: 128-byt
     if (accumulate) p.acc = *(const uint32_t*)&out[row * 32u];
     return p;
   }
-  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, const AccumPre& p) const {
-    const uint32_t w = RowSink<kFloat32>::joinWord(e0, p.r);
+  __device__ __forceinline__ AccumPre prefetchAcc(uint32_t row) const {
+    AccumPre p(0);
+    if (accumulate) p.acc = *(const uint32_t*)&out[row * 32u];
+    return p;
+  }
+  __device__ __forceinline__ void storeWord(uint32_t row, uint32_t w, const AccumPre& p) const {
     const uint32_t o = accumulate ? accAdd(p.acc, __builtin_bit_cast(float, w)) : w;
     streamStore<kNtDecStores>((uint32_t*)&out[row * 32u], o);
+  }
+  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, const AccumPre& p) const {
+    storeWord(row, RowSink<kFloat32>::joinWord(e0, p.r), p);
   }
   static constexpr uint32_t kXposeBytes = 0;
   __device__ __forceinline__ uint2 prefetchGroup(uint32_t, uint32_t) const { return make_uint2(0, 0); }
@@ -793,11 +828,11 @@ __device__ __forceinline__ void decodeBlock(
 // descriptors (8 bytes per block, from the L2, in the round trip of the tile's own descriptor), and no tile of an element
 // with a malformed descriptor stores -- a failing element leaves its accumulator as it was.
 // (kReduce: decodeReduceTile, below)
-enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats };
+enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats };
 template <int P, uint32_t FT, uint32_t kTileBlocks, DecodeForm kForm>
 __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccum = kForm == DecodeForm::kAccum;
-  static_assert(kForm != DecodeForm::kReduce && kForm != DecodeForm::kReduceStats, "decode-reduce has a body of its own: decodeReduceTile");
+  static_assert(kForm == DecodeForm::kWhole || kForm == DecodeForm::kRanged || kForm == DecodeForm::kAccum, "decode-reduce has a body of its own: decodeReduceTile");
   static_assert(!kAccum || FT != 0u, "accumulating decode: float archives only");
   using Sink = std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32>, RowSink<FT>>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks);
@@ -1209,6 +1244,127 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
 // (the encoder codes `capacity` words of the accumulator); a member that fails any check returns before the source loop
 // and so adds nothing.  The last source is selected at run time (a wave-uniform test around the counting), the form at
 // compile time: the plain kernel's code does not change.
+//
+// kMixed (k_ans_decode_reduce_mixed, k_ans_decode_reduce_mixed_stats): a source is an archive or a RAW row of
+// inBytes / wordBytes words of FT, added in its place in source order.  The kind travels in the source's address in the
+// parameter block: a raw row's has bit 0 set (kReduceRawTag; the host checks that rows are word-aligned and archives
+// 16-byte aligned, so the bit is free) -- the address is loaded anyway, where a separate array of kinds is two more
+// live scalars, one more than the counting bf16 form has (it then keeps one in a VGPR lane: 129 VGPRs).  A raw row's
+// verdict needs no header: the count it states is its total and what it reports, and must fit the capacity (kStats:
+// equal it) like a header's; it has no block descriptors and no pdf.  In the source loop it takes its turn before
+// anything of the archive path is set up (reduceRawSource: in one block with that path its values stretch the live
+// ranges across decodeBlock, 167 VGPRs): the same hand-over barrier, the same sink, and instead of LUT build and
+// decodeBlock every half-wave streams its own block's words into the sink (reduceRawBlock) -- in the sink's own
+// lane-to-word mapping, so a lane touches the accumulator words it touches for an archive source, and the hand-over
+// holds in both directions.  No LDS is used, so nothing of it races with the builds of the sources around it.  Kind
+// and base alignment are uniform per source; the form is a template flag: the plain and counting kernels do not change.
+constexpr uintptr_t kReduceRawTag = 1u;
+__device__ __forceinline__ bool reduceIsRaw(const uint8_t* source) { return ((uintptr_t)source & kReduceRawTag) != 0u; }
+typedef uint16_t u16n __attribute__((aligned(2)));
+__device__ __forceinline__ uint32_t rawLoad16(const uint8_t* p) {
+  return kNtEncLoads ? (uint32_t)__builtin_nontemporal_load((const u16n*)p) : (uint32_t)*(const u16n*)p;
+}
+__device__ __forceinline__ uint32_t rawLoad32(const uint8_t* p) {
+  return kNtEncLoads ? __builtin_nontemporal_load((const uint32_t*)p) : *(const uint32_t*)p;
+}
+// a lane's 8 consecutive 16-bit words, two per dword: one 16-byte load, four 4-byte loads or eight 2-byte loads,
+// whichever the row's base allows (align: 16, 4 or 2; block and group offsets are multiples of 16 bytes)
+__device__ __forceinline__ u32x4w rawLoadGroup(const uint8_t* p, uint32_t align) {
+  u32x4w w;
+  if (align >= 16u) {
+    w = kNtEncLoads ? __builtin_nontemporal_load((const u32x4w*)p) : *(const u32x4w*)p;
+  } else if (align >= 4u) {
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) w[k] = rawLoad32(p + 4u * k);
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) w[k] = rawLoad16(p + 4u * k) | (rawLoad16(p + 4u * k + 2u) << 16);
+  }
+  return w;
+}
+// This half's block of a raw source: n words of FT at src (0: the half has no block).  16-bit types: the whole 8-row
+// groups in the wide layout (flushWords), four groups' loads in flight; what is left row by row (storeWord), as the
+// tail path of decodeBlock leaves it.  float32: row by row, eight rows' loads in flight.
+template <uint32_t FT, typename Sink>
+__device__ __forceinline__ void reduceRawBlock(const Sink& sink, const uint8_t* src, uint32_t n, uint32_t hl, uint32_t align) {
+  if constexpr (FT == kFloat32) {
+    const uint32_t rows = n / 32u;
+    uint32_t row = 0;
+    for (; row + 8u <= rows; row += 8u) {
+      typename Sink::Pre p[8];
+      uint32_t w[8];
+#pragma unroll
+      for (uint32_t j = 0; j < 8u; ++j) {
+        p[j] = sink.prefetchAcc(row + j);
+        w[j] = rawLoad32(src + ((size_t)(row + j) * 32u + hl) * 4u);
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < 8u; ++j) sink.storeWord(row + j, w[j], p[j]);
+    }
+    for (; row * 32u + hl < n; ++row) {
+      const typename Sink::Pre p = sink.prefetchAcc(row);
+      sink.storeWord(row, rawLoad32(src + ((size_t)row * 32u + hl) * 4u), p);
+    }
+  } else {
+    const uint32_t groups = n / (kGroupRows * 32u);
+    uint32_t g = 0;
+    for (; g + 4u <= groups; g += 4u) {
+      typename Sink::GroupPre p[4];
+      u32x4w w[4];
+#pragma unroll
+      for (uint32_t j = 0; j < 4u; ++j) {
+        sink.prefetchGroupAcc(g + j, hl, p[j]);
+        w[j] = rawLoadGroup(src + (g + j) * 512u + hl * 16u, align);
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < 4u; ++j) sink.flushWords(g + j, hl, w[j], p[j]);
+    }
+    for (; g < groups; ++g) {
+      typename Sink::GroupPre p;
+      sink.prefetchGroupAcc(g, hl, p);
+      sink.flushWords(g, hl, rawLoadGroup(src + g * 512u + hl * 16u, align), p);
+    }
+    for (uint32_t row = groups * kGroupRows; row * 32u + hl < n; ++row) {
+      const typename Sink::Pre p = sink.prefetchAcc(row);
+      sink.storeWord(row, rawLoad16(src + (row * 32u + hl) * 2u), p);
+    }
+  }
+}
+
+// Between two sources of decodeReduceTile: source s - 1 is in the accumulator before source s asks for it (see there)
+__device__ __forceinline__ void reduceHandOver() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// What a source's sink is told, for an archive and for a raw row alike: store or add, and (counting form) whether the
+// sums are counted -- on the LAST source
+__device__ __forceinline__ uint32_t reduceAccumulates(const DecodeArgs& a, uint32_t s) { return (s != 0u || a.accumulate != 0u) ? 1u : 0u; }
+__device__ __forceinline__ bool reduceCounts(uint32_t s, uint32_t S) { return s + 1u == S; }
+
+// A raw source's turn in the source loop of decodeReduceTile: the hand-over barrier of an archive source, the sink set up
+// as for one, and every half-wave's block through reduceRawBlock.  (Its lane indices are laundered like the loop's own.)
+template <uint32_t FT, typename Sink>
+__device__ __forceinline__ void reduceRawSource(const DecodeArgs& a, uint32_t b, const uint8_t* row, uint32_t s, uint32_t total, uint32_t tileFirst,
+                                                uint32_t nb, uint32_t wave, uint32_t binsLds) {
+  uint32_t tidS = threadIdx.x;
+  asm volatile("" : "+v"(tidS));
+  const uint32_t laneS = tidS & 63u;
+  const uint32_t hl = laneS & 31u;
+  const uint32_t block = tileFirst + wave * 2u + (laneS >= 32u ? 1u : 0u);
+  const bool haveBlock = block < nb;
+  if (s != 0u) reduceHandOver();
+  Sink sink;
+  sink.accumulate = reduceAccumulates(a, s);
+  if constexpr (Sink::kStats) sink.bins = reduceCounts(s, a.numSources) ? binsLds + (laneS & (Sink::kStatSlots - 1u)) * 4u : 0u;
+  sink.init(a.out.ptr(b), row, total, (size_t)(haveBlock ? block : 0u) * kBlockSize, hl);
+  const uint32_t left = haveBlock ? total - block * kBlockSize : 0u;
+  const uint32_t align = ((uintptr_t)row & 15u) == 0u ? 16u : (((uintptr_t)row & 3u) == 0u ? 4u : 2u);
+  reduceRawBlock<FT>(sink, row + (size_t)block * kBlockSize * decOutWordBytes(FT), left < kBlockSize ? left : kBlockSize, hl, align);
+}
+
 struct ReduceSource {  // verdict on one source (LDS)
   uint32_t ok;          // headers and pdf sum
   uint32_t total;       // words the ANS header states (ok)
@@ -1217,7 +1373,7 @@ struct ReduceSource {  // verdict on one source (LDS)
 };
 constexpr uint32_t kMaxReduceSources = 64;
 
-template <int P, uint32_t FT, uint32_t kTileBlocks, bool kStats = false>
+template <int P, uint32_t FT, uint32_t kTileBlocks, bool kStats = false, bool kMixed = false>
 __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
   static_assert(FT != 0u, "decode-reduce: float archives only");
   constexpr uint32_t kSlots = kStats ? decStatsSlots(kTileBlocks) : 0u;
@@ -1253,7 +1409,13 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
     const uint8_t* archive = a.in.ptr(first + s);
     const uint64_t inBytes = a.inBytes[first + s];
     ReduceSource r = {0u, 0u, 0u, 0u};
-    if (inBytes >= sizeof(FloatHeader)) {
+    bool raw = false;
+    if constexpr (kMixed) raw = reduceIsRaw(archive);
+    if (raw) {  // the row states its count as a header would
+      const uint32_t words = (uint32_t)(inBytes / decOutWordBytes(FT));
+      r.ok = (kStats ? words == capacity : words <= capacity) ? 1u : 0u;
+      r.total = r.report = words;
+    } else if (inBytes >= sizeof(FloatHeader)) {
       const FloatHeader fh = *(const FloatHeader*)archive;
       r.report = fh.size;
       const bool fhOk = fh.magicAndVersion == ((kFloatMagic << 16) | kFloatVersion) && (fh.options & 0xfu) == FT && fh.size <= capacity &&
@@ -1301,6 +1463,9 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
     bool allBlocksOk = true;
     for (uint32_t i = tid; i < S * nb; i += kDecThreads) {
       const uint32_t s = i / nb, blk = i - s * nb;
+      if constexpr (kMixed) {
+        if (reduceIsRaw(a.in.ptr(first + s))) continue;  // a raw row has no descriptors
+      }
       const uint2 bw = ((const uint2*)(a.in.ptr(first + s) + ansOff + ansBlockWordsOffset(nb)))[blk];
       const uint32_t want = (blk + 1u < nb) ? kBlockSize : total - blk * kBlockSize;
       const bool ok = (bw.x >> 16) == want && (bw.y & (kBlockAlignWords - 1u)) == 0u &&
@@ -1333,6 +1498,13 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
     // out of the loop, these addresses and offsets stay in registers across decodeBlock (151 VGPRs: one wave per SIMD,
     // i.e. one of two workgroups per CU, fewer than k_ans_decode_accum; recomputed per source they cost a few dozen VALU
     // per source).  tests/test_reduce_kernel_resources.py holds the 16-bit forms to the 128 VGPRs of four waves per SIMD.
+    if constexpr (kMixed) {
+      const uint8_t* src = a.in.ptr(first + s);
+      if (reduceIsRaw(src)) {  // uniform.  A raw row: no LUT, no ring, no row loop
+        reduceRawSource<FT, Sink>(a, b, src - kReduceRawTag, s, total, tileFirst, nb, wave, ldsBase + kBinsAt);
+        continue;
+      }
+    }
     uint32_t tidS = threadIdx.x;
     asm volatile("" : "+v"(tidS));
     const uint32_t laneS = tidS & 63u;
@@ -1354,18 +1526,12 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
       bwMine = ((const uint2*)(ans + ansBlockWordsOffset(nb)))[block];
       state = ((const uint32_t*)(ans + ansStatesOffset()))[block * 32u + hl];
     }
-    if (s != 0u) {
-      // source s - 1 is in the accumulator before source s asks for it; the barrier also frees LUT and rings
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
+    if (s != 0u) reduceHandOver();  // (the barrier also frees LUT and rings)
     const uint32_t n = bwMine.x >> 16, numWords = bwMine.x & 0xffffu;
     const uint8_t* gwords = ans + ansOverhead(nb) + 2u * (size_t)bwMine.y;
     Sink sink;
-    sink.accumulate = (s != 0u || a.accumulate != 0u) ? 1u : 0u;
-    if constexpr (kStats) sink.bins = s + 1u == S ? ldsBase + kBinsAt + (laneS & (kSlots - 1u)) * 4u : 0u;
+    sink.accumulate = reduceAccumulates(a, s);
+    if constexpr (kStats) sink.bins = reduceCounts(s, S) ? ldsBase + kBinsAt + (laneS & (kSlots - 1u)) * 4u : 0u;
     sink.init(a.out.ptr(b), archive, total, (size_t)sinkBlock * kBlockSize, hl);
     // uniform per wave (the staging mode is this source's own; full / tail follow the word count, the same for all)
     const uint32_t nFirst = __shfl(n, 0, 64);
@@ -1496,6 +1662,18 @@ template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce_stats(DecodeArgs a) {
   static_assert(FT == kFloat16 || FT == kBFloat16, "the archive types of a cast");
   decodeReduceTile<P, FT, kTileBlocks, true>(a);
+}
+
+// Mixed forms: k_ans_decode_reduce and k_ans_decode_reduce_stats whose sources are archives or raw rows of FT words
+// (DecodeArgs::sourceKind; decodeReduceTile, kMixed).  Built for the types and tile sizes of their plain siblings.
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce_mixed(DecodeArgs a) {
+  decodeReduceTile<P, FT, kTileBlocks, false, true>(a);
+}
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce_mixed_stats(DecodeArgs a) {
+  static_assert(FT == kFloat16 || FT == kBFloat16, "the archive types of a cast");
+  decodeReduceTile<P, FT, kTileBlocks, true, true>(a);
 }
 
 }  // namespace dgpu

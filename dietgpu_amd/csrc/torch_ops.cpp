@@ -690,6 +690,105 @@ std::tuple<at::Tensor, at::Tensor, int64_t> decompress_data_reduce_compress(
   return {std::move(comp), std::move(sizes), (int64_t)used};
 }
 
+// The sources of the mixed ops: a uint8 tensor is an archive; a tensor of the dtype float_type names is a RAW row
+// (1-D, contiguous, on the device); anything else is an error.  Accumulators as in decompress_data_reduce.
+namespace {
+struct MixedTensors {
+  std::vector<const void*> inPtrs;
+  std::vector<uint32_t> inBytes;
+  std::vector<uint8_t> kinds;
+  std::vector<void*> accPtrs;
+  std::vector<uint32_t> capacity;
+  int64_t maxWords = 0;
+};
+MixedTensors marshalMixed(const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tAccs, int64_t floatType, int dev) {
+  const at::ScalarType rawType = floatType == (int64_t)DGPU_FLOAT16 ? at::ScalarType::Half
+      : (floatType == (int64_t)DGPU_BFLOAT16 ? at::ScalarType::BFloat16 : at::ScalarType::Float);
+  const size_t n = tAccs.size();
+  MixedTensors m;
+  m.inPtrs.resize(tIns.size());
+  m.inBytes.resize(tIns.size());
+  m.kinds.resize(tIns.size());
+  m.accPtrs.resize(n);
+  m.capacity.resize(n);
+  for (size_t k = 0; k < tIns.size(); ++k) {
+    auto& t = tIns[k];
+    TORCH_CHECK(t.device().is_cuda() && t.get_device() == dev && t.is_contiguous(), "dietgpu: sources must be contiguous tensors on one GPU");
+    const bool raw = t.scalar_type() != at::ScalarType::Byte;
+    TORCH_CHECK(!raw || t.scalar_type() == rawType, "dietgpu: a source is a uint8 archive or a raw row of the dtype float_type names");
+    TORCH_CHECK(!raw || t.dim() == 1, "dietgpu: a raw source must be 1-D");
+    const int64_t bytes = t.numel() * (int64_t)t.element_size();
+    TORCH_CHECK(!raw || bytes <= (int64_t)std::numeric_limits<uint32_t>::max(), "dietgpu: raw source too large");
+    m.inPtrs[k] = t.data_ptr();
+    m.inBytes[k] = (uint32_t)std::min<int64_t>(bytes, std::numeric_limits<uint32_t>::max());
+    m.kinds[k] = raw ? 1 : 0;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    auto& t = tAccs[i];
+    TORCH_CHECK(t.device().is_cuda() && t.get_device() == dev && t.is_contiguous(), "dietgpu: accumulators must be contiguous tensors on the GPU");
+    TORCH_CHECK(t.scalar_type() == at::ScalarType::Float, "dietgpu: accumulators must be float32");
+    TORCH_CHECK((uint64_t)t.numel() <= std::numeric_limits<uint32_t>::max());
+    m.accPtrs[i] = t.data_ptr();
+    m.capacity[i] = (uint32_t)t.numel();
+    m.maxWords = std::max<int64_t>(m.maxWords, t.numel());
+  }
+  return m;
+}
+}  // namespace
+
+// decompress_data_reduce with sources that are archives or raw rows (dgpu_float_decode_reduce_mixed).
+int64_t decompress_data_reduce_mixed(
+    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, bool accumulate,
+    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes) {
+  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
+  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
+  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType >= (int64_t)DGPU_FLOAT16 && floatType <= (int64_t)DGPU_FLOAT32, "dietgpu: float_type must be 1, 2 or 3");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tAccs.size();
+  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  size_t used = 0;
+  check(dgpu_float_decode_reduce_mixed(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
+                                       (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), m.accPtrs.data(),
+                                       m.capacity.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
+        "floatDecompressReduceMixed", true);
+  return (int64_t)used;
+}
+
+// decompress_data_reduce_compress with sources that are archives or raw rows (dgpu_float_reduce_compress_mixed).
+std::tuple<at::Tensor, at::Tensor, int64_t> decompress_data_reduce_compress_mixed(
+    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, bool accumulate,
+    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes,
+    const std::optional<at::Tensor>& outCompressed, const std::optional<at::Tensor>& outCompressedSizes) {
+  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
+  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
+  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tAccs.size();
+  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  at::Tensor comp, sizes;
+  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)m.maxWords), dev,
+                  tAccs[0].device(), comp, sizes);
+  std::vector<void*> compPtrs(n);
+  for (size_t i = 0; i < n; ++i) compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
+  size_t used = 0;
+  check(dgpu_float_reduce_compress_mixed(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
+                                         (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), m.accPtrs.data(),
+                                         m.capacity.data(), compPtrs.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes),
+                                         (uint32_t*)sizes.data_ptr(), streamOf(dev)),
+        "floatReduceCompressMixed", true);
+  return {std::move(comp), std::move(sizes), (int64_t)used};
+}
+
 void set_precision(int64_t probBits) {
   TORCH_CHECK(probBits == 9 || probBits == 10 || probBits == 11, "probBits must be 9, 10 or 11");
   tPrecision = (int)probBits;
@@ -747,6 +846,12 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "decompress_data_reduce_compress(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::decompress_data_reduce_compress);
+  m.def(
+      "decompress_data_reduce_mixed(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
+      &dietgpu_amd::decompress_data_reduce_mixed);
+  m.def(
+      "decompress_data_reduce_compress_mixed(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
+      &dietgpu_amd::decompress_data_reduce_compress_mixed);
 }
 
 TORCH_LIBRARY(dietgpu, m) {

@@ -181,6 +181,28 @@ class GpuFloatCodec:
                                                              dtype=self.dtype)
         return status, comp, sizes
 
+    def _mixed_dtype(self, rows_per_acc):
+        # (a raw row says what the call's float type is; without one, what the last compress call held)
+        return next((t.dtype for rows in rows_per_acc for t in rows if t.dtype != torch.uint8), self.dtype)
+
+    def decompress_reduce_mixed(self, rows_per_acc, accs, accumulate):
+        """decompress_reduce whose rows are uint8 archives or UNCOMPRESSED 1-D tensors of the rows' dtype, which are widened
+        and added in their place -> status, one per accumulator"""
+        from . import ops
+
+        status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
+        ops.decompress_data_reduce_mixed(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self._mixed_dtype(rows_per_acc))
+        return status
+
+    def decompress_reduce_compress_mixed(self, rows_per_acc, accs, accumulate):
+        """decompress_reduce_compress with rows as in decompress_reduce_mixed -> (status, comp, sizes)"""
+        from . import ops
+
+        status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
+        comp, sizes, _ = ops.decompress_data_reduce_compress_mixed(rows_per_acc, accs, accumulate, self.temp_mem, status, None,
+                                                                   dtype=self._mixed_dtype(rows_per_acc))
+        return status, comp, sizes
+
 
 def compressed_all_gather(tensors, codec=None):
     """All-gathers a list of equally-shaped float tensors per rank, moving compressed bytes.
@@ -234,14 +256,30 @@ def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec):
 _MAX_REDUCE_SOURCES = 64  # of one decode-reduce call (dgpu_float_decode_reduce)
 
 
-def _exchange_shard_rows(tensor, codec):
+def _exchange_shard_rows(tensor, codec, raw_local=False):
     """The exchange half of compressed_reduce_scatter: shard j of this rank's flat tensor, compressed, goes to rank j ->
-    (words per shard, recv [source rank, width] uint8, all_sizes [source rank, destination rank] int32, width)."""
+    (words per shard, recv [source rank, width] uint8, all_sizes [source rank, destination rank] int32, width).
+    raw_local: the rank's own shard is not compressed (the codec gets the other world - 1, none at all in a world of one);
+    its row of the exchange has size 0 and carries nothing."""
     world = dist.get_world_size()
     if tensor.dim() != 1 or tensor.numel() % world != 0:
         raise RuntimeError("compressed_reduce_scatter: the tensor must be flat, its length a multiple of the world size")
     shard_words = tensor.numel() // world
-    comp, sizes = codec.compress(list(tensor.view(world, shard_words).unbind(0)))  # all shards in one call
+    shards = list(tensor.view(world, shard_words).unbind(0))
+    if raw_local:
+        me = dist.get_rank()
+        others = [j for j in range(world) if j != me]
+        sizes = torch.zeros((world,), dtype=torch.int32, device=tensor.device)
+        comp = torch.empty((world, 0), dtype=torch.uint8, device=tensor.device)
+        if others:
+            comp_others, sizes_others = codec.compress([shards[j] for j in others])
+            at = torch.tensor(others, dtype=torch.int64, device=tensor.device)
+            sizes[at] = sizes_others[: len(others)].to(torch.int32)
+            comp = torch.empty((world, comp_others.shape[1]), dtype=torch.uint8, device=tensor.device)
+            comp[at] = comp_others[: len(others)]
+            comp[me].zero_()  # (travels to this rank itself; nothing reads it)
+    else:
+        comp, sizes = codec.compress(shards)  # all shards in one call
     sizes = sizes.to(torch.int32)
 
     # phase 1: sizes (every rank learns every row's size: the width is the widest row anywhere)
@@ -253,13 +291,23 @@ def _exchange_shard_rows(tensor, codec):
     # phase 2: row j of this rank to rank j, trimmed to the widest row
     send = comp[:, :width].contiguous()
     recv = torch.empty_like(send)
-    work = _all_to_all_flat(recv.view(-1), send.view(-1), world)
-    if work is not None:
-        work.wait()
+    if width:  # (0: a world of one with raw_local -- every rank sees the same width)
+        work = _all_to_all_flat(recv.view(-1), send.view(-1), world)
+        if work is not None:
+            work.wait()
     return shard_words, recv, all_sizes, width
 
 
-def compressed_reduce_scatter(tensor, codec=None):
+def _rows_with_local(tensor, recv, all_sizes, me, world, raw_local):
+    """The sources of this rank's shard in rank order: the received rows, with the rank's own shard uncompressed in its
+    place when raw_local."""
+    rows = [recv[r, : int(all_sizes[r, me])] for r in range(world)]
+    if raw_local:
+        rows[me] = tensor.view(world, -1)[me]
+    return rows
+
+
+def compressed_reduce_scatter(tensor, codec=None, raw_local=False):
     """Reduce-scatter (sum) of a flat float tensor, moving compressed bytes and summing in float32.
 
     `tensor`: this rank's flat fp16 / bf16 / fp32 tensor; its length is a multiple of the world size and the same on
@@ -274,11 +322,26 @@ def compressed_reduce_scatter(tensor, codec=None):
     decode-reduce path the shard was then not partly summed (the call adds all rows or none).
     `codec` needs compress(list) -> (uint8 [n, cap], int32 [n]) and, for the shard's sum, decompress_reduce(rows_per_acc,
     accs, accumulate) -> uint8 status [len(accs)] or decompress_accumulate(rows, accs, accumulate) -> uint8 status [n];
-    a world of more than 64 ranks needs decompress_accumulate (RuntimeError without it)."""
+    a world of more than 64 ranks needs decompress_accumulate (RuntimeError without it).
+
+    raw_local=True, with a codec that has decompress_reduce_mixed(rows_per_acc, accs, accumulate) in a world of at most
+    64 ranks: the rank's own shard is neither compressed nor sent to itself nor decoded -- the codec compresses the other
+    world - 1 shards (none in a world of one) and the sum takes `tensor.view(world, -1)[me]` as it is, at position `me`
+    of the rank order.  The result is bit-identical; stats["payload_bytes"] no longer holds the own row.  Without the
+    method, or in a larger world, the call quietly takes the path above."""
     codec = codec or GpuFloatCodec()
     world = dist.get_world_size()
-    shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec)
     me = dist.get_rank()
+    if raw_local and callable(getattr(codec, "decompress_reduce_mixed", None)) and world <= _MAX_REDUCE_SOURCES:
+        shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec, True)
+        shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
+        status = codec.decompress_reduce_mixed([_rows_with_local(tensor, recv, all_sizes, me, world, True)], [shard], False)
+        if not bool(status.all().item()):
+            raise RuntimeError("decode-reduce of the received rows failed: a row is malformed or the rows differ in length; "
+                               "the shard was not partly summed")
+        return shard, {"raw_bytes": tensor.numel() * tensor.element_size(), "wire_bytes": world * width,
+                       "payload_bytes": int(all_sizes[me].sum().item())}
+    shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec)
     shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
     has_reduce = callable(getattr(codec, "decompress_reduce", None))
     if not (has_reduce and world <= _MAX_REDUCE_SOURCES) and not callable(getattr(codec, "decompress_accumulate", None)):
@@ -302,7 +365,7 @@ def compressed_reduce_scatter(tensor, codec=None):
     return shard, stats
 
 
-def compressed_all_reduce(tensor, codec=None):
+def compressed_all_reduce(tensor, codec=None, raw_local=False):
     """All-reduce (sum) of a flat fp16 / bf16 tensor, moving compressed bytes both ways and summing in float32.
 
     Three steps: `compressed_reduce_scatter` (this rank's float32 shard of the sum), the codec's `compress_cast` of that
@@ -316,16 +379,22 @@ def compressed_all_reduce(tensor, codec=None):
     A codec with decompress_reduce_compress(rows_per_acc, accs, accumulate) -> (status, comp, sizes), in a world of at most
     64 ranks, makes the middle ONE call: the received rows are summed into the shard and the shard's archive is written
     by the same call, which counts the exponents while it sums instead of reading the shard again for a histogram.  The
-    result is bit-identical to the three-step path."""
+    result is bit-identical to the three-step path.
+
+    raw_local=True: as in compressed_reduce_scatter -- the rank's own shard enters the sum uncompressed.  On the one-call
+    path that needs the codec's decompress_reduce_compress_mixed, on the three-step path its decompress_reduce_mixed;
+    without the method the path needs, today's path runs.  Bit-identical either way."""
     if tensor.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError("compressed_all_reduce: the tensor must be float16 or bfloat16")
     codec = codec or GpuFloatCodec()
     world = dist.get_world_size()
     if callable(getattr(codec, "decompress_reduce_compress", None)) and world <= _MAX_REDUCE_SOURCES:
-        shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec)
+        mixed = raw_local and callable(getattr(codec, "decompress_reduce_compress_mixed", None))
+        shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec, mixed)
         me = dist.get_rank()
         shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
-        status, comp, sizes = codec.decompress_reduce_compress([[recv[r, : int(all_sizes[r, me])] for r in range(world)]], [shard], False)
+        reduce_compress = codec.decompress_reduce_compress_mixed if mixed else codec.decompress_reduce_compress
+        status, comp, sizes = reduce_compress([_rows_with_local(tensor, recv, all_sizes, me, world, mixed)], [shard], False)
         if not bool(status.all().item()):
             raise RuntimeError("reduce-compress of the received rows failed: a row is malformed or the rows differ in length")
         rs = {
@@ -334,7 +403,7 @@ def compressed_all_reduce(tensor, codec=None):
             "payload_bytes": int(all_sizes[me].sum().item()),
         }
     else:
-        shard, rs = compressed_reduce_scatter(tensor, codec)
+        shard, rs = compressed_reduce_scatter(tensor, codec, raw_local)
         comp, sizes = codec.compress_cast([shard], tensor.dtype)
     out = torch.empty_like(tensor)
     rows = out.view(world, shard.numel())

@@ -775,6 +775,106 @@ def decompress_data_reduce_compress(ts_in, ts_acc, accumulate=False, temp_mem=No
     return comp, sizes, int(used.value)
 
 
+# ------------------------------------------------------------------ mixed sources
+# (no reference ops: dgpu_float_decode_reduce_mixed / dgpu_float_reduce_compress_mixed, include/dietgpu_amd.h)
+def _mixed_sources(ts_in, ts_acc, dtype, allowed):
+    """Checks of the two mixed calls -> (flat member-major sources, sources per accumulator, device, float type or None).
+    A uint8 tensor is an archive; a 1-D tensor of the call's float dtype a raw row.  The float type is `dtype`, else that
+    of the first raw row, else None (the caller reads it from the first archive's header)."""
+    _check(len(ts_in) > 0)
+    _check(len(ts_in) == len(ts_acc), "one list of sources per accumulator")
+    sources = len(ts_in[0])
+    _check(1 <= sources <= MAX_REDUCE_SOURCES, "between 1 and 64 sources per accumulator")
+    for srcs in ts_in:
+        _check(len(srcs) == sources, "every accumulator takes the same number of sources")
+    flat = [t for srcs in ts_in for t in srcs]  # member-major
+    _check(flat[0].is_cuda, "tensors must be on the GPU")
+    dev = flat[0].get_device()
+    _check(dtype is None or dtype in allowed, "dtype must be one of " + ", ".join(str(d).replace("torch.", "") for d in allowed))
+    if dtype is None:
+        dtype = next((t.dtype for t in flat if t.dtype != torch.uint8), None)
+    for ti in flat:
+        _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous(), "sources must be contiguous tensors on one GPU")
+        if ti.dtype != torch.uint8:
+            _check(ti.dtype == dtype and dtype in allowed, "a source is a uint8 archive or a raw row of the call's float dtype")
+            _check(ti.dim() == 1, "a raw source must be 1-D")
+            _check(ti.numel() * ti.element_size() <= _U32_MAX)
+    for ta in ts_acc:
+        _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
+        _check(ta.dtype == torch.float32, "accumulators must be float32")
+        _check(ta.numel() <= _U32_MAX)
+    return flat, sources, dev, (_DTYPE_TO_FT[dtype] if dtype is not None else None)
+
+
+def _source_kinds(flat):
+    return _cached_array(C.c_uint8, tuple(0 if t.dtype == torch.uint8 else 1 for t in flat))
+
+
+def decompress_data_reduce_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
+                                 prob_bits=K_DEFAULT_PRECISION, dtype=None):
+    """`decompress_data_reduce` whose sources may be UNCOMPRESSED: an entry of ts_in[i] is a uint8 archive or a raw row --
+    a 1-D contiguous tensor of the call's float dtype, aligned to its element size only -- which is widened and added in
+    its place in source order.  Bit for bit what decompress_data_reduce leaves when every raw row is replaced by its
+    archive.  A raw row's numel() counts as the size a header states (all sources equal, at most ts_acc[i].numel(),
+    reported in out_sizes[i] when it is the first source).  Raw rows must not overlap the accumulators.  `dtype`: given,
+    else that of the first raw row, else read from the header of the first archive -> temp bytes used (0)."""
+    flat, sources, dev, ft = _mixed_sources(ts_in, ts_acc, dtype, (torch.float16, torch.bfloat16, torch.float32))
+    n = len(ts_acc)
+    _validate_status(out_status, out_sizes, n, dev)
+    with torch.cuda.device(dev):
+        tp, tb = _temp(temp_mem, dev)
+        if ft is None:
+            ft = _header_info(True, flat[:1], tp, tb)[1][0]
+            _check(ft in _FT_TO_DTYPE, "ts_in[0][0] is not a float archive")
+        if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_mixed"):
+            torch.ops.dietgpu_amd.set_precision(prob_bits)
+            try:
+                return torch.ops.dietgpu_amd.decompress_data_reduce_mixed(flat, sources, ts_acc, ft, bool(accumulate), temp_mem,
+                                                                          out_status, out_sizes)
+            finally:
+                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+        used = C.c_size_t(0)
+        check(lib().dgpu_float_decode_reduce_mixed(
+            tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
+            _source_kinds(flat), _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), _ptr(out_status), _ptr(out_sizes),
+            _stream()))
+    return int(used.value)
+
+
+def decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
+                                          out_compressed=None, out_compressed_sizes=None, prob_bits=K_DEFAULT_PRECISION,
+                                          dtype=None):
+    """`decompress_data_reduce_compress` whose sources may be uncompressed rows, as in decompress_data_reduce_mixed (every
+    source, raw or not, must hold EXACTLY ts_acc[i].numel() words) -> (comp, sizes, temp bytes used).  `dtype`: float16 or
+    bfloat16."""
+    flat, sources, dev, ft = _mixed_sources(ts_in, ts_acc, dtype, (torch.float16, torch.bfloat16))
+    n = len(ts_acc)
+    _validate_status(out_status, out_sizes, n, dev)
+    with torch.cuda.device(dev):
+        tp, tb = _temp(temp_mem, dev)
+        if ft is None:
+            ft = _header_info(True, flat[:1], tp, tb)[1][0]
+            _check(ft in (_DTYPE_TO_FT[torch.float16], _DTYPE_TO_FT[torch.bfloat16]), "ts_in[0][0] is not a float16 / bfloat16 archive")
+        if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_compress_mixed"):
+            torch.ops.dietgpu_amd.set_precision(prob_bits)
+            try:
+                return torch.ops.dietgpu_amd.decompress_data_reduce_compress_mixed(
+                    flat, sources, ts_acc, ft, bool(accumulate), temp_mem, out_status, out_sizes, out_compressed, out_compressed_sizes)
+            finally:
+                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+        _, mx = _total_and_max(ts_acc)
+        cols = _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
+        comp, sizes = _validate_out(out_compressed, out_compressed_sizes, n, cols, dev, ts_acc[0].device)
+        row = comp.size(1)
+        out_ptrs = (C.c_void_p * n)(*[comp.data_ptr() + i * row for i in range(n)])
+        used = C.c_size_t(0)
+        check(lib().dgpu_float_reduce_compress_mixed(
+            tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
+            _source_kinds(flat), _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), out_ptrs, _ptr(out_status),
+            _ptr(out_sizes), _ptr(sizes), _stream()))
+    return comp, sizes, int(used.value)
+
+
 def _check_slice_args(compress_as_float, ts_in, dtype):
     _check(len(ts_in) > 0)
     for t in ts_in:

@@ -69,7 +69,8 @@ const char* dgpu_version(void);
  * point that is only ADDED leaves every existing one as it was and does not move the version: a library without the new
  * symbol fails at load too, by symbol resolution, in anything that links it (dgpu_float_decode_accumulate,
  * dgpu_float_cast_compress, dgpu_float_decode_reduce, dgpu_float_reduce_compress,
- * dgpu_float_reduce_compress_temp_bytes and dgpu_float_rolling_compress were added at version 8). */
+ * dgpu_float_reduce_compress_temp_bytes, dgpu_float_rolling_compress, dgpu_float_decode_reduce_mixed and
+ * dgpu_float_reduce_compress_mixed were added at version 8). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -446,6 +447,47 @@ int dgpu_float_reduce_compress(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
     uint32_t numInBatch, uint32_t numSources,
     const void* const* in /* [numInBatch * numSources] */, const uint32_t* inBytes /* same shape */,
+    void* const* acc /* float32, [numInBatch] */, const uint32_t* outCapacity /* float words */,
+    void* const* outArchive /* [numInBatch] */,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev /* words */, uint32_t* outArchiveSize_dev /* bytes */,
+    void* stream);
+
+/* ---- mixed sources: archives and raw rows (no upstream equivalent) ------------------------
+ * dgpu_float_decode_reduce and dgpu_float_reduce_compress whose sources may be UNCOMPRESSED: the shard a rank already
+ * holds takes its place in the rank-ordered sum without being compressed and decoded again.  Everything said of the two
+ * calls above holds (layout, order of the adds, widening, all or nothing per member, what outSize_dev reports, temp
+ * memory, no synchronisation, graph capture after one identical warm call), with these additions:
+ *   - sourceKind: a HOST array of numInBatch * numSources bytes, member-major like `in`: 0, source k is an archive;
+ *     1, it is RAW: in[k] points at inBytes[k] / wordBytes words of floatType (2 bytes for float16 and bfloat16, 4 for
+ *     float32), aligned to the word size -- a shard row of a flat tensor is not 16-byte aligned in general; the kernel
+ *     loads 16 bytes at a time from a 16-byte aligned row and 4 or 2 bytes at a time otherwise.
+ *   - The count a raw source states is inBytes[k] / wordBytes.  It takes part in "all sources state the same word
+ *     count" and in "<= outCapacity[i]" ("== outCapacity[i]" in reduce-compress) exactly like a header's; if source 0
+ *     is raw, outSize_dev[i] is that count.  A member with a raw source whose count disagrees fails like any other.
+ *   - The words are widened as decoded words are and added with one __fadd_rn in their place in source order: the
+ *     result is bit for bit what the plain call leaves when every raw row is replaced by its archive.
+ *   - All sources of a member raw is valid (no probability table is read for it), and so is numSources == 1 with a raw
+ *     source, which stores or adds the widened row.
+ *   - Raw sources MUST NOT overlap any accumulator or output archive of the call; they may alias each other and
+ *     archive sources.
+ *   - DGPU_ERR_INVALID_ARGUMENT, with a dgpu_last_error() text and before anything is enqueued, also for: sourceKind
+ *     null with numInBatch > 0, a kind other than 0 or 1, a raw in[k] not aligned to the word size, a raw inBytes[k]
+ *     that is not a multiple of it.  The 16-byte alignment is required of archive sources only.
+ *   - sourceKind is part of the batch's description: it is in the resident parameter block and its cache key, so a
+ *     call that differs from a warm one only in its kinds is a different batch (and, under capture, not a warm one).
+ *   - With every kind 0 the calls ARE dgpu_float_decode_reduce / dgpu_float_reduce_compress: same kernels, same block. */
+int dgpu_float_decode_reduce_mixed(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources,
+    const void* const* in /* [numInBatch * numSources] */, const uint32_t* inBytes /* same shape */,
+    const uint8_t* sourceKind /* HOST, same shape: 0 archive, 1 raw */,
+    void* const* out /* float32, [numInBatch] */, const uint32_t* outCapacity /* float words, [numInBatch] */,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
+int dgpu_float_reduce_compress_mixed(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources,
+    const void* const* in /* [numInBatch * numSources] */, const uint32_t* inBytes /* same shape */,
+    const uint8_t* sourceKind /* HOST, same shape: 0 archive, 1 raw */,
     void* const* acc /* float32, [numInBatch] */, const uint32_t* outCapacity /* float words */,
     void* const* outArchive /* [numInBatch] */,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev /* words */, uint32_t* outArchiveSize_dev /* bytes */,

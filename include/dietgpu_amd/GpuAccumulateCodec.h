@@ -38,4 +38,20 @@ inline void floatDecompressReduce(
                   "floatDecompressReduce");
 }
 
+// Decode-reduce with mixed sources: floatDecompressReduce whose source k is an archive (sourceKind[k] == 0) or a RAW row
+// of inBytes[k] / wordBytes words of config.floatType (1), word-aligned, widened and added in its place in source order
+// -- bit for bit what floatDecompressReduce leaves when the row is replaced by its archive.  `sourceKind` is a HOST
+// array shaped like `in`.  dgpu_float_decode_reduce_mixed of ../dietgpu_amd.h.
+inline void floatDecompressReduceMixed(
+    StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, uint32_t numSources,
+    const void** in, const uint32_t* inBytes, const uint8_t* sourceKind, float** out, const uint32_t* outCapacity,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+  (void)res;
+  size_t used = 0;
+  detail::checkRc(dgpu_float_decode_reduce_mixed(nullptr, 0, &used, (uint32_t)config.floatType, config.ansConfig.probBits,
+                                                 accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, sourceKind,
+                                                 (void* const*)out, outCapacity, outSuccess_dev, outSize_dev, stream),
+                  "floatDecompressReduceMixed");
+}
+
 }  // namespace dietgpu

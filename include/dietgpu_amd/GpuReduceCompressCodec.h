@@ -27,4 +27,21 @@ inline void floatDecompressReduceCompress(
                   "floatDecompressReduceCompress");
 }
 
+// Reduce-compress with mixed sources: as floatDecompressReduceCompress, source k an archive (sourceKind[k] == 0) or a RAW
+// row of exactly outCapacity[i] words of config.floatType (1); `sourceKind` is a HOST array shaped like `in`.
+// dgpu_float_reduce_compress_mixed of ../dietgpu_amd.h.
+inline void floatDecompressReduceCompressMixed(
+    StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, uint32_t numSources,
+    const void** in, const uint32_t* inBytes, const uint8_t* sourceKind, float** acc, const uint32_t* outCapacity, void** outArchive,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream) {
+  uint32_t maxWords = 0;
+  for (uint32_t i = 0; i < numInBatch; ++i) maxWords = std::max(maxWords, outCapacity[i]);
+  detail::TempRegion t(res, stream, dgpu_float_reduce_compress_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords));
+  detail::checkRc(dgpu_float_reduce_compress_mixed(t.ptr, t.bytes, &t.used, (uint32_t)config.floatType, config.ansConfig.probBits,
+                                                   accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, sourceKind,
+                                                   (void* const*)acc, outCapacity, outArchive, outSuccess_dev, outSize_dev,
+                                                   outArchiveSize_dev, stream),
+                  "floatDecompressReduceCompressMixed");
+}
+
 }  // namespace dietgpu
