@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <atomic>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1534,15 +1535,19 @@ int mixedSourceAddresses(const char* nullMsg, const void* const* in, const uint3
 // decode-accumulate call with the same capacities.  No temp memory, no host synchronisation.
 // mixed (dgpu_float_decode_reduce_mixed): `kinds` says which sources are raw rows (mixedSourceAddresses); with one
 // among them the launch is k_ans_decode_reduce_mixed, for S == 1 too; with none the call is the plain one from here on.
+// scale (dgpu_float_decode_reduce_scaled): other than 1, the launch is k_ans_decode_reduce_mixed_scaled whatever the
+// kinds and for S == 1 too, with the factor as a kernel argument: the parameter block and its cache entry are those of
+// the unscaled call.  1 is the unscaled call.
 int decodeReduceImpl(
     size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, uint32_t S, const void* const* in, const uint32_t* inBytes,
     void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream, bool mixed = false,
-    const uint8_t* kinds = nullptr) {
+    const uint8_t* kinds = nullptr, float scale = 1.0f) {
   DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
+  const bool scaled = scale != 1.0f;
   DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "decode-reduce: accumulate must be 0 or 1");
   DGPU_REQUIRE(S >= 1u && S <= kMaxReduceSources, "decode-reduce: numSources must be between 1 and 64");
   DGPU_REQUIRE((uint64_t)B * S <= 65535u, "decode-reduce: numInBatch * numSources must be <= 65535");
-  if (S == 1u && !mixed) return decodeAccumulateImpl(tempUsed, ft, P, accumulate, B, in, inBytes, out, outCapacity, outSuccess_dev, outSize_dev, stream);
+  if (S == 1u && !mixed && !scaled) return decodeAccumulateImpl(tempUsed, ft, P, accumulate, B, in, inBytes, out, outCapacity, outSuccess_dev, outSize_dev, stream);
   bool done;
   int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
   if (done) return rc;
@@ -1552,7 +1557,7 @@ int decodeReduceImpl(
   // (pointerBatch, with S inputs per output)
   if (mixed) {
     rc = mixedSourceAddresses("decode-reduce: sourceKind is null with numInBatch > 0", in, inBytes, kinds, B * S, floatWordBytes(ft), &b.inPtrs, &anyRaw);
-    if (!rc && !anyRaw && S == 1u) {
+    if (!rc && !anyRaw && S == 1u && !scaled) {
       return decodeAccumulateImpl(tempUsed, ft, P, accumulate, B, in, inBytes, out, outCapacity, outSuccess_dev, outSize_dev, stream);
     }
   } else {
@@ -1574,7 +1579,8 @@ int decodeReduceImpl(
   DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
   d.accumulate = (uint32_t)accumulate;
   d.numSources = S;
-  return launchDecode(d, groups[0], dev.work, anyRaw ? DecodeForm::kReduceMixed : DecodeForm::kReduce, P, stream);
+  d.scale = scale;
+  return launchDecode(d, groups[0], dev.work, scaled ? DecodeForm::kReduceScaled : (anyRaw ? DecodeForm::kReduceMixed : DecodeForm::kReduce), P, stream);
 }
 
 // Reduce-compress: decode-reduce into the accumulators, then cast-compress of the accumulators, without the cast
@@ -1585,11 +1591,13 @@ int decodeReduceImpl(
 // region of temp memory cleared by one memset on the stream.  A member that fails the reduce has no counts: its table is
 // the flat one, which codes any data.  Everything is validated before the first enqueue; nothing synchronises.
 // mixed (dgpu_float_reduce_compress_mixed): as in decodeReduceImpl; the reduce kernel is k_ans_decode_reduce_mixed_stats.
+// scale (dgpu_float_reduce_compress_scaled): as in decodeReduceImpl; the reduce kernel is
+// k_ans_decode_reduce_mixed_stats_scaled, which stores, rounds and counts the scaled sums.  The encoder does not know.
 int reduceCompressImpl(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, uint32_t S,
     const void* const* in, const uint32_t* inBytes, void* const* acc, const uint32_t* outCapacity, void* const* outArchive,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream, bool mixed = false,
-    const uint8_t* kinds = nullptr) {
+    const uint8_t* kinds = nullptr, float scale = 1.0f) {
   DGPU_REQUIRE(ft == kFloat16 || ft == kBFloat16, "reduce-compress: floatType must be float16 or bfloat16 (float32: decode-reduce, then dgpu_float_compress)");
   DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "reduce-compress: accumulate must be 0 or 1");
   DGPU_REQUIRE(S >= 1u && S <= kMaxReduceSources, "reduce-compress: numSources must be between 1 and 64");
@@ -1643,7 +1651,9 @@ int reduceCompressImpl(
   d.accumulate = (uint32_t)accumulate;
   d.numSources = S;
   d.stats = counts;
-  rc = launchDecode(d, groupsD[0], devD.work, anyRaw ? DecodeForm::kReduceMixedStats : DecodeForm::kReduceStats, P, stream);
+  d.scale = scale;
+  const DecodeForm form = scale != 1.0f ? DecodeForm::kReduceScaledStats : (anyRaw ? DecodeForm::kReduceMixedStats : DecodeForm::kReduceStats);
+  rc = launchDecode(d, groupsD[0], devD.work, form, P, stream);
   if (!rc) {
     EncodeShared shared;
     rc = encodeCommon(arena, streamLease, stream, P, false, B, devE.in, devE.out, castType, groupsE[0], devE.work, shared,
@@ -1996,6 +2006,32 @@ int dgpu_float_reduce_compress_mixed(
     uint32_t* outArchiveSize_dev, void* stream) {
   return reduceCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, acc,
                             outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream, true, sourceKind);
+}
+
+// ---- scaled: acc = fl32(sum * scale) in the reduce kernel (no upstream equivalent) ----------------
+// (sourceKind NULL: every source is an archive.  The scale is checked first: nothing is enqueued for a bad one.)
+static bool scaleOk(float scale) { return std::isfinite(scale) && scale != 0.0f; }
+
+int dgpu_float_decode_reduce_scaled(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, const uint8_t* sourceKind,
+    float scale, void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream) {
+  (void)temp_dev;
+  (void)tempBytes;
+  DGPU_REQUIRE(scaleOk(scale), "decode-reduce: scale must be finite and not zero");
+  return decodeReduceImpl(tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, out, outCapacity,
+                          outSuccess_dev, outSize_dev, (hipStream_t)stream, sourceKind != nullptr, sourceKind, scale);
+}
+
+int dgpu_float_reduce_compress_scaled(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, const uint8_t* sourceKind,
+    float scale, void* const* acc, const uint32_t* outCapacity, void* const* outArchive, uint8_t* outSuccess_dev,
+    uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, void* stream) {
+  DGPU_REQUIRE(scaleOk(scale), "reduce-compress: scale must be finite and not zero");
+  return reduceCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, acc,
+                            outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream,
+                            sourceKind != nullptr, sourceKind, scale);
 }
 
 // ---- float stride batches with capacities on both sides (the compressed collectives) --------------------

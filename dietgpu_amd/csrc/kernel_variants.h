@@ -168,7 +168,10 @@ inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, boo
 //     (DecodeArgs::stats); float16 and bfloat16 only (anything else: the bfloat16 form), 16- and 4-block tiles, with
 //     the LDS of the bins behind that of the plain form;
 //   * DecodeForm::kReduceMixed / kReduceMixedStats: k_ans_decode_reduce_mixed / k_ans_decode_reduce_mixed_stats, the two
-//     above with sources that are archives or raw rows (DecodeArgs::sourceKind); the same types, tiles and LDS.
+//     above with sources that are archives or raw rows (DecodeArgs::sourceKind); the same types, tiles and LDS;
+//   * DecodeForm::kReduceScaled / kReduceScaledStats: k_ans_decode_reduce_mixed_scaled / _mixed_stats_scaled, the mixed
+//     forms that multiply the last source's store by DecodeArgs::scale; they serve all-archive members too.  The
+//     counting form keeps the factor in LDS behind its bins (decReduceStatsScaledLdsBytes).
 inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, DecodeForm form = DecodeForm::kWhole) {
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> DecodeVariant {
     constexpr int kP = decltype(p)::value;
@@ -211,6 +214,23 @@ inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, Dec
         constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
         return {k_ans_decode_reduce_mixed_stats<kP, kCastFT, kTB>, decThreads(kTB), decReduceStatsLdsBytes(kP, kCastFT, kTB),
                 "k_ans_decode_reduce_mixed_stats"};
+      };
+      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
+    }
+    if (form == DecodeForm::kReduceScaled) {
+      auto tiled = [](auto tb) -> DecodeVariant {
+        constexpr uint32_t kTB = decltype(tb)::value;
+        constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
+        return {k_ans_decode_reduce_mixed_scaled<kP, kAccFT, kTB>, decThreads(kTB), decLdsBytes(kP, kAccFT, kTB), "k_ans_decode_reduce_mixed_scaled"};
+      };
+      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
+    }
+    if (form == DecodeForm::kReduceScaledStats) {
+      auto tiled = [](auto tb) -> DecodeVariant {
+        constexpr uint32_t kTB = decltype(tb)::value;
+        constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
+        return {k_ans_decode_reduce_mixed_stats_scaled<kP, kCastFT, kTB>, decThreads(kTB), decReduceStatsScaledLdsBytes(kP, kCastFT, kTB),
+                "k_ans_decode_reduce_mixed_stats_scaled"};
       };
       return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
     }

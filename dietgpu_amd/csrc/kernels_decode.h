@@ -72,6 +72,9 @@ struct DecodeArgs {
   // k_ans_decode_reduce_stats only: [numInBatch][256] counts of the exponent bytes of the stored sums, rounded to the
   // archive type (zero at launch; see decodeReduceTile, kStats)
   uint32_t* stats = nullptr;
+  // the scaled forms of k_ans_decode_reduce_mixed / _mixed_stats only: acc = fl32(sum * scale) on the last source's store
+  // (finite, not zero, not 1: the host launches the unscaled kernels for 1; see decodeReduceTile, kScaled)
+  float scale = 1.0f;
 };
 __device__ __forceinline__ uint64_t decodeInBytes(const DecodeArgs& a, uint32_t b) {
   return a.inBytes ? (uint64_t)a.inBytes[b] : (a.uniformInBytes ? (uint64_t)a.uniformInBytes : ~0ull);
@@ -344,11 +347,38 @@ struct AccumBins<true> {
   uint32_t bins;
 };
 
-template <uint32_t FT, uint32_t kSlots = 0>
-struct AccumSink : AccumBins<kSlots != 0u> {  // kFloat16 / kBFloat16
+// kScaled (the scaled forms of the mixed reduce kernels): on the LAST source the word about to be stored is multiplied by
+// the call's scale -- one IEEE float32 multiply after the add, before the store and before count(), so the value counted
+// is the value stored.  Where the factor lives: the plain sinks have registers to spare and keep it beside a flag for
+// the last source (AccumScale<true>); the counting sink has none (128 VGPRs, the scalar file full: a member, or a
+// reload from the kernel arguments, spills a scalar into a VGPR lane, 129) and reads it from LDS, one float per slot
+// column directly behind the bins, through the address it already holds: at bins + kNumSymbols * kSlots * 4.  Its
+// `bins` is non-zero on the last source and on no other, which is the flag.
+template <bool kInRegisters>
+struct AccumScale {};
+template <>
+struct AccumScale<true> {
+  float scale;
+  uint32_t scaleLast;  // wave-uniform: this is the last source
+};
+typedef __attribute__((address_space(3))) float LdsF32w;
+// (__fmul_rn: never contracted)
+__device__ __forceinline__ uint32_t accScale(uint32_t o, float f) { return __builtin_bit_cast(uint32_t, __fmul_rn(__builtin_bit_cast(float, o), f)); }
+
+template <uint32_t FT, uint32_t kSlots = 0, bool kScaledSink = false>
+struct AccumSink : AccumBins<kSlots != 0u>, AccumScale<kScaledSink && kSlots == 0u> {  // kFloat16 / kBFloat16
   static_assert(FT == kFloat16 || FT == kBFloat16, "");
   static constexpr bool kStats = kSlots != 0u;
+  static constexpr bool kScaled = kScaledSink;
   static constexpr uint32_t kStatSlots = kSlots;
+  __device__ __forceinline__ bool scales() const {
+    if constexpr (kStats) return this->bins != 0u;
+    else return this->scaleLast != 0u;
+  }
+  __device__ __forceinline__ float factor() const {
+    if constexpr (kStats) return *(LdsF32w*)(uintptr_t)(this->bins + kNumSymbols * kSlots * 4u);
+    else return this->scale;
+  }
   float* out;
   const uint8_t* nc;
   uint32_t accumulate;
@@ -382,7 +412,10 @@ struct AccumSink : AccumBins<kSlots != 0u> {  // kFloat16 / kBFloat16
   // h: the 16-bit word of FT in the LOW half
   __device__ __forceinline__ void storeWord(uint32_t row, uint32_t h, const AccumPre& p) const {
     const float v = accWiden16<FT>(h);
-    const uint32_t o = accumulate ? accAdd(p.acc, v) : __builtin_bit_cast(uint32_t, v);
+    uint32_t o = accumulate ? accAdd(p.acc, v) : __builtin_bit_cast(uint32_t, v);
+    if constexpr (kScaled) {
+      if (scales()) o = accScale(o, factor());
+    }
     streamStore<kNtDecStores>((uint32_t*)&out[row * 32u], o);
     if constexpr (kStats) {
       if (this->bins) count(o);
@@ -434,6 +467,16 @@ struct AccumSink : AccumBins<kSlots != 0u> {  // kFloat16 / kBFloat16
       o0[k] = accumulate ? accAdd(p.a0[k], v[k]) : __builtin_bit_cast(uint32_t, v[k]);
       o1[k] = accumulate ? accAdd(p.a1[k], v[4u + k]) : __builtin_bit_cast(uint32_t, v[4u + k]);
     }
+    if constexpr (kScaled) {
+      if (scales()) {
+        const float f = factor();
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+          o0[k] = accScale(o0[k], f);
+          o1[k] = accScale(o1[k], f);
+        }
+      }
+    }
     u32x4w4* dst = (u32x4w4*)(out - hl + g * 256u + hl * 8u);
     if (kNtDecStores) {
       __builtin_nontemporal_store(o0, &dst[0]);
@@ -454,10 +497,11 @@ struct AccumSink : AccumBins<kSlots != 0u> {  // kFloat16 / kBFloat16
   }
 };
 
-template <uint32_t kSlots>
-struct AccumSink<kFloat32, kSlots> {  // row-wise, as RowSink<kFloat32>: 128-byte pieces already
+template <uint32_t kSlots, bool kScaledSink>
+struct AccumSink<kFloat32, kSlots, kScaledSink> : AccumScale<kScaledSink> {  // row-wise, as RowSink<kFloat32>: 128-byte pieces already
   static_assert(kSlots == 0u, "counting sinks: the 16-bit archive types only");
   static constexpr bool kStats = false;
+  static constexpr bool kScaled = kScaledSink;
   float* out;
   const uint16_t* nc2;
   const uint8_t* nc1;
@@ -481,7 +525,10 @@ struct AccumSink<kFloat32, kSlots> {  // row-wise, as RowSink<kFloat32>: 128-byt
     return p;
   }
   __device__ __forceinline__ void storeWord(uint32_t row, uint32_t w, const AccumPre& p) const {
-    const uint32_t o = accumulate ? accAdd(p.acc, __builtin_bit_cast(float, w)) : w;
+    uint32_t o = accumulate ? accAdd(p.acc, __builtin_bit_cast(float, w)) : w;
+    if constexpr (kScaled) {
+      if (this->scaleLast != 0u) o = accScale(o, this->scale);
+    }
     streamStore<kNtDecStores>((uint32_t*)&out[row * 32u], o);
   }
   __device__ __forceinline__ void store(uint32_t row, uint32_t e0, const AccumPre& p) const {
@@ -828,7 +875,7 @@ __device__ __forceinline__ void decodeBlock(
 // descriptors (8 bytes per block, from the L2, in the round trip of the tile's own descriptor), and no tile of an element
 // with a malformed descriptor stores -- a failing element leaves its accumulator as it was.
 // (kReduce: decodeReduceTile, below)
-enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats };
+enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats };
 template <int P, uint32_t FT, uint32_t kTileBlocks, DecodeForm kForm>
 __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccum = kForm == DecodeForm::kAccum;
@@ -1258,6 +1305,12 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
 // lane-to-word mapping, so a lane touches the accumulator words it touches for an archive source, and the hand-over
 // holds in both directions.  No LDS is used, so nothing of it races with the builds of the sources around it.  Kind
 // and base alignment are uniform per source; the form is a template flag: the plain and counting kernels do not change.
+//
+// kScaled (the *_scaled kernels, built for the mixed forms, which take all-archive members as well): the last source's
+// store leaves fl32(sum * a.scale) instead of the sum, and the counting form counts that product (AccumSink, kScaled).
+// The factor is a kernel argument, not part of the parameter block: calls that differ in it alone share the block.  The
+// counting form writes it behind the bins, one float per slot column, when it zeroes them.  A template flag again: every
+// unscaled kernel keeps its code, and scale 1 launches those.
 constexpr uintptr_t kReduceRawTag = 1u;
 __device__ __forceinline__ bool reduceIsRaw(const uint8_t* source) { return ((uintptr_t)source & kReduceRawTag) != 0u; }
 typedef uint16_t u16n __attribute__((aligned(2)));
@@ -1343,6 +1396,14 @@ __device__ __forceinline__ void reduceHandOver() {
 // sums are counted -- on the LAST source
 __device__ __forceinline__ uint32_t reduceAccumulates(const DecodeArgs& a, uint32_t s) { return (s != 0u || a.accumulate != 0u) ? 1u : 0u; }
 __device__ __forceinline__ bool reduceCounts(uint32_t s, uint32_t S) { return s + 1u == S; }
+// (scaled forms that keep the factor in registers: it applies where the counting form counts)
+template <typename Sink>
+__device__ __forceinline__ void reduceScales(Sink& sink, const DecodeArgs& a, uint32_t s) {
+  if constexpr (Sink::kScaled && !Sink::kStats) {
+    sink.scale = a.scale;
+    sink.scaleLast = reduceCounts(s, a.numSources) ? 1u : 0u;
+  }
+}
 
 // A raw source's turn in the source loop of decodeReduceTile: the hand-over barrier of an archive source, the sink set up
 // as for one, and every half-wave's block through reduceRawBlock.  (Its lane indices are laundered like the loop's own.)
@@ -1359,6 +1420,7 @@ __device__ __forceinline__ void reduceRawSource(const DecodeArgs& a, uint32_t b,
   Sink sink;
   sink.accumulate = reduceAccumulates(a, s);
   if constexpr (Sink::kStats) sink.bins = reduceCounts(s, a.numSources) ? binsLds + (laneS & (Sink::kStatSlots - 1u)) * 4u : 0u;
+  reduceScales(sink, a, s);
   sink.init(a.out.ptr(b), row, total, (size_t)(haveBlock ? block : 0u) * kBlockSize, hl);
   const uint32_t left = haveBlock ? total - block * kBlockSize : 0u;
   const uint32_t align = ((uintptr_t)row & 15u) == 0u ? 16u : (((uintptr_t)row & 3u) == 0u ? 4u : 2u);
@@ -1373,11 +1435,11 @@ struct ReduceSource {  // verdict on one source (LDS)
 };
 constexpr uint32_t kMaxReduceSources = 64;
 
-template <int P, uint32_t FT, uint32_t kTileBlocks, bool kStats = false, bool kMixed = false>
+template <int P, uint32_t FT, uint32_t kTileBlocks, bool kStats = false, bool kMixed = false, bool kScaled = false>
 __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
   static_assert(FT != 0u, "decode-reduce: float archives only");
   constexpr uint32_t kSlots = kStats ? decStatsSlots(kTileBlocks) : 0u;
-  using Sink = AccumSink<FT, kSlots>;
+  using Sink = AccumSink<FT, kSlots, kScaled>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks), kWaves = kDecThreads / 64u;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint2* sLut = (uint2*)(smem + kTileBlocks * kRingBytes);
@@ -1402,6 +1464,9 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
   constexpr uint32_t kBinsAt = kTileBlocks * kRingBytes + decLutBytes(P, kTileBlocks) + kTileBlocks * kXpose;
   if constexpr (kStats) {
     for (uint32_t i = tid; i < kNumSymbols * kSlots / 4u; i += kDecThreads) ((uint4*)(smem + kBinsAt))[i] = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (kScaled) {  // the factor, one per slot column behind the bins (AccumSink::factor)
+      if (tid < kSlots) ((float*)(smem + kBinsAt + decStatsBinBytes(kTileBlocks)))[tid] = a.scale;
+    }
   }
 
   // ---- 1. validate every source ----
@@ -1532,6 +1597,7 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
     Sink sink;
     sink.accumulate = reduceAccumulates(a, s);
     if constexpr (kStats) sink.bins = reduceCounts(s, S) ? ldsBase + kBinsAt + (laneS & (kSlots - 1u)) * 4u : 0u;
+    reduceScales(sink, a, s);
     sink.init(a.out.ptr(b), archive, total, (size_t)sinkBlock * kBlockSize, hl);
     // uniform per wave (the staging mode is this source's own; full / tail follow the word count, the same for all)
     const uint32_t nFirst = __shfl(n, 0, 64);
@@ -1674,6 +1740,21 @@ template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce_mixed_stats(DecodeArgs a) {
   static_assert(FT == kFloat16 || FT == kBFloat16, "the archive types of a cast");
   decodeReduceTile<P, FT, kTileBlocks, true, true>(a);
+}
+
+// Scaled forms of the two mixed kernels: the last source's store leaves fl32(sum * DecodeArgs::scale), and the counting
+// form counts it (decodeReduceTile, kScaled).  The counting form keeps the factor in LDS behind its bins.
+__host__ __device__ constexpr uint32_t decReduceStatsScaledLdsBytes(int P, uint32_t ft, uint32_t tileBlocks) {
+  return decReduceStatsLdsBytes(P, ft, tileBlocks) + decStatsSlots(tileBlocks) * 4u;
+}
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce_mixed_scaled(DecodeArgs a) {
+  decodeReduceTile<P, FT, kTileBlocks, false, true, true>(a);
+}
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce_mixed_stats_scaled(DecodeArgs a) {
+  static_assert(FT == kFloat16 || FT == kBFloat16, "the archive types of a cast");
+  decodeReduceTile<P, FT, kTileBlocks, true, true, true>(a);
 }
 
 }  // namespace dgpu

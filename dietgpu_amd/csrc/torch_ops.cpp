@@ -12,6 +12,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <cmath>
 #include <optional>
 #include <tuple>
 #include <vector>
@@ -789,6 +790,72 @@ std::tuple<at::Tensor, at::Tensor, int64_t> decompress_data_reduce_compress_mixe
   return {std::move(comp), std::move(sizes), (int64_t)used};
 }
 
+// The scaled ops: `scale` is a float32 value (ops.py rounds it once); finite and not zero, as the C ABI demands.
+namespace {
+float checkedScale(double scale) {
+  const float f = (float)scale;
+  TORCH_CHECK(std::isfinite(f) && f != 0.0f, "dietgpu: scale must be finite and not zero");
+  return f;
+}
+}  // namespace
+
+// decompress_data_reduce_mixed whose sums are multiplied by `scale` in the reduce kernel (dgpu_float_decode_reduce_scaled).
+int64_t decompress_data_reduce_scaled(
+    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, double scale,
+    bool accumulate, const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus,
+    const std::optional<at::Tensor>& outSizes) {
+  const float f = checkedScale(scale);
+  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
+  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
+  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType >= (int64_t)DGPU_FLOAT16 && floatType <= (int64_t)DGPU_FLOAT32, "dietgpu: float_type must be 1, 2 or 3");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tAccs.size();
+  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  size_t used = 0;
+  check(dgpu_float_decode_reduce_scaled(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
+                                        (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), f, m.accPtrs.data(),
+                                        m.capacity.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
+        "floatDecompressReduceScaled", true);
+  return (int64_t)used;
+}
+
+// decompress_data_reduce_compress_mixed of the scaled sums (dgpu_float_reduce_compress_scaled).
+std::tuple<at::Tensor, at::Tensor, int64_t> decompress_data_reduce_compress_scaled(
+    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, double scale,
+    bool accumulate, const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus,
+    const std::optional<at::Tensor>& outSizes, const std::optional<at::Tensor>& outCompressed,
+    const std::optional<at::Tensor>& outCompressedSizes) {
+  const float f = checkedScale(scale);
+  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
+  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
+  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tAccs.size();
+  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  at::Tensor comp, sizes;
+  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)m.maxWords), dev,
+                  tAccs[0].device(), comp, sizes);
+  std::vector<void*> compPtrs(n);
+  for (size_t i = 0; i < n; ++i) compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
+  size_t used = 0;
+  check(dgpu_float_reduce_compress_scaled(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
+                                          (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), f, m.accPtrs.data(),
+                                          m.capacity.data(), compPtrs.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes),
+                                          (uint32_t*)sizes.data_ptr(), streamOf(dev)),
+        "floatReduceCompressScaled", true);
+  return {std::move(comp), std::move(sizes), (int64_t)used};
+}
+
 void set_precision(int64_t probBits) {
   TORCH_CHECK(probBits == 9 || probBits == 10 || probBits == 11, "probBits must be 9, 10 or 11");
   tPrecision = (int)probBits;
@@ -852,6 +919,12 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "decompress_data_reduce_compress_mixed(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::decompress_data_reduce_compress_mixed);
+  m.def(
+      "decompress_data_reduce_scaled(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, float scale, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
+      &dietgpu_amd::decompress_data_reduce_scaled);
+  m.def(
+      "decompress_data_reduce_compress_scaled(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, float scale, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
+      &dietgpu_amd::decompress_data_reduce_compress_scaled);
 }
 
 TORCH_LIBRARY(dietgpu, m) {

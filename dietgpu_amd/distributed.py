@@ -6,6 +6,9 @@ so every rank knows the whole batch's layout and (b) reduce timings.
 
 Backend "nccl" is RCCL on ROCm; the same code runs on "gloo" for CPU tests.
 """
+import ctypes
+import inspect
+import math
 import os
 
 import torch
@@ -162,45 +165,47 @@ class GpuFloatCodec:
         ops.decompress_data_accumulate(rows, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype)
         return status
 
-    def decompress_reduce(self, rows_per_acc, accs, accumulate):
+    def decompress_reduce(self, rows_per_acc, accs, accumulate, scale=None):
         """rows_per_acc[i]: equally long lists of rows, summed left to right into (accumulate) or stored as their sum to
-        the float32 tensor accs[i], in ONE launch and all or nothing per accumulator -> status, one per accumulator"""
+        the float32 tensor accs[i], in ONE launch and all or nothing per accumulator -> status, one per accumulator.
+        `scale` (here and in the three methods below): the sums are left multiplied by it, in the same launch"""
         from . import ops
 
         status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
-        ops.decompress_data_reduce(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype)
+        ops.decompress_data_reduce(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype, scale=scale)
         return status
 
-    def decompress_reduce_compress(self, rows_per_acc, accs, accumulate):
+    def decompress_reduce_compress(self, rows_per_acc, accs, accumulate, scale=None):
         """decompress_reduce and compress_cast of the accumulators back to the rows' dtype in ONE call, without the cast's
         histogram pass over the accumulators -> (status, comp, sizes): as the two calls return them"""
         from . import ops
 
         status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
         comp, sizes, _ = ops.decompress_data_reduce_compress(rows_per_acc, accs, accumulate, self.temp_mem, status, None,
-                                                             dtype=self.dtype)
+                                                             dtype=self.dtype, scale=scale)
         return status, comp, sizes
 
     def _mixed_dtype(self, rows_per_acc):
         # (a raw row says what the call's float type is; without one, what the last compress call held)
         return next((t.dtype for rows in rows_per_acc for t in rows if t.dtype != torch.uint8), self.dtype)
 
-    def decompress_reduce_mixed(self, rows_per_acc, accs, accumulate):
+    def decompress_reduce_mixed(self, rows_per_acc, accs, accumulate, scale=None):
         """decompress_reduce whose rows are uint8 archives or UNCOMPRESSED 1-D tensors of the rows' dtype, which are widened
         and added in their place -> status, one per accumulator"""
         from . import ops
 
         status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
-        ops.decompress_data_reduce_mixed(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self._mixed_dtype(rows_per_acc))
+        ops.decompress_data_reduce_mixed(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self._mixed_dtype(rows_per_acc),
+                                         scale=scale)
         return status
 
-    def decompress_reduce_compress_mixed(self, rows_per_acc, accs, accumulate):
+    def decompress_reduce_compress_mixed(self, rows_per_acc, accs, accumulate, scale=None):
         """decompress_reduce_compress with rows as in decompress_reduce_mixed -> (status, comp, sizes)"""
         from . import ops
 
         status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
         comp, sizes, _ = ops.decompress_data_reduce_compress_mixed(rows_per_acc, accs, accumulate, self.temp_mem, status, None,
-                                                                   dtype=self._mixed_dtype(rows_per_acc))
+                                                                   dtype=self._mixed_dtype(rows_per_acc), scale=scale)
         return status, comp, sizes
 
 
@@ -307,7 +312,39 @@ def _rows_with_local(tensor, recv, all_sizes, me, world, raw_local):
     return rows
 
 
-def compressed_reduce_scatter(tensor, codec=None, raw_local=False):
+def _reduce_factor(op, scale, world):
+    """What the sum is multiplied by: (scale or 1) * (1 / world for op "avg"), rounded ONCE to float32 -> that float32
+    value, or None when it is 1.0 (nothing is multiplied and nothing new is asked of the codec)."""
+    if op not in ("sum", "avg"):
+        raise ValueError(f'op must be "sum" or "avg", not {op!r}')
+    f = ctypes.c_float((1.0 if scale is None else float(scale)) * (1.0 / world if op == "avg" else 1.0)).value
+    if not math.isfinite(f) or f == 0.0:
+        raise RuntimeError("the scale of a reduction must be finite and not zero")
+    return None if f == 1.0 else f
+
+
+def _takes_scale(method):
+    """A pluggable codec is asked to scale only by a method that has a `scale` parameter."""
+    try:
+        return "scale" in inspect.signature(method).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+def _reduce_call(method, rows_per_acc, accs, factor):
+    """One reduce call of the codec, accumulate off -> (what it returns, whether `factor` is still to be applied).  Without a
+    factor the call is the three positional arguments it always was."""
+    if factor is not None and _takes_scale(method):
+        return method(rows_per_acc, accs, False, scale=factor), False
+    return method(rows_per_acc, accs, False), factor is not None
+
+
+def _scale_shard(shard, factor):
+    # the same single float32 multiply as the kernel's: a 0-dim float32 factor, so nothing is promoted
+    shard.mul_(torch.tensor(factor, dtype=torch.float32, device=shard.device))
+
+
+def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", scale=None):
     """Reduce-scatter (sum) of a flat float tensor, moving compressed bytes and summing in float32.
 
     `tensor`: this rank's flat fp16 / bf16 / fp32 tensor; its length is a multiple of the world size and the same on
@@ -328,17 +365,26 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False):
     64 ranks: the rank's own shard is neither compressed nor sent to itself nor decoded -- the codec compresses the other
     world - 1 shards (none in a world of one) and the sum takes `tensor.view(world, -1)[me]` as it is, at position `me`
     of the rank order.  The result is bit-identical; stats["payload_bytes"] no longer holds the own row.  Without the
-    method, or in a larger world, the call quietly takes the path above."""
+    method, or in a larger world, the call quietly takes the path above.
+
+    op="avg" divides by the world size and `scale` multiplies by a factor of the caller's: the shard is
+    fl32(sum * f), f = (scale or 1) * (1 / world if op == "avg" else 1) rounded once to float32 -- ONE float32 multiply
+    of the float32 sum, made by the codec's reduce call where its method has a `scale` parameter (GpuFloatCodec: in the
+    reduce kernel, at no extra pass) and by one multiply of the shard otherwise: the same bits either way.  f == 1
+    changes nothing and asks nothing new of the codec."""
     codec = codec or GpuFloatCodec()
     world = dist.get_world_size()
     me = dist.get_rank()
+    factor = _reduce_factor(op, scale, world)
     if raw_local and callable(getattr(codec, "decompress_reduce_mixed", None)) and world <= _MAX_REDUCE_SOURCES:
         shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec, True)
         shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
-        status = codec.decompress_reduce_mixed([_rows_with_local(tensor, recv, all_sizes, me, world, True)], [shard], False)
+        status, pending = _reduce_call(codec.decompress_reduce_mixed, [_rows_with_local(tensor, recv, all_sizes, me, world, True)], [shard], factor)
         if not bool(status.all().item()):
             raise RuntimeError("decode-reduce of the received rows failed: a row is malformed or the rows differ in length; "
                                "the shard was not partly summed")
+        if pending:
+            _scale_shard(shard, factor)
         return shard, {"raw_bytes": tensor.numel() * tensor.element_size(), "wire_bytes": world * width,
                        "payload_bytes": int(all_sizes[me].sum().item())}
     shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec)
@@ -348,7 +394,7 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False):
         raise RuntimeError(f"compressed_reduce_scatter: the codec has no decompress_accumulate, which a world of {world} ranks "
                            f"(more than {_MAX_REDUCE_SOURCES}) or a codec without decompress_reduce needs")
     if has_reduce and world <= _MAX_REDUCE_SOURCES:
-        status = codec.decompress_reduce([[recv[r, : int(all_sizes[r, me])] for r in range(world)]], [shard], False)
+        status, pending = _reduce_call(codec.decompress_reduce, [[recv[r, : int(all_sizes[r, me])] for r in range(world)]], [shard], factor)
         if not bool(status.all().item()):
             raise RuntimeError("decode-reduce of the received rows failed: a row is malformed or the rows differ in length; "
                                "the shard was not partly summed")
@@ -357,6 +403,9 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False):
             status = codec.decompress_accumulate([recv[r, : int(all_sizes[r, me])]], [shard], r != 0)
             if not bool(status.all().item()):
                 raise RuntimeError(f"decode-accumulate of rank {r}'s row failed")
+        pending = factor is not None
+    if pending:
+        _scale_shard(shard, factor)
     stats = {
         "raw_bytes": tensor.numel() * tensor.element_size(),
         "wire_bytes": world * width,
@@ -365,7 +414,7 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False):
     return shard, stats
 
 
-def compressed_all_reduce(tensor, codec=None, raw_local=False):
+def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=None):
     """All-reduce (sum) of a flat fp16 / bf16 tensor, moving compressed bytes both ways and summing in float32.
 
     Three steps: `compressed_reduce_scatter` (this rank's float32 shard of the sum), the codec's `compress_cast` of that
@@ -383,18 +432,27 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False):
 
     raw_local=True: as in compressed_reduce_scatter -- the rank's own shard enters the sum uncompressed.  On the one-call
     path that needs the codec's decompress_reduce_compress_mixed, on the three-step path its decompress_reduce_mixed;
-    without the method the path needs, today's path runs.  Bit-identical either way."""
+    without the method the path needs, today's path runs.  Bit-identical either way.
+
+    op, scale: as in compressed_reduce_scatter -- the mean, or any multiple of the sum, rounded ONCE to the input dtype
+    after the float32 multiply: a mean that is representable does not overflow because the sum would have.  The one-call
+    path is taken with a factor only if the codec's method has a `scale` parameter; otherwise the three-step path runs
+    with the factor in its reduce-scatter.  Bit-identical on every path and rank."""
     if tensor.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError("compressed_all_reduce: the tensor must be float16 or bfloat16")
     codec = codec or GpuFloatCodec()
     world = dist.get_world_size()
-    if callable(getattr(codec, "decompress_reduce_compress", None)) and world <= _MAX_REDUCE_SOURCES:
-        mixed = raw_local and callable(getattr(codec, "decompress_reduce_compress_mixed", None))
+    factor = _reduce_factor(op, scale, world)
+    one_call = callable(getattr(codec, "decompress_reduce_compress", None)) and world <= _MAX_REDUCE_SOURCES
+    mixed = one_call and raw_local and callable(getattr(codec, "decompress_reduce_compress_mixed", None))
+    if one_call:
+        reduce_compress = codec.decompress_reduce_compress_mixed if mixed else codec.decompress_reduce_compress
+        one_call = factor is None or _takes_scale(reduce_compress)
+    if one_call:
         shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec, mixed)
         me = dist.get_rank()
         shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
-        reduce_compress = codec.decompress_reduce_compress_mixed if mixed else codec.decompress_reduce_compress
-        status, comp, sizes = reduce_compress([_rows_with_local(tensor, recv, all_sizes, me, world, mixed)], [shard], False)
+        (status, comp, sizes), _ = _reduce_call(reduce_compress, [_rows_with_local(tensor, recv, all_sizes, me, world, mixed)], [shard], factor)
         if not bool(status.all().item()):
             raise RuntimeError("reduce-compress of the received rows failed: a row is malformed or the rows differ in length")
         rs = {
@@ -403,7 +461,7 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False):
             "payload_bytes": int(all_sizes[me].sum().item()),
         }
     else:
-        shard, rs = compressed_reduce_scatter(tensor, codec, raw_local)
+        shard, rs = compressed_reduce_scatter(tensor, codec, raw_local, scale=factor)
         comp, sizes = codec.compress_cast([shard], tensor.dtype)
     out = torch.empty_like(tensor)
     rows = out.view(world, shard.numel())

@@ -18,6 +18,7 @@ ctypes route (profiles/r03_api_rate.txt) -- `prefer_torch_ops(False)` forces it 
 on both routes).  Either way the work is done by libdietgpu_amd.so: there is no CPU path.
 """
 import ctypes as C
+import math
 import os
 import threading
 
@@ -667,8 +668,18 @@ def decompress_data_accumulate(ts_in, ts_acc, accumulate=True, temp_mem=None, ou
 MAX_REDUCE_SOURCES = 64
 
 
+def _scale32(scale):
+    """The `scale` keyword of the reduce calls -> None (no scale given, or one whose float32 is 1.0: the unscaled call) or
+    the factor rounded ONCE to float32, which must be finite and not zero."""
+    if scale is None:
+        return None
+    f = C.c_float(float(scale)).value
+    _check(math.isfinite(f) and f != 0.0, "scale must be finite and not zero")
+    return None if f == 1.0 else f
+
+
 def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
-                           prob_bits=K_DEFAULT_PRECISION, dtype=None):
+                           prob_bits=K_DEFAULT_PRECISION, dtype=None, scale=None):
     """Sums SEVERAL float archives per accumulator in one launch: ts_in is a list, one entry per accumulator, of equally
     long lists of uint8 CUDA tensors (at most 64 each); ts_acc[i] = ((ts_acc[i] + x0) + x1) + ... with accumulate=True,
     (x0 + x1) + ... with accumulate=False -- the first source is then STORED, the accumulator is never read and no
@@ -678,7 +689,13 @@ def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_s
     All or nothing per accumulator: out_status[i] is 1 only if every source of ts_in[i] is a sound archive of the
     call's float type that fits ts_acc[i] and all of them hold the same number of words; otherwise it is 0 and
     ts_acc[i] keeps every bit it had.  out_sizes[i] is the size the header of ts_in[i][0] states.  `dtype` as in
-    decompress_data_accumulate (given: no host synchronisation; else read from the header of ts_in[0][0])."""
+    decompress_data_accumulate (given: no host synchronisation; else read from the header of ts_in[0][0]).
+
+    `scale`: every word of a successful accumulator is left as fl32(sum * scale) -- one IEEE float32 multiply in the
+    reduce kernel, on the last source's store; with accumulate=True it covers the old contents too.  None, or a value
+    whose float32 is 1.0, is the unscaled call; anything else is rounded once to float32 and must be finite and not
+    zero (RuntimeError)."""
+    scale = _scale32(scale)
     _check(len(ts_in) > 0)
     _check(len(ts_in) == len(ts_acc), "one list of sources per accumulator")
     sources = len(ts_in[0])
@@ -694,6 +711,8 @@ def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_s
         _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
         _check(ta.dtype == torch.float32, "accumulators must be float32")
         _check(ta.numel() <= _U32_MAX)
+    if scale is not None:  # the scaled kernels are forms of the mixed ones, which take all-archive members as well
+        return decompress_data_reduce_mixed(ts_in, ts_acc, accumulate, temp_mem, out_status, out_sizes, prob_bits, dtype, scale=scale)
     n = len(ts_acc)
     _validate_status(out_status, out_sizes, n, dev)
     with torch.cuda.device(dev):
@@ -721,7 +740,8 @@ def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_s
 # ---------------------------------------------------------------- reduce-compress
 # (no reference op: dgpu_float_reduce_compress, include/dietgpu_amd.h)
 def decompress_data_reduce_compress(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
-                                    out_compressed=None, out_compressed_sizes=None, prob_bits=K_DEFAULT_PRECISION, dtype=None):
+                                    out_compressed=None, out_compressed_sizes=None, prob_bits=K_DEFAULT_PRECISION, dtype=None,
+                                    scale=None):
     """`decompress_data_reduce(ts_in, ts_acc, accumulate)` and `compress_data_cast(ts_acc, dtype)` in ONE call: the sums
     land in the float32 accumulators and, rounded to `dtype`, in archives of the sources' own type, without the second
     read of the accumulators that the cast histogram makes -> (comp [n, maxSize] u8, sizes [n] i32, temp bytes used), as
@@ -730,7 +750,9 @@ def decompress_data_reduce_compress(ts_in, ts_acc, accumulate=False, temp_mem=No
     and, for members with out_status 1, the archives are bit for bit what the two calls leave.  A failed member keeps
     its accumulator; its archive is a valid one of whatever the accumulator holds -- look at out_status.  `dtype`:
     float16 or bfloat16, of the sources and of the archives (given: no host synchronisation; else read from the header
-    of ts_in[0][0])."""
+    of ts_in[0][0]).  `scale` as in decompress_data_reduce: the accumulators hold the scaled sums, and the archives are
+    those of the scaled sums, rounded once."""
+    scale = _scale32(scale)
     _check(len(ts_in) > 0)
     _check(len(ts_in) == len(ts_acc), "one list of sources per accumulator")
     sources = len(ts_in[0])
@@ -746,6 +768,9 @@ def decompress_data_reduce_compress(ts_in, ts_acc, accumulate=False, temp_mem=No
         _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
         _check(ta.dtype == torch.float32, "accumulators must be float32")
     _check(dtype is None or dtype in (torch.float16, torch.bfloat16), "dtype (of sources and archives) must be float16 or bfloat16")
+    if scale is not None:  # the scaled kernels are forms of the mixed ones, which take all-archive members as well
+        return decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate, temp_mem, out_status, out_sizes, out_compressed,
+                                                     out_compressed_sizes, prob_bits, dtype, scale=scale)
     n = len(ts_acc)
     _validate_status(out_status, out_sizes, n, dev)
     with torch.cuda.device(dev):
@@ -811,13 +836,15 @@ def _source_kinds(flat):
 
 
 def decompress_data_reduce_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
-                                 prob_bits=K_DEFAULT_PRECISION, dtype=None):
+                                 prob_bits=K_DEFAULT_PRECISION, dtype=None, scale=None):
     """`decompress_data_reduce` whose sources may be UNCOMPRESSED: an entry of ts_in[i] is a uint8 archive or a raw row --
     a 1-D contiguous tensor of the call's float dtype, aligned to its element size only -- which is widened and added in
     its place in source order.  Bit for bit what decompress_data_reduce leaves when every raw row is replaced by its
     archive.  A raw row's numel() counts as the size a header states (all sources equal, at most ts_acc[i].numel(),
     reported in out_sizes[i] when it is the first source).  Raw rows must not overlap the accumulators.  `dtype`: given,
-    else that of the first raw row, else read from the header of the first archive -> temp bytes used (0)."""
+    else that of the first raw row, else read from the header of the first archive -> temp bytes used (0).  `scale` as in
+    decompress_data_reduce."""
+    scale = _scale32(scale)
     flat, sources, dev, ft = _mixed_sources(ts_in, ts_acc, dtype, (torch.float16, torch.bfloat16, torch.float32))
     n = len(ts_acc)
     _validate_status(out_status, out_sizes, n, dev)
@@ -826,6 +853,20 @@ def decompress_data_reduce_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None,
         if ft is None:
             ft = _header_info(True, flat[:1], tp, tb)[1][0]
             _check(ft in _FT_TO_DTYPE, "ts_in[0][0] is not a float archive")
+        if scale is not None:
+            if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_scaled"):
+                torch.ops.dietgpu_amd.set_precision(prob_bits)
+                try:
+                    return torch.ops.dietgpu_amd.decompress_data_reduce_scaled(flat, sources, ts_acc, ft, scale, bool(accumulate),
+                                                                               temp_mem, out_status, out_sizes)
+                finally:
+                    torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+            used = C.c_size_t(0)
+            check(lib().dgpu_float_decode_reduce_scaled(
+                tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
+                _source_kinds(flat), scale, _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), _ptr(out_status),
+                _ptr(out_sizes), _stream()))
+            return int(used.value)
         if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_mixed"):
             torch.ops.dietgpu_amd.set_precision(prob_bits)
             try:
@@ -843,10 +884,11 @@ def decompress_data_reduce_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None,
 
 def decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
                                           out_compressed=None, out_compressed_sizes=None, prob_bits=K_DEFAULT_PRECISION,
-                                          dtype=None):
+                                          dtype=None, scale=None):
     """`decompress_data_reduce_compress` whose sources may be uncompressed rows, as in decompress_data_reduce_mixed (every
     source, raw or not, must hold EXACTLY ts_acc[i].numel() words) -> (comp, sizes, temp bytes used).  `dtype`: float16 or
-    bfloat16."""
+    bfloat16.  `scale` as in decompress_data_reduce_compress."""
+    scale = _scale32(scale)
     flat, sources, dev, ft = _mixed_sources(ts_in, ts_acc, dtype, (torch.float16, torch.bfloat16))
     n = len(ts_acc)
     _validate_status(out_status, out_sizes, n, dev)
@@ -855,7 +897,14 @@ def decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate=False, temp_
         if ft is None:
             ft = _header_info(True, flat[:1], tp, tb)[1][0]
             _check(ft in (_DTYPE_TO_FT[torch.float16], _DTYPE_TO_FT[torch.bfloat16]), "ts_in[0][0] is not a float16 / bfloat16 archive")
-        if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_compress_mixed"):
+        if scale is not None and _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_compress_scaled"):
+            torch.ops.dietgpu_amd.set_precision(prob_bits)
+            try:
+                return torch.ops.dietgpu_amd.decompress_data_reduce_compress_scaled(
+                    flat, sources, ts_acc, ft, scale, bool(accumulate), temp_mem, out_status, out_sizes, out_compressed, out_compressed_sizes)
+            finally:
+                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+        if scale is None and _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_compress_mixed"):
             torch.ops.dietgpu_amd.set_precision(prob_bits)
             try:
                 return torch.ops.dietgpu_amd.decompress_data_reduce_compress_mixed(
@@ -868,6 +917,12 @@ def decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate=False, temp_
         row = comp.size(1)
         out_ptrs = (C.c_void_p * n)(*[comp.data_ptr() + i * row for i in range(n)])
         used = C.c_size_t(0)
+        if scale is not None:
+            check(lib().dgpu_float_reduce_compress_scaled(
+                tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
+                _source_kinds(flat), scale, _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), out_ptrs, _ptr(out_status),
+                _ptr(out_sizes), _ptr(sizes), _stream()))
+            return comp, sizes, int(used.value)
         check(lib().dgpu_float_reduce_compress_mixed(
             tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
             _source_kinds(flat), _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), out_ptrs, _ptr(out_status),

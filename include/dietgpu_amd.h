@@ -69,8 +69,9 @@ const char* dgpu_version(void);
  * point that is only ADDED leaves every existing one as it was and does not move the version: a library without the new
  * symbol fails at load too, by symbol resolution, in anything that links it (dgpu_float_decode_accumulate,
  * dgpu_float_cast_compress, dgpu_float_decode_reduce, dgpu_float_reduce_compress,
- * dgpu_float_reduce_compress_temp_bytes, dgpu_float_rolling_compress, dgpu_float_decode_reduce_mixed and
- * dgpu_float_reduce_compress_mixed were added at version 8). */
+ * dgpu_float_reduce_compress_temp_bytes, dgpu_float_rolling_compress, dgpu_float_decode_reduce_mixed,
+ * dgpu_float_reduce_compress_mixed, dgpu_float_decode_reduce_scaled and dgpu_float_reduce_compress_scaled were added at
+ * version 8). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -488,6 +489,47 @@ int dgpu_float_reduce_compress_mixed(
     uint32_t numInBatch, uint32_t numSources,
     const void* const* in /* [numInBatch * numSources] */, const uint32_t* inBytes /* same shape */,
     const uint8_t* sourceKind /* HOST, same shape: 0 archive, 1 raw */,
+    void* const* acc /* float32, [numInBatch] */, const uint32_t* outCapacity /* float words */,
+    void* const* outArchive /* [numInBatch] */,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev /* words */, uint32_t* outArchiveSize_dev /* bytes */,
+    void* stream);
+
+/* ---- scaled: the mean, or an unscaled sum, in the reduce kernel (no upstream equivalent) --
+ * dgpu_float_decode_reduce_mixed and dgpu_float_reduce_compress_mixed with one float32 factor per call.  Every successful
+ * member is left with
+ *     acc[i] = fl32( U[i] * scale )
+ * where U[i] is, bit for bit, what the unscaled call would have left: ((acc + x0) + x1) + ... with accumulate,
+ * (x0 + x1) + ... without, the widened source for numSources == 1 without.  The product is one IEEE float32 multiply
+ * (__fmul_rn: round to nearest even, denormals kept, never contracted), made where the sum is in registers, on the last
+ * source's store: no pass over the data, no second rounding, and an overflow of the SUM's rounding to the archive type
+ * cannot happen to a mean that is representable.  With accumulate == 1 the factor covers the old accumulator contents too.
+ *   - Reduce-compress rounds and counts the SCALED value: a successful member's archive is byte for byte what
+ *     dgpu_float_cast_compress writes for the scaled accumulator.  The encoder is untouched.
+ *   - Everything else is the contract of the mixed calls: order of the adds, all or nothing per member, outSuccess_dev and
+ *     outSize_dev, a failed member keeps every bit of its accumulator (and gets a decodable flat-table archive), raw
+ *     rows, capacities, temp memory (reduce-compress: within dgpu_float_reduce_compress_temp_bytes), no host
+ *     synchronisation, graph capture after one identical warm call.
+ *   - sourceKind may be NULL: every source is an archive.
+ *   - scale must be finite and not zero: otherwise DGPU_ERR_INVALID_ARGUMENT, with a dgpu_last_error() text, before
+ *     anything is enqueued.
+ *   - scale == 1.0f IS the unscaled call (the mixed one, or with sourceKind NULL the plain one): same kernels, same
+ *     parameter block, no multiply -- a signalling NaN stored by numSources == 1, accumulate == 0 keeps its bits.
+ *   - With any other scale numSources == 1 runs the reducing kernel as well (decode-reduce does not forward to
+ *     decode-accumulate, which does not scale).
+ *   - The scale is a kernel argument and not part of the resident parameter block: calls that differ only in it share
+ *     the block and its cache entry.  A captured call has its scale baked in. */
+int dgpu_float_decode_reduce_scaled(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources,
+    const void* const* in /* [numInBatch * numSources] */, const uint32_t* inBytes /* same shape */,
+    const uint8_t* sourceKind /* HOST, same shape: 0 archive, 1 raw; NULL: all archives */, float scale,
+    void* const* out /* float32, [numInBatch] */, const uint32_t* outCapacity /* float words, [numInBatch] */,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
+int dgpu_float_reduce_compress_scaled(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources,
+    const void* const* in /* [numInBatch * numSources] */, const uint32_t* inBytes /* same shape */,
+    const uint8_t* sourceKind /* HOST, same shape: 0 archive, 1 raw; NULL: all archives */, float scale,
     void* const* acc /* float32, [numInBatch] */, const uint32_t* outCapacity /* float words */,
     void* const* outArchive /* [numInBatch] */,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev /* words */, uint32_t* outArchiveSize_dev /* bytes */,

@@ -54,4 +54,20 @@ inline void floatDecompressReduceMixed(
                   "floatDecompressReduceMixed");
 }
 
+// Scaled decode-reduce: floatDecompressReduceMixed that leaves out[i] = fl32(sum * scale) -- one float32 multiply in the
+// reduce kernel, on the last source's store; with `accumulate` it covers the old contents too.  `sourceKind` may be null
+// (every source an archive); `scale` is finite and not zero, and 1.0f is the unscaled call.
+// dgpu_float_decode_reduce_scaled of ../dietgpu_amd.h.
+inline void floatDecompressReduceScaled(
+    StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, uint32_t numSources,
+    const void** in, const uint32_t* inBytes, const uint8_t* sourceKind, float scale, float** out, const uint32_t* outCapacity,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+  (void)res;
+  size_t used = 0;
+  detail::checkRc(dgpu_float_decode_reduce_scaled(nullptr, 0, &used, (uint32_t)config.floatType, config.ansConfig.probBits,
+                                                  accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, sourceKind, scale,
+                                                  (void* const*)out, outCapacity, outSuccess_dev, outSize_dev, stream),
+                  "floatDecompressReduceScaled");
+}
+
 }  // namespace dietgpu

@@ -44,4 +44,21 @@ inline void floatDecompressReduceCompressMixed(
                   "floatDecompressReduceCompressMixed");
 }
 
+// Scaled reduce-compress: floatDecompressReduceCompressMixed of fl32(sum * scale): the accumulators hold the scaled sums
+// and the archives are those of the scaled sums, rounded once.  `sourceKind` may be null (every source an archive);
+// `scale` is finite and not zero, and 1.0f is the unscaled call.  dgpu_float_reduce_compress_scaled of ../dietgpu_amd.h.
+inline void floatDecompressReduceCompressScaled(
+    StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, uint32_t numSources,
+    const void** in, const uint32_t* inBytes, const uint8_t* sourceKind, float scale, float** acc, const uint32_t* outCapacity,
+    void** outArchive, uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream) {
+  uint32_t maxWords = 0;
+  for (uint32_t i = 0; i < numInBatch; ++i) maxWords = std::max(maxWords, outCapacity[i]);
+  detail::TempRegion t(res, stream, dgpu_float_reduce_compress_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords));
+  detail::checkRc(dgpu_float_reduce_compress_scaled(t.ptr, t.bytes, &t.used, (uint32_t)config.floatType, config.ansConfig.probBits,
+                                                    accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, sourceKind, scale,
+                                                    (void* const*)acc, outCapacity, outArchive, outSuccess_dev, outSize_dev,
+                                                    outArchiveSize_dev, stream),
+                  "floatDecompressReduceCompressScaled");
+}
+
 }  // namespace dietgpu
