@@ -50,6 +50,9 @@ _SIGS = {
     "dgpu_float_reduce_compress_mixed": (i32, [vp, sz, vp, u32, i32, i32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dgpu_float_decode_reduce_scaled": (i32, [vp, sz, vp, u32, i32, i32, u32, u32, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
     "dgpu_float_reduce_compress_scaled": (i32, [vp, sz, vp, u32, i32, i32, u32, u32, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp]),
+    "dgpu_float_reduce_norm_temp_bytes": (sz, [u32, u32, u32, i32]),
+    "dgpu_float_decode_reduce_norm": (i32, [vp, sz, vp, u32, i32, i32, u32, u32, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp]),
+    "dgpu_float_reduce_compress_norm": (i32, [vp, sz, vp, u32, i32, i32, u32, u32, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dgpu_float_compress_stride_capped": (i32, [vp, sz, vp, u32, i32, i32, u32, vp, u32, u32, vp, u32, u32, vp, vp]),
     "dgpu_float_decompress_stride_bounded": (i32, [vp, sz, vp, u32, i32, i32, u32, vp, u32, u32, vp, u32, u32, vp, vp, vp, vp]),
     "dgpu_float_get_compressed_info": (i32, [vp, sz, vp, u32, vp, vp, vp, vp]),

@@ -1538,12 +1538,53 @@ int mixedSourceAddresses(const char* nullMsg, const void* const* in, const uint3
 // scale (dgpu_float_decode_reduce_scaled): other than 1, the launch is k_ans_decode_reduce_mixed_scaled whatever the
 // kinds and for S == 1 too, with the factor as a kernel argument: the parameter block and its cache entry are those of
 // the unscaled call.  1 is the unscaled call.
+// norm (dgpu_float_decode_reduce_norm; either of outSumSq_dev / outNonFinite_dev given): the launch is
+// k_ans_decode_reduce_mixed_norm whatever the kinds and the scale, for S == 1 too, and k_reduce_norm_finish after it
+// (reduceNormBegin / reduceNormFinish).  The tile partials are the only temp memory of a decode-reduce call.
+struct ReduceNorm {
+  double* outSumSq = nullptr;      // [B] device, nullable
+  uint32_t* outNonFinite = nullptr;  // [B] device, nullable
+  void* temp = nullptr;
+  size_t tempBytes = 0;
+  bool wanted() const { return outSumSq != nullptr || outNonFinite != nullptr; }
+};
+// (before anything is enqueued)
+int reduceNormCheck(const ReduceNorm& norm) {
+  DGPU_REQUIRE((uintptr_t)norm.outSumSq % 8u == 0u, "outSumSq_dev must be 8-byte aligned");
+  DGPU_REQUIRE((uintptr_t)norm.outNonFinite % 4u == 0u, "outNonFinite_dev must be 4-byte aligned");
+  return DGPU_OK;
+}
+// The (member, tile) partials of the launch group: carved from the arena, zero when the reduce kernel starts.
+int reduceNormBegin(TempArena& arena, uint32_t B, const LaunchGroup& g, DecodeArgs* d, hipStream_t stream) {
+  const size_t bytes = reduceNormPartialBytes(B, std::max(g.maxTiles, 1u));
+  DGPU_ALLOC(partials, uint8_t, arena, bytes);
+  DGPU_HIP(hipMemsetAsync(partials, 0, bytes, stream));
+  d->normPartials = (double*)partials;
+  return DGPU_OK;
+}
+int reduceNormFinish(const ReduceNorm& norm, uint32_t B, const LaunchGroup& g, const DecodeArgs& d, hipStream_t stream) {
+  ReduceNormFinishArgs f;
+  f.partials = d.normPartials;
+  f.numInBatch = B;
+  f.maxTiles = std::max(g.maxTiles, 1u);
+  f.outSumSq = norm.outSumSq;
+  f.outNonFinite = norm.outNonFinite;
+  DGPU_LAUNCH("k_reduce_norm_finish", stream, k_reduce_norm_finish, dim3(divUp(B, kNormFinishThreads / 64u)), dim3(kNormFinishThreads), 0, stream, f);
+  DGPU_HIP(hipGetLastError());
+  return DGPU_OK;
+}
+
 int decodeReduceImpl(
     size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, uint32_t S, const void* const* in, const uint32_t* inBytes,
     void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream, bool mixed = false,
-    const uint8_t* kinds = nullptr, float scale = 1.0f) {
+    const uint8_t* kinds = nullptr, float scale = 1.0f, const ReduceNorm& norm = ReduceNorm()) {
   DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
-  const bool scaled = scale != 1.0f;
+  const bool withNorm = norm.wanted();
+  const bool scaled = scale != 1.0f || withNorm;  // (neither goes the ways of the plain call)
+  if (withNorm) {
+    const int rcNorm = reduceNormCheck(norm);
+    if (rcNorm) return rcNorm;
+  }
   DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "decode-reduce: accumulate must be 0 or 1");
   DGPU_REQUIRE(S >= 1u && S <= kMaxReduceSources, "decode-reduce: numSources must be between 1 and 64");
   DGPU_REQUIRE((uint64_t)B * S <= 65535u, "decode-reduce: numInBatch * numSources must be <= 65535");
@@ -1580,6 +1621,14 @@ int decodeReduceImpl(
   d.accumulate = (uint32_t)accumulate;
   d.numSources = S;
   d.scale = scale;
+  if (withNorm) {
+    TempArena arena(norm.temp, norm.tempBytes, streamLease);
+    rc = reduceNormBegin(arena, B, groups[0], &d, stream);
+    if (!rc) rc = launchDecode(d, groups[0], dev.work, DecodeForm::kReduceNorm, P, stream);
+    if (!rc) rc = reduceNormFinish(norm, B, groups[0], d, stream);
+    if (tempUsed) *tempUsed = arena.requested();
+    return rc;
+  }
   return launchDecode(d, groups[0], dev.work, scaled ? DecodeForm::kReduceScaled : (anyRaw ? DecodeForm::kReduceMixed : DecodeForm::kReduce), P, stream);
 }
 
@@ -1593,12 +1642,19 @@ int decodeReduceImpl(
 // mixed (dgpu_float_reduce_compress_mixed): as in decodeReduceImpl; the reduce kernel is k_ans_decode_reduce_mixed_stats.
 // scale (dgpu_float_reduce_compress_scaled): as in decodeReduceImpl; the reduce kernel is
 // k_ans_decode_reduce_mixed_stats_scaled, which stores, rounds and counts the scaled sums.  The encoder does not know.
+// norm (dgpu_float_reduce_compress_norm): as in decodeReduceImpl; the reduce kernel is k_ans_decode_reduce_mixed_stats_norm,
+// which measures the sums ROUNDED to the archive type; the partials come out of the call's temp memory like the counts.
 int reduceCompressImpl(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, uint32_t S,
     const void* const* in, const uint32_t* inBytes, void* const* acc, const uint32_t* outCapacity, void* const* outArchive,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream, bool mixed = false,
-    const uint8_t* kinds = nullptr, float scale = 1.0f) {
+    const uint8_t* kinds = nullptr, float scale = 1.0f, const ReduceNorm& norm = ReduceNorm()) {
   DGPU_REQUIRE(ft == kFloat16 || ft == kBFloat16, "reduce-compress: floatType must be float16 or bfloat16 (float32: decode-reduce, then dgpu_float_compress)");
+  const bool withNorm = norm.wanted();
+  if (withNorm) {
+    const int rcNorm = reduceNormCheck(norm);
+    if (rcNorm) return rcNorm;
+  }
   DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "reduce-compress: accumulate must be 0 or 1");
   DGPU_REQUIRE(S >= 1u && S <= kMaxReduceSources, "reduce-compress: numSources must be between 1 and 64");
   DGPU_REQUIRE((uint64_t)B * S <= 65535u, "reduce-compress: numInBatch * numSources must be <= 65535");
@@ -1652,7 +1708,15 @@ int reduceCompressImpl(
   d.numSources = S;
   d.stats = counts;
   d.scale = scale;
-  const DecodeForm form = scale != 1.0f ? DecodeForm::kReduceScaledStats : (anyRaw ? DecodeForm::kReduceMixedStats : DecodeForm::kReduceStats);
+  const DecodeForm form = withNorm ? DecodeForm::kReduceNormStats
+                                   : (scale != 1.0f ? DecodeForm::kReduceScaledStats : (anyRaw ? DecodeForm::kReduceMixedStats : DecodeForm::kReduceStats));
+  if (withNorm) {
+    rc = reduceNormBegin(arena, B, groupsD[0], &d, stream);
+    if (rc) {  // (nothing is launched: the counters are still zero)
+      if (tempUsed) *tempUsed = arena.requested();
+      return rc;
+    }
+  }
   rc = launchDecode(d, groupsD[0], devD.work, form, P, stream);
   if (!rc) {
     EncodeShared shared;
@@ -1661,6 +1725,8 @@ int reduceCompressImpl(
     // (the normalisation may not have been enqueued: the counters are zero at rest whatever happened)
     if (rc && countsAtRest) (void)hipMemsetAsync(countsAtRest, 0, (size_t)B * kNumSymbols * 4, stream);
   }
+  // (after the encoder: its failure handling above stays what it was; the partials are a region of their own, d.normPartials)
+  if (!rc && withNorm) rc = reduceNormFinish(norm, B, groupsD[0], d, stream);
   if (tempUsed) *tempUsed = arena.requested();
   return rc;
 }
@@ -2032,6 +2098,46 @@ int dgpu_float_reduce_compress_scaled(
   return reduceCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, acc,
                             outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream,
                             sourceKind != nullptr, sourceKind, scale);
+}
+
+// ---- norm: the reduce call also reports the squared norm and the non-finite count of what it leaves ----------------
+// (both outputs NULL: the scaled call.  Scale and alignment are checked first: nothing is enqueued for a bad one.)
+size_t dgpu_float_reduce_norm_temp_bytes(uint32_t floatType, uint32_t numInBatch, uint32_t maxWords, int compress) {
+  // (the tiles of the launch, bounded so that the figure never falls as maxWords grows: 8 blocks are two 4-block tiles,
+  // 9 blocks one 16-block tile)
+  const uint32_t blocks = divUp(maxWords, kBlockSize);
+  const uint32_t tiles = std::max({divUp(blocks, kDecBlocksPerTile), std::min(divUp(blocks, kDecBlocksPerSmallTile), 2u), 1u});
+  return alignUp(reduceNormPartialBytes(numInBatch, tiles), kTempAlign) + kTempAlign +
+      (compress ? dgpu_float_reduce_compress_temp_bytes(floatType, numInBatch, maxWords) : 0u);
+}
+
+int dgpu_float_decode_reduce_norm(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, const uint8_t* sourceKind,
+    float scale, void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev,
+    double* outSumSq_dev, uint32_t* outNonFinite_dev, void* stream) {
+  DGPU_REQUIRE(scaleOk(scale), "decode-reduce: scale must be finite and not zero");
+  ReduceNorm norm;
+  norm.outSumSq = outSumSq_dev;
+  norm.outNonFinite = outNonFinite_dev;
+  norm.temp = temp_dev;
+  norm.tempBytes = tempBytes;
+  return decodeReduceImpl(tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, out, outCapacity,
+                          outSuccess_dev, outSize_dev, (hipStream_t)stream, sourceKind != nullptr, sourceKind, scale, norm);
+}
+
+int dgpu_float_reduce_compress_norm(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, const uint8_t* sourceKind,
+    float scale, void* const* acc, const uint32_t* outCapacity, void* const* outArchive, uint8_t* outSuccess_dev,
+    uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, double* outSumSq_dev, uint32_t* outNonFinite_dev, void* stream) {
+  DGPU_REQUIRE(scaleOk(scale), "reduce-compress: scale must be finite and not zero");
+  ReduceNorm norm;
+  norm.outSumSq = outSumSq_dev;
+  norm.outNonFinite = outNonFinite_dev;
+  return reduceCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, acc,
+                            outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream,
+                            sourceKind != nullptr, sourceKind, scale, norm);
 }
 
 // ---- float stride batches with capacities on both sides (the compressed collectives) --------------------

@@ -172,6 +172,9 @@ inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, boo
 //   * DecodeForm::kReduceScaled / kReduceScaledStats: k_ans_decode_reduce_mixed_scaled / _mixed_stats_scaled, the mixed
 //     forms that multiply the last source's store by DecodeArgs::scale; they serve all-archive members too.  The
 //     counting form keeps the factor in LDS behind its bins (decReduceStatsScaledLdsBytes).
+//   * DecodeForm::kReduceNorm / kReduceNormStats: k_ans_decode_reduce_mixed_norm / _mixed_stats_norm, the scaled forms
+//     that also measure the words they leave (DecodeArgs::normPartials) and take a factor of 1 as well; the LDS of the
+//     scaled forms and a ReduceNormTile behind it (decReduceNormLdsBytes).
 inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, DecodeForm form = DecodeForm::kWhole) {
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> DecodeVariant {
     constexpr int kP = decltype(p)::value;
@@ -231,6 +234,23 @@ inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, Dec
         constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
         return {k_ans_decode_reduce_mixed_stats_scaled<kP, kCastFT, kTB>, decThreads(kTB), decReduceStatsScaledLdsBytes(kP, kCastFT, kTB),
                 "k_ans_decode_reduce_mixed_stats_scaled"};
+      };
+      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
+    }
+    if (form == DecodeForm::kReduceNorm) {
+      auto tiled = [](auto tb) -> DecodeVariant {
+        constexpr uint32_t kTB = decltype(tb)::value;
+        constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
+        return {k_ans_decode_reduce_mixed_norm<kP, kAccFT, kTB>, decThreads(kTB), decReduceNormLdsBytes(kP, kAccFT, kTB, false), "k_ans_decode_reduce_mixed_norm"};
+      };
+      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
+    }
+    if (form == DecodeForm::kReduceNormStats) {
+      auto tiled = [](auto tb) -> DecodeVariant {
+        constexpr uint32_t kTB = decltype(tb)::value;
+        constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
+        return {k_ans_decode_reduce_mixed_stats_norm<kP, kCastFT, kTB>, decThreads(kTB), decReduceNormLdsBytes(kP, kCastFT, kTB, true),
+                "k_ans_decode_reduce_mixed_stats_norm"};
       };
       return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
     }

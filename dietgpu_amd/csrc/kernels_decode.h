@@ -75,6 +75,11 @@ struct DecodeArgs {
   // the scaled forms of k_ans_decode_reduce_mixed / _mixed_stats only: acc = fl32(sum * scale) on the last source's store
   // (finite, not zero, not 1: the host launches the unscaled kernels for 1; see decodeReduceTile, kScaled)
   float scale = 1.0f;
+  // the norm forms (k_ans_decode_reduce_mixed_norm / _mixed_stats_norm) only: one partial per (member, tile), slot
+  // b * maxTiles + tile, zero at launch -- the squared norm of the tile's finite measured words and, behind the
+  // numInBatch * maxTiles float64, the counts of its non-finite ones (decodeReduceTile, kNorm); k_reduce_norm_finish
+  // adds a member's partials in tile order
+  double* normPartials = nullptr;
 };
 __device__ __forceinline__ uint64_t decodeInBytes(const DecodeArgs& a, uint32_t b) {
   return a.inBytes ? (uint64_t)a.inBytes[b] : (a.uniformInBytes ? (uint64_t)a.uniformInBytes : ~0ull);
@@ -365,11 +370,16 @@ typedef __attribute__((address_space(3))) float LdsF32w;
 // (__fmul_rn: never contracted)
 __device__ __forceinline__ uint32_t accScale(uint32_t o, float f) { return __builtin_bit_cast(uint32_t, __fmul_rn(__builtin_bit_cast(float, o), f)); }
 
-template <uint32_t FT, uint32_t kSlots = 0, bool kScaledSink = false>
+// kUnitAware (the norm forms, which serve a factor of 1 as well): the counting sink multiplies by a factor other than 1
+// only, so that a factor of 1 leaves the bits of the unscaled call (a multiply by 1 quiets a signalling NaN).  The
+// plain sinks need nothing: their flag is simply not set (reduceScales).
+template <uint32_t FT, uint32_t kSlots = 0, bool kScaledSink = false, bool kUnitAware = false>
 struct AccumSink : AccumBins<kSlots != 0u>, AccumScale<kScaledSink && kSlots == 0u> {  // kFloat16 / kBFloat16
   static_assert(FT == kFloat16 || FT == kBFloat16, "");
   static constexpr bool kStats = kSlots != 0u;
   static constexpr bool kScaled = kScaledSink;
+  static constexpr bool kUnit = kUnitAware;
+  static_assert(!kUnitAware || kScaledSink, "");
   static constexpr uint32_t kStatSlots = kSlots;
   __device__ __forceinline__ bool scales() const {
     if constexpr (kStats) return this->bins != 0u;
@@ -413,7 +423,12 @@ struct AccumSink : AccumBins<kSlots != 0u>, AccumScale<kScaledSink && kSlots == 
   __device__ __forceinline__ void storeWord(uint32_t row, uint32_t h, const AccumPre& p) const {
     const float v = accWiden16<FT>(h);
     uint32_t o = accumulate ? accAdd(p.acc, v) : __builtin_bit_cast(uint32_t, v);
-    if constexpr (kScaled) {
+    if constexpr (kScaled && kStats && kUnit) {
+      if (scales()) {
+        const float f = factor();
+        o = f != 1.0f ? accScale(o, f) : o;
+      }
+    } else if constexpr (kScaled) {
       if (scales()) o = accScale(o, factor());
     }
     streamStore<kNtDecStores>((uint32_t*)&out[row * 32u], o);
@@ -467,7 +482,17 @@ struct AccumSink : AccumBins<kSlots != 0u>, AccumScale<kScaledSink && kSlots == 
       o0[k] = accumulate ? accAdd(p.a0[k], v[k]) : __builtin_bit_cast(uint32_t, v[k]);
       o1[k] = accumulate ? accAdd(p.a1[k], v[4u + k]) : __builtin_bit_cast(uint32_t, v[4u + k]);
     }
-    if constexpr (kScaled) {
+    if constexpr (kScaled && kStats && kUnit) {
+      if (scales()) {
+        const float f = factor();
+        const bool unit = f == 1.0f;
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+          o0[k] = unit ? o0[k] : accScale(o0[k], f);
+          o1[k] = unit ? o1[k] : accScale(o1[k], f);
+        }
+      }
+    } else if constexpr (kScaled) {
       if (scales()) {
         const float f = factor();
 #pragma unroll
@@ -497,11 +522,12 @@ struct AccumSink : AccumBins<kSlots != 0u>, AccumScale<kScaledSink && kSlots == 
   }
 };
 
-template <uint32_t kSlots, bool kScaledSink>
-struct AccumSink<kFloat32, kSlots, kScaledSink> : AccumScale<kScaledSink> {  // row-wise, as RowSink<kFloat32>: 128-byte pieces already
+template <uint32_t kSlots, bool kScaledSink, bool kUnitAware>
+struct AccumSink<kFloat32, kSlots, kScaledSink, kUnitAware> : AccumScale<kScaledSink> {  // row-wise, as RowSink<kFloat32>: 128-byte pieces already
   static_assert(kSlots == 0u, "counting sinks: the 16-bit archive types only");
   static constexpr bool kStats = false;
   static constexpr bool kScaled = kScaledSink;
+  static constexpr bool kUnit = kUnitAware;
   float* out;
   const uint16_t* nc2;
   const uint8_t* nc1;
@@ -875,7 +901,7 @@ __device__ __forceinline__ void decodeBlock(
 // descriptors (8 bytes per block, from the L2, in the round trip of the tile's own descriptor), and no tile of an element
 // with a malformed descriptor stores -- a failing element leaves its accumulator as it was.
 // (kReduce: decodeReduceTile, below)
-enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats };
+enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats, kReduceNorm, kReduceNormStats };
 template <int P, uint32_t FT, uint32_t kTileBlocks, DecodeForm kForm>
 __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccum = kForm == DecodeForm::kAccum;
@@ -1311,6 +1337,97 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
 // The factor is a kernel argument, not part of the parameter block: calls that differ in it alone share the block.  The
 // counting form writes it behind the bins, one float per slot column, when it zeroes them.  A template flag again: every
 // unscaled kernel keeps its code, and scale 1 launches those.
+//
+// kNorm (the *_norm kernels, forms of the scaled ones that also take a factor of 1): when the last source is in the
+// accumulator the workgroup MEASURES the words it left there -- the words of this tile that the sources state, read back
+// through the hand-over that every source change uses, right behind the (non-temporal) stores that left them and not
+// in a later pass over the whole shard; which level of the memory system serves that read has not been measured.
+// (Measuring inside the sinks, in the registers the words are stored from, does not
+// fit: the counting 16-bit form has 128 VGPRs and the scalar file full, and a float64 partial in a per-lane LDS slot
+// beside each store still costs it 3 to 5 VGPRs and a dozen spilled scalars: three waves per SIMD for every pass.)
+// The measured word is the float32 word itself, or in the counting form that word rounded to FT by castRound and widened
+// again: the word of the archive the cast encoder will write, where a finite float32 sum may have become an infinity.
+// A finite measured word adds its square to the thread's float64 partial -- the square of a widened float32 is exact, so
+// the only rounding is the add's -- and any other adds one to the thread's count.  Thread t takes the 16-byte quads t,
+// t + threads, ... of the tile in that order; the partials are added in a fixed tree over the lanes of a wave and then in
+// wave order, and leave as one float64 and one count per (member, tile) with plain stores: the same bits every time,
+// whichever workgroup ran the tile.  A workgroup that returns before the source loop -- a failed member, a tile past the
+// member's end -- stores nothing: the host zeroes the slots before the launch.
+template <uint32_t FT, bool kRounded>
+__device__ __forceinline__ uint32_t normWord(uint32_t o) {  // the float32 bits of the word measured for the stored bits o
+  if constexpr (!kRounded) {
+    return o;
+  } else if constexpr (FT == kBFloat16) {
+    return castRoundHigh<kBFloat16>(o) & 0xffff0000u;
+  } else {
+    return __builtin_bit_cast(uint32_t, accWiden16<kFloat16>(castRound<kFloat16>(o)));
+  }
+}
+template <uint32_t FT, bool kRounded>
+__device__ __forceinline__ void normMeasure(uint32_t o, double& sq, uint32_t& bad) {
+  const uint32_t m = normWord<FT, kRounded>(o);
+  const bool finite = (m & 0x7f800000u) != 0x7f800000u;
+  const double d = (double)__builtin_bit_cast(float, finite ? m : 0u);
+  sq = __fma_rn(d, d, sq);
+  bad += finite ? 0u : 1u;
+}
+__device__ __forceinline__ void reduceHandOver();
+// What the measuring pass of a tile needs, written to LDS by thread 0 before the source loop and read back after it:
+// held in scalars instead, these values live across decodeBlock, where the scalar file is full (each one spills into a
+// VGPR lane: 129 VGPRs in the counting form).
+struct ReduceNormTile {
+  uint64_t words;     // the tile's first accumulator word
+  uint64_t sumSq;     // this (member, tile)'s slot of DecodeArgs::normPartials
+  uint64_t nonFinite; // and of the counts behind them
+  uint32_t numWords;  // words of this tile that the sources state
+  uint32_t pad;
+};
+template <uint32_t FT, bool kRounded, uint32_t kThreads>
+__device__ __forceinline__ void reduceNormTile(const ReduceNormTile* sTile, uint8_t* smem) {
+  constexpr uint32_t kWaves = kThreads / 64u;
+  reduceHandOver();  // the last source is in the accumulator; rings and LUT are free
+  typedef __attribute__((address_space(1))) uint8_t* GlobalBytes;
+  const ReduceNormTile t = *sTile;
+  const uint32_t tileWords = (uint32_t)__builtin_amdgcn_readfirstlane((int)t.numWords);
+  const uint32_t* words = (const uint32_t*)(GlobalBytes)(uintptr_t)t.words;
+  // (the thread's indices are derived here, like the source loop's own: nothing of this lives across decodeBlock)
+  uint32_t tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const uint32_t lane = tid & 63u, wave = tid >> 6;
+  double sq = 0.0;
+  uint32_t bad = 0;
+  const uint32_t quads = tileWords / 4u;
+#pragma unroll 4
+  for (uint32_t q = tid; q < quads; q += kThreads) {
+    const u32x4w v = ((const u32x4w4*)words)[q];
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) normMeasure<FT, kRounded>(v[k], sq, bad);
+  }
+  if (tid < (tileWords & 3u)) normMeasure<FT, kRounded>(words[quads * 4u + tid], sq, bad);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    sq += __shfl_xor(sq, d, 64);
+    bad += __shfl_xor(bad, d, 64);
+  }
+  double* sWaveSq = (double*)smem;
+  uint32_t* sWaveCount = (uint32_t*)(sWaveSq + kWaves);
+  if (lane == 0u) {
+    sWaveSq[wave] = sq;
+    sWaveCount[wave] = bad;
+  }
+  __syncthreads();
+  if (tid == 0u) {
+    double tileSq = sWaveSq[0];
+    uint32_t tileBad = sWaveCount[0];
+#pragma unroll
+    for (uint32_t w = 1; w < kWaves; ++w) {
+      tileSq += sWaveSq[w];
+      tileBad += sWaveCount[w];
+    }
+    *(double*)(GlobalBytes)(uintptr_t)t.sumSq = tileSq;
+    *(uint32_t*)(GlobalBytes)(uintptr_t)t.nonFinite = tileBad;
+  }
+}
 constexpr uintptr_t kReduceRawTag = 1u;
 __device__ __forceinline__ bool reduceIsRaw(const uint8_t* source) { return ((uintptr_t)source & kReduceRawTag) != 0u; }
 typedef uint16_t u16n __attribute__((aligned(2)));
@@ -1402,6 +1519,7 @@ __device__ __forceinline__ void reduceScales(Sink& sink, const DecodeArgs& a, ui
   if constexpr (Sink::kScaled && !Sink::kStats) {
     sink.scale = a.scale;
     sink.scaleLast = reduceCounts(s, a.numSources) ? 1u : 0u;
+    if constexpr (Sink::kUnit) sink.scaleLast = a.scale != 1.0f ? sink.scaleLast : 0u;
   }
 }
 
@@ -1435,11 +1553,12 @@ struct ReduceSource {  // verdict on one source (LDS)
 };
 constexpr uint32_t kMaxReduceSources = 64;
 
-template <int P, uint32_t FT, uint32_t kTileBlocks, bool kStats = false, bool kMixed = false, bool kScaled = false>
+template <int P, uint32_t FT, uint32_t kTileBlocks, bool kStats = false, bool kMixed = false, bool kScaled = false, bool kNorm = false>
 __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
   static_assert(FT != 0u, "decode-reduce: float archives only");
+  static_assert(!kNorm || (kMixed && kScaled), "the norm forms are forms of the scaled mixed kernels");
   constexpr uint32_t kSlots = kStats ? decStatsSlots(kTileBlocks) : 0u;
-  using Sink = AccumSink<FT, kSlots, kScaled>;
+  using Sink = AccumSink<FT, kSlots, kScaled, kNorm>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks), kWaves = kDecThreads / 64u;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint2* sLut = (uint2*)(smem + kTileBlocks * kRingBytes);
@@ -1462,6 +1581,7 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
   if (tile != 0 && (uint64_t)tileFirst * kBlockSize >= capacity) return;  // uniform
   // kStats: the bins lie behind rings, LUT and store buffers; they are zero after the first barrier below
   constexpr uint32_t kBinsAt = kTileBlocks * kRingBytes + decLutBytes(P, kTileBlocks) + kTileBlocks * kXpose;
+  constexpr uint32_t kNormTileAt = kBinsAt + (kStats ? decStatsBinBytes(kTileBlocks) + kSlots * 4u : 0u);  // kNorm: ReduceNormTile
   if constexpr (kStats) {
     for (uint32_t i = tid; i < kNumSymbols * kSlots / 4u; i += kDecThreads) ((uint4*)(smem + kBinsAt))[i] = make_uint4(0u, 0u, 0u, 0u);
     if constexpr (kScaled) {  // the factor, one per slot column behind the bins (AccumSink::factor)
@@ -1523,6 +1643,18 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
   const uint32_t nb = divUp(total, kBlockSize);
   if (tileFirst >= nb && tile != 0) return;  // uniform
   const uint32_t ansOff = ansOffsetInArchive(FT, total);
+  if constexpr (kNorm) {  // for reduceNormTile, behind everything else in LDS (visible after any of the barriers below)
+    if (tid == 0u) {
+      ReduceNormTile t;
+      t.words = (uint64_t)(uintptr_t)((const uint32_t*)a.out.ptr(b) + (size_t)tileFirst * kBlockSize);
+      const size_t slots = (size_t)a.numInBatch * a.maxTiles, at = (size_t)b * a.maxTiles + tile;
+      t.sumSq = (uint64_t)(uintptr_t)(a.normPartials + at);
+      t.nonFinite = (uint64_t)(uintptr_t)((uint32_t*)(a.normPartials + slots) + at);
+      t.numWords = total - tileFirst * kBlockSize < kTileBlocks * kBlockSize ? total - tileFirst * kBlockSize : kTileBlocks * kBlockSize;
+      t.pad = 0u;
+      *(ReduceNormTile*)(smem + kNormTileAt) = t;
+    }
+  }
   {
     // block i of source s must be what an encoder can produce (decodeTile's blockOk)
     bool allBlocksOk = true;
@@ -1690,6 +1822,7 @@ __device__ __forceinline__ void decodeReduceTile(const DecodeArgs& a) {
       if (sum) __hip_atomic_fetch_add(a.stats + (size_t)b * kNumSymbols + c, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+  if constexpr (kNorm) reduceNormTile<FT, kStats, kDecThreads>((const ReduceNormTile*)(smem + kNormTileAt), smem);
 }
 
 // grid = the (element, tile) pairs in the order of DecodeArgs::order
@@ -1755,6 +1888,56 @@ template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce_mixed_stats_scaled(DecodeArgs a) {
   static_assert(FT == kFloat16 || FT == kBFloat16, "the archive types of a cast");
   decodeReduceTile<P, FT, kTileBlocks, true, true, true>(a);
+}
+
+// Norm forms of the two scaled kernels: when a tile's last source is stored, the workgroup also measures what it left --
+// the squared norm of the finite words and the count of the others, per (member, tile), in DecodeArgs::normPartials
+// (decodeReduceTile, kNorm).  They take a factor of 1 too, and then multiply nothing.  LDS: the scaled forms' and a ReduceNormTile.
+__host__ __device__ constexpr uint32_t decReduceNormLdsBytes(int P, uint32_t ft, uint32_t tileBlocks, bool stats) {
+  return (stats ? decReduceStatsScaledLdsBytes(P, ft, tileBlocks) : decLdsBytes(P, ft, tileBlocks)) + (uint32_t)sizeof(ReduceNormTile);
+}
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce_mixed_norm(DecodeArgs a) {
+  decodeReduceTile<P, FT, kTileBlocks, false, true, true, true>(a);
+}
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_reduce_mixed_stats_norm(DecodeArgs a) {
+  static_assert(FT == kFloat16 || FT == kBFloat16, "the archive types of a cast");
+  decodeReduceTile<P, FT, kTileBlocks, true, true, true, true>(a);
+}
+
+// One wavefront per member adds the member's tile partials: lane l those of tiles l, l + 64, ... in tile order, then the
+// fixed tree over the lanes.  A member that failed, or is empty, stored no partial: its slots hold the zeros they were
+// launched with, and so do its results.  Either output may be absent.
+struct ReduceNormFinishArgs {
+  const double* partials;  // DecodeArgs::normPartials
+  uint32_t numInBatch, maxTiles;
+  double* outSumSq;        // [numInBatch] nullable
+  uint32_t* outNonFinite;  // [numInBatch] nullable
+};
+constexpr uint32_t kNormFinishThreads = 256;
+__host__ __device__ constexpr size_t reduceNormPartialBytes(size_t numInBatch, size_t maxTiles) { return numInBatch * maxTiles * 12u; }
+__global__ __launch_bounds__(kNormFinishThreads) void k_reduce_norm_finish(ReduceNormFinishArgs a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t b = blockIdx.x * (kNormFinishThreads / 64u) + (threadIdx.x >> 6);
+  if (b >= a.numInBatch) return;  // wave-uniform
+  const double* partSq = a.partials + (size_t)b * a.maxTiles;
+  const uint32_t* partBad = (const uint32_t*)(a.partials + (size_t)a.numInBatch * a.maxTiles) + (size_t)b * a.maxTiles;
+  double sq = 0.0;
+  uint32_t bad = 0;
+  for (uint32_t t = lane; t < a.maxTiles; t += 64u) {
+    sq += partSq[t];
+    bad += partBad[t];
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    sq += __shfl_xor(sq, d, 64);
+    bad += __shfl_xor(bad, d, 64);
+  }
+  if (lane == 0u) {
+    if (a.outSumSq) a.outSumSq[b] = sq;
+    if (a.outNonFinite) a.outNonFinite[b] = bad;
+  }
 }
 
 }  // namespace dgpu

@@ -856,6 +856,84 @@ std::tuple<at::Tensor, at::Tensor, int64_t> decompress_data_reduce_compress_scal
   return {std::move(comp), std::move(sizes), (int64_t)used};
 }
 
+// The norm ops: the scaled ops that also report, per accumulator, the squared norm (float64) and the non-finite count
+// (int32) of what the call leaves (dgpu_float_decode_reduce_norm, dgpu_float_reduce_compress_norm).  A scale of 1.0 is no
+// scale.  Either output may be absent; with both absent the call is the scaled one.
+namespace {
+void validateNorm(const std::optional<at::Tensor>& outSumSq, const std::optional<at::Tensor>& outNonFinite, int64_t n, int dev) {
+  if (outSumSq) {
+    TORCH_CHECK(outSumSq->scalar_type() == at::ScalarType::Double, "dietgpu: out_sumsq must be a float64 tensor");
+    TORCH_CHECK(outSumSq->dim() == 1 && outSumSq->numel() == n && outSumSq->is_contiguous(), "dietgpu: out_sumsq must be a contiguous tensor with one entry per accumulator");
+    TORCH_CHECK(outSumSq->device().is_cuda() && outSumSq->get_device() == dev, "dietgpu: out_sumsq must be on the GPU of the other tensors");
+  }
+  if (outNonFinite) {
+    TORCH_CHECK(outNonFinite->scalar_type() == at::ScalarType::Int, "dietgpu: out_nonfinite must be an int32 tensor");
+    TORCH_CHECK(outNonFinite->dim() == 1 && outNonFinite->numel() == n && outNonFinite->is_contiguous(), "dietgpu: out_nonfinite must be a contiguous tensor with one entry per accumulator");
+    TORCH_CHECK(outNonFinite->device().is_cuda() && outNonFinite->get_device() == dev, "dietgpu: out_nonfinite must be on the GPU of the other tensors");
+  }
+}
+}  // namespace
+
+int64_t decompress_data_reduce_norm(
+    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, double scale,
+    bool accumulate, const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus,
+    const std::optional<at::Tensor>& outSizes, const std::optional<at::Tensor>& outSumSq, const std::optional<at::Tensor>& outNonFinite) {
+  const float f = checkedScale(scale);
+  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
+  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
+  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType >= (int64_t)DGPU_FLOAT16 && floatType <= (int64_t)DGPU_FLOAT32, "dietgpu: float_type must be 1, 2 or 3");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tAccs.size();
+  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  validateNorm(outSumSq, outNonFinite, (int64_t)n, dev);
+  size_t used = 0;
+  check(dgpu_float_decode_reduce_norm(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
+                                      (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), f, m.accPtrs.data(),
+                                      m.capacity.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes),
+                                      ptrOrNull<double>(outSumSq), ptrOrNull<uint32_t>(outNonFinite), streamOf(dev)),
+        "floatDecompressReduceNorm", true);
+  return (int64_t)used;
+}
+
+std::tuple<at::Tensor, at::Tensor, int64_t> decompress_data_reduce_compress_norm(
+    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, double scale,
+    bool accumulate, const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus,
+    const std::optional<at::Tensor>& outSizes, const std::optional<at::Tensor>& outCompressed,
+    const std::optional<at::Tensor>& outCompressedSizes, const std::optional<at::Tensor>& outSumSq,
+    const std::optional<at::Tensor>& outNonFinite) {
+  const float f = checkedScale(scale);
+  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
+  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
+  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tAccs.size();
+  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  validateNorm(outSumSq, outNonFinite, (int64_t)n, dev);
+  at::Tensor comp, sizes;
+  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)m.maxWords), dev,
+                  tAccs[0].device(), comp, sizes);
+  std::vector<void*> compPtrs(n);
+  for (size_t i = 0; i < n; ++i) compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
+  size_t used = 0;
+  check(dgpu_float_reduce_compress_norm(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
+                                        (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), f, m.accPtrs.data(),
+                                        m.capacity.data(), compPtrs.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes),
+                                        (uint32_t*)sizes.data_ptr(), ptrOrNull<double>(outSumSq), ptrOrNull<uint32_t>(outNonFinite),
+                                        streamOf(dev)),
+        "floatReduceCompressNorm", true);
+  return {std::move(comp), std::move(sizes), (int64_t)used};
+}
+
 void set_precision(int64_t probBits) {
   TORCH_CHECK(probBits == 9 || probBits == 10 || probBits == 11, "probBits must be 9, 10 or 11");
   tPrecision = (int)probBits;
@@ -925,6 +1003,12 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "decompress_data_reduce_compress_scaled(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, float scale, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::decompress_data_reduce_compress_scaled);
+  m.def(
+      "decompress_data_reduce_norm(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, float scale, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None, Tensor? out_sumsq=None, Tensor? out_nonfinite=None) -> int",
+      &dietgpu_amd::decompress_data_reduce_norm);
+  m.def(
+      "decompress_data_reduce_compress_norm(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, float scale, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None, Tensor? out_sumsq=None, Tensor? out_nonfinite=None) -> (Tensor, Tensor, int)",
+      &dietgpu_amd::decompress_data_reduce_compress_norm);
 }
 
 TORCH_LIBRARY(dietgpu, m) {

@@ -165,47 +165,57 @@ class GpuFloatCodec:
         ops.decompress_data_accumulate(rows, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype)
         return status
 
-    def decompress_reduce(self, rows_per_acc, accs, accumulate, scale=None):
+    @staticmethod
+    def _norm_kwargs(norm):
+        # (no `norm`: the call of ops is the one it always was)
+        return {} if norm is None else {"out_sumsq": norm[0], "out_nonfinite": norm[1]}
+
+    def decompress_reduce(self, rows_per_acc, accs, accumulate, scale=None, norm=None):
         """rows_per_acc[i]: equally long lists of rows, summed left to right into (accumulate) or stored as their sum to
         the float32 tensor accs[i], in ONE launch and all or nothing per accumulator -> status, one per accumulator.
-        `scale` (here and in the three methods below): the sums are left multiplied by it, in the same launch"""
+        `scale` (here and in the three methods below): the sums are left multiplied by it, in the same launch.
+        `norm` (here and below): a pair (float64 [len(accs)], int32 [len(accs)]) of tensors that the same launch fills
+        with the squared norm of the finite words it leaves and the count of the others -- of the accumulators here,
+        of the archives in the reduce-compress methods"""
         from . import ops
 
         status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
-        ops.decompress_data_reduce(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype, scale=scale)
+        ops.decompress_data_reduce(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype, scale=scale,
+                                   **self._norm_kwargs(norm))
         return status
 
-    def decompress_reduce_compress(self, rows_per_acc, accs, accumulate, scale=None):
+    def decompress_reduce_compress(self, rows_per_acc, accs, accumulate, scale=None, norm=None):
         """decompress_reduce and compress_cast of the accumulators back to the rows' dtype in ONE call, without the cast's
         histogram pass over the accumulators -> (status, comp, sizes): as the two calls return them"""
         from . import ops
 
         status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
         comp, sizes, _ = ops.decompress_data_reduce_compress(rows_per_acc, accs, accumulate, self.temp_mem, status, None,
-                                                             dtype=self.dtype, scale=scale)
+                                                             dtype=self.dtype, scale=scale, **self._norm_kwargs(norm))
         return status, comp, sizes
 
     def _mixed_dtype(self, rows_per_acc):
         # (a raw row says what the call's float type is; without one, what the last compress call held)
         return next((t.dtype for rows in rows_per_acc for t in rows if t.dtype != torch.uint8), self.dtype)
 
-    def decompress_reduce_mixed(self, rows_per_acc, accs, accumulate, scale=None):
+    def decompress_reduce_mixed(self, rows_per_acc, accs, accumulate, scale=None, norm=None):
         """decompress_reduce whose rows are uint8 archives or UNCOMPRESSED 1-D tensors of the rows' dtype, which are widened
         and added in their place -> status, one per accumulator"""
         from . import ops
 
         status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
         ops.decompress_data_reduce_mixed(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self._mixed_dtype(rows_per_acc),
-                                         scale=scale)
+                                         scale=scale, **self._norm_kwargs(norm))
         return status
 
-    def decompress_reduce_compress_mixed(self, rows_per_acc, accs, accumulate, scale=None):
+    def decompress_reduce_compress_mixed(self, rows_per_acc, accs, accumulate, scale=None, norm=None):
         """decompress_reduce_compress with rows as in decompress_reduce_mixed -> (status, comp, sizes)"""
         from . import ops
 
         status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
         comp, sizes, _ = ops.decompress_data_reduce_compress_mixed(rows_per_acc, accs, accumulate, self.temp_mem, status, None,
-                                                                   dtype=self._mixed_dtype(rows_per_acc), scale=scale)
+                                                                   dtype=self._mixed_dtype(rows_per_acc), scale=scale,
+                                                                   **self._norm_kwargs(norm))
         return status, comp, sizes
 
 
@@ -331,12 +341,45 @@ def _takes_scale(method):
         return False
 
 
-def _reduce_call(method, rows_per_acc, accs, factor):
+def _takes_norm(method):
+    """... and to measure what it leaves only by a method that has a `norm` parameter."""
+    try:
+        return "norm" in inspect.signature(method).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+def _reduce_call(method, rows_per_acc, accs, factor, norm=None):
     """One reduce call of the codec, accumulate off -> (what it returns, whether `factor` is still to be applied).  Without a
-    factor the call is the three positional arguments it always was."""
-    if factor is not None and _takes_scale(method):
-        return method(rows_per_acc, accs, False, scale=factor), False
-    return method(rows_per_acc, accs, False), factor is not None
+    factor the call is the three positional arguments it always was.  `norm`: a pair from _norm_pair, handed to a method
+    that has a `norm` parameter (and leaves the final, scaled words); norm[2] then says that it is filled."""
+    kwargs = {}
+    scaled_here = factor is not None and _takes_scale(method)
+    if scaled_here:
+        kwargs["scale"] = factor
+    if norm is not None and _takes_norm(method) and (factor is None or scaled_here):
+        kwargs["norm"] = (norm[0], norm[1])
+        norm[2] = True
+    return method(rows_per_acc, accs, False, **kwargs), factor is not None and not scaled_here
+
+
+def _norm_pair(device):
+    """[sumsq float64 [1], nonfinite int32 [1], filled by the codec]"""
+    return [torch.zeros((1,), dtype=torch.float64, device=device), torch.zeros((1,), dtype=torch.int32, device=device), False]
+
+
+def _norm_by_torch(norm, words):
+    """The statistic of a codec that does not report it: one pass over `words` -- the squared norm of the finite ones in
+    float64 and the count of the others."""
+    finite = torch.isfinite(words)
+    norm[0].copy_(torch.where(finite, words, torch.zeros((), dtype=words.dtype, device=words.device)).to(torch.float64).square().sum().reshape(1))
+    norm[1].copy_((~finite).sum().to(torch.int32).reshape(1))
+    norm[2] = True
+
+
+def _norm_stats(stats, norm):
+    stats["sumsq"] = norm[0].reshape(())
+    stats["nonfinite"] = norm[1].reshape(())
 
 
 def _scale_shard(shard, factor):
@@ -344,7 +387,7 @@ def _scale_shard(shard, factor):
     shard.mul_(torch.tensor(factor, dtype=torch.float32, device=shard.device))
 
 
-def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", scale=None):
+def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False):
     """Reduce-scatter (sum) of a flat float tensor, moving compressed bytes and summing in float32.
 
     `tensor`: this rank's flat fp16 / bf16 / fp32 tensor; its length is a multiple of the world size and the same on
@@ -371,22 +414,36 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
     fl32(sum * f), f = (scale or 1) * (1 / world if op == "avg" else 1) rounded once to float32 -- ONE float32 multiply
     of the float32 sum, made by the codec's reduce call where its method has a `scale` parameter (GpuFloatCodec: in the
     reduce kernel, at no extra pass) and by one multiply of the shard otherwise: the same bits either way.  f == 1
-    changes nothing and asks nothing new of the codec."""
+    changes nothing and asks nothing new of the codec.
+
+    norm=True: stats gains "sumsq", a 0-dim float64 tensor with the sum of squares of the finite words of the returned
+    float32 shard (exact squares, added in float64), and "nonfinite", a 0-dim int32 tensor with the number of its words
+    that are inf or NaN -- what clipping by global norm and a loss scaler's overflow check need of the shard.  They are
+    filled by the codec's reduce call where its method has a `norm` parameter (GpuFloatCodec: by the reduce kernel), and
+    by one torch pass over the shard otherwise; nothing is read back to the host.  With the default the codec is called
+    exactly as it always was."""
     codec = codec or GpuFloatCodec()
     world = dist.get_world_size()
     me = dist.get_rank()
     factor = _reduce_factor(op, scale, world)
+    pair = _norm_pair(tensor.device) if norm else None
     if raw_local and callable(getattr(codec, "decompress_reduce_mixed", None)) and world <= _MAX_REDUCE_SOURCES:
         shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec, True)
         shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
-        status, pending = _reduce_call(codec.decompress_reduce_mixed, [_rows_with_local(tensor, recv, all_sizes, me, world, True)], [shard], factor)
+        status, pending = _reduce_call(codec.decompress_reduce_mixed, [_rows_with_local(tensor, recv, all_sizes, me, world, True)], [shard], factor,
+                                       pair)
         if not bool(status.all().item()):
             raise RuntimeError("decode-reduce of the received rows failed: a row is malformed or the rows differ in length; "
                                "the shard was not partly summed")
         if pending:
             _scale_shard(shard, factor)
-        return shard, {"raw_bytes": tensor.numel() * tensor.element_size(), "wire_bytes": world * width,
-                       "payload_bytes": int(all_sizes[me].sum().item())}
+        stats = {"raw_bytes": tensor.numel() * tensor.element_size(), "wire_bytes": world * width,
+                 "payload_bytes": int(all_sizes[me].sum().item())}
+        if norm:
+            if not pair[2]:
+                _norm_by_torch(pair, shard)
+            _norm_stats(stats, pair)
+        return shard, stats
     shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec)
     shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
     has_reduce = callable(getattr(codec, "decompress_reduce", None))
@@ -394,7 +451,7 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
         raise RuntimeError(f"compressed_reduce_scatter: the codec has no decompress_accumulate, which a world of {world} ranks "
                            f"(more than {_MAX_REDUCE_SOURCES}) or a codec without decompress_reduce needs")
     if has_reduce and world <= _MAX_REDUCE_SOURCES:
-        status, pending = _reduce_call(codec.decompress_reduce, [[recv[r, : int(all_sizes[r, me])] for r in range(world)]], [shard], factor)
+        status, pending = _reduce_call(codec.decompress_reduce, [[recv[r, : int(all_sizes[r, me])] for r in range(world)]], [shard], factor, pair)
         if not bool(status.all().item()):
             raise RuntimeError("decode-reduce of the received rows failed: a row is malformed or the rows differ in length; "
                                "the shard was not partly summed")
@@ -411,10 +468,14 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
         "wire_bytes": world * width,
         "payload_bytes": int(all_sizes[me].sum().item()),
     }
+    if norm:
+        if not pair[2]:
+            _norm_by_torch(pair, shard)
+        _norm_stats(stats, pair)
     return shard, stats
 
 
-def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=None):
+def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False):
     """All-reduce (sum) of a flat fp16 / bf16 tensor, moving compressed bytes both ways and summing in float32.
 
     Three steps: `compressed_reduce_scatter` (this rank's float32 shard of the sum), the codec's `compress_cast` of that
@@ -437,7 +498,15 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
     op, scale: as in compressed_reduce_scatter -- the mean, or any multiple of the sum, rounded ONCE to the input dtype
     after the float32 multiply: a mean that is representable does not overflow because the sum would have.  The one-call
     path is taken with a factor only if the codec's method has a `scale` parameter; otherwise the three-step path runs
-    with the factor in its reduce-scatter.  Bit-identical on every path and rank."""
+    with the factor in its reduce-scatter.  Bit-identical on every path and rank.
+
+    norm=True: stats gains "sumsq" and "nonfinite" as in compressed_reduce_scatter, but of this rank's shard ROUNDED to
+    the input dtype -- the words of its archive, which are the words of the returned tensor: a float32 sum that rounds
+    to a float16 infinity counts as non-finite -- and "global_sumsq" (0-dim float64) and "global_nonfinite" (0-dim
+    int32), their sums over the ranks from one all-reduce of a float64 [2] tensor: the squared norm and the non-finite
+    count of the tensor this call returns, the same on every rank.  On the one-call path they are filled by the codec's
+    reduce-compress method where it has a `norm` parameter; otherwise by one torch pass over shard.to(dtype).  No host
+    read is added."""
     if tensor.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError("compressed_all_reduce: the tensor must be float16 or bfloat16")
     codec = codec or GpuFloatCodec()
@@ -452,7 +521,8 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
         shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec, mixed)
         me = dist.get_rank()
         shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
-        (status, comp, sizes), _ = _reduce_call(reduce_compress, [_rows_with_local(tensor, recv, all_sizes, me, world, mixed)], [shard], factor)
+        pair = _norm_pair(tensor.device) if norm else None
+        (status, comp, sizes), _ = _reduce_call(reduce_compress, [_rows_with_local(tensor, recv, all_sizes, me, world, mixed)], [shard], factor, pair)
         if not bool(status.all().item()):
             raise RuntimeError("reduce-compress of the received rows failed: a row is malformed or the rows differ in length")
         rs = {
@@ -461,12 +531,22 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
             "payload_bytes": int(all_sizes[me].sum().item()),
         }
     else:
+        pair = _norm_pair(tensor.device) if norm else None
         shard, rs = compressed_reduce_scatter(tensor, codec, raw_local, scale=factor)
         comp, sizes = codec.compress_cast([shard], tensor.dtype)
     out = torch.empty_like(tensor)
     rows = out.view(world, shard.numel())
     _, ag = _all_gather_archives(comp, sizes, lambda r: [rows[r]], shard.numel() * tensor.element_size(), codec)
-    return out, {k: rs[k] + ag[k] for k in rs}
+    stats = {k: rs[k] + ag[k] for k in rs}
+    if norm:
+        if not pair[2]:  # (the words of the archive: the shard rounded as the cast rounds it)
+            _norm_by_torch(pair, shard.to(tensor.dtype))
+        _norm_stats(stats, pair)
+        both = torch.cat([pair[0], pair[1].to(torch.float64)])
+        dist.all_reduce(both)
+        stats["global_sumsq"] = both[0]
+        stats["global_nonfinite"] = both[1].to(torch.int32)
+    return out, stats
 
 
 # ---------------------------------------------------------------------------

@@ -678,8 +678,20 @@ def _scale32(scale):
     return None if f == 1.0 else f
 
 
+def _norm_outputs(out_sumsq, out_nonfinite, n, dev=None):
+    """The `out_sumsq` / `out_nonfinite` keywords of the reduce calls -> whether either is given.  float64 [n] and int32
+    [n], contiguous, on the GPU (`dev` given: on that one).  Dtype and shape are looked at first."""
+    given = [(t, dt, name) for t, dt, name in ((out_sumsq, torch.float64, "out_sumsq"), (out_nonfinite, torch.int32, "out_nonfinite")) if t is not None]
+    for t, dt, name in given:
+        _check(isinstance(t, torch.Tensor) and t.dtype == dt, f"{name} must be a tensor of dtype {str(dt).replace('torch.', '')}")
+        _check(t.dim() == 1 and t.numel() == n and t.is_contiguous(), f"{name} must be a contiguous tensor of shape [{n}], one entry per accumulator")
+    for t, dt, name in given:
+        _check(t.is_cuda and (dev is None or t.get_device() == dev), f"{name} must be on the GPU of the other tensors")
+    return out_sumsq is not None or out_nonfinite is not None
+
+
 def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
-                           prob_bits=K_DEFAULT_PRECISION, dtype=None, scale=None):
+                           prob_bits=K_DEFAULT_PRECISION, dtype=None, scale=None, out_sumsq=None, out_nonfinite=None):
     """Sums SEVERAL float archives per accumulator in one launch: ts_in is a list, one entry per accumulator, of equally
     long lists of uint8 CUDA tensors (at most 64 each); ts_acc[i] = ((ts_acc[i] + x0) + x1) + ... with accumulate=True,
     (x0 + x1) + ... with accumulate=False -- the first source is then STORED, the accumulator is never read and no
@@ -694,8 +706,15 @@ def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_s
     `scale`: every word of a successful accumulator is left as fl32(sum * scale) -- one IEEE float32 multiply in the
     reduce kernel, on the last source's store; with accumulate=True it covers the old contents too.  None, or a value
     whose float32 is 1.0, is the unscaled call; anything else is rounded once to float32 and must be finite and not
-    zero (RuntimeError)."""
+    zero (RuntimeError).
+
+    `out_sumsq` (float64 [n]) / `out_nonfinite` (int32 [n]), either or both: the call also leaves, per accumulator, the
+    sum of squares of the FINITE float32 words it left there (the words the sources state; squares and sum in float64,
+    within relative words * 2**-52 of the exact value) and the number of words that are inf or NaN -- what clipping by
+    global norm and the overflow check of loss scaling otherwise read the shard again for.  A member with out_status 0
+    gets 0.0 and 0.  The same call leaves the same bits every time."""
     scale = _scale32(scale)
+    norm = _norm_outputs(out_sumsq, out_nonfinite, len(ts_acc))
     _check(len(ts_in) > 0)
     _check(len(ts_in) == len(ts_acc), "one list of sources per accumulator")
     sources = len(ts_in[0])
@@ -711,6 +730,9 @@ def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_s
         _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
         _check(ta.dtype == torch.float32, "accumulators must be float32")
         _check(ta.numel() <= _U32_MAX)
+    if norm:  # the norm kernels are forms of the scaled ones
+        return decompress_data_reduce_mixed(ts_in, ts_acc, accumulate, temp_mem, out_status, out_sizes, prob_bits, dtype, scale=scale,
+                                            out_sumsq=out_sumsq, out_nonfinite=out_nonfinite)
     if scale is not None:  # the scaled kernels are forms of the mixed ones, which take all-archive members as well
         return decompress_data_reduce_mixed(ts_in, ts_acc, accumulate, temp_mem, out_status, out_sizes, prob_bits, dtype, scale=scale)
     n = len(ts_acc)
@@ -741,7 +763,7 @@ def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_s
 # (no reference op: dgpu_float_reduce_compress, include/dietgpu_amd.h)
 def decompress_data_reduce_compress(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
                                     out_compressed=None, out_compressed_sizes=None, prob_bits=K_DEFAULT_PRECISION, dtype=None,
-                                    scale=None):
+                                    scale=None, out_sumsq=None, out_nonfinite=None):
     """`decompress_data_reduce(ts_in, ts_acc, accumulate)` and `compress_data_cast(ts_acc, dtype)` in ONE call: the sums
     land in the float32 accumulators and, rounded to `dtype`, in archives of the sources' own type, without the second
     read of the accumulators that the cast histogram makes -> (comp [n, maxSize] u8, sizes [n] i32, temp bytes used), as
@@ -751,8 +773,11 @@ def decompress_data_reduce_compress(ts_in, ts_acc, accumulate=False, temp_mem=No
     its accumulator; its archive is a valid one of whatever the accumulator holds -- look at out_status.  `dtype`:
     float16 or bfloat16, of the sources and of the archives (given: no host synchronisation; else read from the header
     of ts_in[0][0]).  `scale` as in decompress_data_reduce: the accumulators hold the scaled sums, and the archives are
-    those of the scaled sums, rounded once."""
+    those of the scaled sums, rounded once.  `out_sumsq` / `out_nonfinite` as in decompress_data_reduce, but of the words
+    of the ARCHIVES -- the sums rounded to `dtype` -- which is the tensor every rank holds after the all-gather: a float32
+    sum that is finite and rounds to a float16 infinity counts as non-finite."""
     scale = _scale32(scale)
+    norm = _norm_outputs(out_sumsq, out_nonfinite, len(ts_acc))
     _check(len(ts_in) > 0)
     _check(len(ts_in) == len(ts_acc), "one list of sources per accumulator")
     sources = len(ts_in[0])
@@ -768,6 +793,10 @@ def decompress_data_reduce_compress(ts_in, ts_acc, accumulate=False, temp_mem=No
         _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
         _check(ta.dtype == torch.float32, "accumulators must be float32")
     _check(dtype is None or dtype in (torch.float16, torch.bfloat16), "dtype (of sources and archives) must be float16 or bfloat16")
+    if norm:  # the norm kernels are forms of the scaled ones
+        return decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate, temp_mem, out_status, out_sizes, out_compressed,
+                                                     out_compressed_sizes, prob_bits, dtype, scale=scale, out_sumsq=out_sumsq,
+                                                     out_nonfinite=out_nonfinite)
     if scale is not None:  # the scaled kernels are forms of the mixed ones, which take all-archive members as well
         return decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate, temp_mem, out_status, out_sizes, out_compressed,
                                                      out_compressed_sizes, prob_bits, dtype, scale=scale)
@@ -836,23 +865,40 @@ def _source_kinds(flat):
 
 
 def decompress_data_reduce_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
-                                 prob_bits=K_DEFAULT_PRECISION, dtype=None, scale=None):
+                                 prob_bits=K_DEFAULT_PRECISION, dtype=None, scale=None, out_sumsq=None, out_nonfinite=None):
     """`decompress_data_reduce` whose sources may be UNCOMPRESSED: an entry of ts_in[i] is a uint8 archive or a raw row --
     a 1-D contiguous tensor of the call's float dtype, aligned to its element size only -- which is widened and added in
     its place in source order.  Bit for bit what decompress_data_reduce leaves when every raw row is replaced by its
     archive.  A raw row's numel() counts as the size a header states (all sources equal, at most ts_acc[i].numel(),
     reported in out_sizes[i] when it is the first source).  Raw rows must not overlap the accumulators.  `dtype`: given,
-    else that of the first raw row, else read from the header of the first archive -> temp bytes used (0).  `scale` as in
-    decompress_data_reduce."""
+    else that of the first raw row, else read from the header of the first archive -> temp bytes used (0; with the norm
+    outputs, their tile partials).  `scale`, `out_sumsq` and `out_nonfinite` as in decompress_data_reduce."""
     scale = _scale32(scale)
+    norm = _norm_outputs(out_sumsq, out_nonfinite, len(ts_acc))
     flat, sources, dev, ft = _mixed_sources(ts_in, ts_acc, dtype, (torch.float16, torch.bfloat16, torch.float32))
     n = len(ts_acc)
     _validate_status(out_status, out_sizes, n, dev)
+    _norm_outputs(out_sumsq, out_nonfinite, n, dev)
     with torch.cuda.device(dev):
         tp, tb = _temp(temp_mem, dev)
         if ft is None:
             ft = _header_info(True, flat[:1], tp, tb)[1][0]
             _check(ft in _FT_TO_DTYPE, "ts_in[0][0] is not a float archive")
+        if norm:
+            factor = 1.0 if scale is None else scale
+            if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_norm"):
+                torch.ops.dietgpu_amd.set_precision(prob_bits)
+                try:
+                    return torch.ops.dietgpu_amd.decompress_data_reduce_norm(flat, sources, ts_acc, ft, factor, bool(accumulate), temp_mem,
+                                                                             out_status, out_sizes, out_sumsq, out_nonfinite)
+                finally:
+                    torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+            used = C.c_size_t(0)
+            check(lib().dgpu_float_decode_reduce_norm(
+                tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
+                _source_kinds(flat), factor, _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), _ptr(out_status),
+                _ptr(out_sizes), _ptr(out_sumsq), _ptr(out_nonfinite), _stream()))
+            return int(used.value)
         if scale is not None:
             if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_scaled"):
                 torch.ops.dietgpu_amd.set_precision(prob_bits)
@@ -884,19 +930,42 @@ def decompress_data_reduce_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None,
 
 def decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
                                           out_compressed=None, out_compressed_sizes=None, prob_bits=K_DEFAULT_PRECISION,
-                                          dtype=None, scale=None):
+                                          dtype=None, scale=None, out_sumsq=None, out_nonfinite=None):
     """`decompress_data_reduce_compress` whose sources may be uncompressed rows, as in decompress_data_reduce_mixed (every
     source, raw or not, must hold EXACTLY ts_acc[i].numel() words) -> (comp, sizes, temp bytes used).  `dtype`: float16 or
-    bfloat16.  `scale` as in decompress_data_reduce_compress."""
+    bfloat16.  `scale`, `out_sumsq` and `out_nonfinite` as in decompress_data_reduce_compress."""
     scale = _scale32(scale)
+    norm = _norm_outputs(out_sumsq, out_nonfinite, len(ts_acc))
     flat, sources, dev, ft = _mixed_sources(ts_in, ts_acc, dtype, (torch.float16, torch.bfloat16))
     n = len(ts_acc)
     _validate_status(out_status, out_sizes, n, dev)
+    _norm_outputs(out_sumsq, out_nonfinite, n, dev)
     with torch.cuda.device(dev):
         tp, tb = _temp(temp_mem, dev)
         if ft is None:
             ft = _header_info(True, flat[:1], tp, tb)[1][0]
             _check(ft in (_DTYPE_TO_FT[torch.float16], _DTYPE_TO_FT[torch.bfloat16]), "ts_in[0][0] is not a float16 / bfloat16 archive")
+        if norm:
+            factor = 1.0 if scale is None else scale
+            if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_compress_norm"):
+                torch.ops.dietgpu_amd.set_precision(prob_bits)
+                try:
+                    return torch.ops.dietgpu_amd.decompress_data_reduce_compress_norm(
+                        flat, sources, ts_acc, ft, factor, bool(accumulate), temp_mem, out_status, out_sizes, out_compressed,
+                        out_compressed_sizes, out_sumsq, out_nonfinite)
+                finally:
+                    torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+            _, mx = _total_and_max(ts_acc)
+            cols = _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
+            comp, sizes = _validate_out(out_compressed, out_compressed_sizes, n, cols, dev, ts_acc[0].device)
+            row = comp.size(1)
+            out_ptrs = (C.c_void_p * n)(*[comp.data_ptr() + i * row for i in range(n)])
+            used = C.c_size_t(0)
+            check(lib().dgpu_float_reduce_compress_norm(
+                tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
+                _source_kinds(flat), factor, _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), out_ptrs, _ptr(out_status),
+                _ptr(out_sizes), _ptr(sizes), _ptr(out_sumsq), _ptr(out_nonfinite), _stream()))
+            return comp, sizes, int(used.value)
         if scale is not None and _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_compress_scaled"):
             torch.ops.dietgpu_amd.set_precision(prob_bits)
             try:

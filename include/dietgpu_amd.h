@@ -70,7 +70,8 @@ const char* dgpu_version(void);
  * symbol fails at load too, by symbol resolution, in anything that links it (dgpu_float_decode_accumulate,
  * dgpu_float_cast_compress, dgpu_float_decode_reduce, dgpu_float_reduce_compress,
  * dgpu_float_reduce_compress_temp_bytes, dgpu_float_rolling_compress, dgpu_float_decode_reduce_mixed,
- * dgpu_float_reduce_compress_mixed, dgpu_float_decode_reduce_scaled and dgpu_float_reduce_compress_scaled were added at
+ * dgpu_float_reduce_compress_mixed, dgpu_float_decode_reduce_scaled, dgpu_float_reduce_compress_scaled,
+ * dgpu_float_reduce_norm_temp_bytes, dgpu_float_decode_reduce_norm and dgpu_float_reduce_compress_norm were added at
  * version 8). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
@@ -534,6 +535,55 @@ int dgpu_float_reduce_compress_scaled(
     void* const* outArchive /* [numInBatch] */,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev /* words */, uint32_t* outArchiveSize_dev /* bytes */,
     void* stream);
+
+/* ---- norm: the squared norm and the non-finite count of what a reduce call leaves (no upstream equivalent) --
+ * dgpu_float_decode_reduce_scaled and dgpu_float_reduce_compress_scaled with two more outputs per member, for gradient
+ * clipping by global norm and for the overflow check of loss scaling, which otherwise read the reduced shard again:
+ *     outSumSq_dev[i]     float64: the sum of w * w over the FINITE measured words w of member i, each w widened exactly
+ *     outNonFinite_dev[i] uint32:  the number of measured words that are +-inf or NaN
+ *   - The measured words.  Decode-reduce: the float32 words the call leaves in out[i] -- after the last add, after the
+ *     multiply by scale, with accumulate == 1 including the old contents; exactly as many as the member's sources state
+ *     (a prefix of a larger capacity is measured as a prefix).  Reduce-compress: the words of the ARCHIVE -- those float32
+ *     words rounded to floatType by the cast encoder's own rounding, the tensor every rank holds after the all-gather.  A
+ *     float32 sum of 70000 is finite and its float16 rounding is not: reduce-compress counts it non-finite.
+ *   - Precision: the square of a float32 is exact in float64 and the squares are added in float64, so the result lies
+ *     within relative n * 2^-52 of the exact sum over the n measured words, and squares beyond the float32 range stay
+ *     finite.
+ *   - A member with outSuccess_dev[i] == 0, and an empty member, gets 0.0 and 0.
+ *   - Determinism: the same call with the same arguments and library settings leaves the same 64 bits every time,
+ *     whatever the order the workgroups run in (work lists, decoder order): a tile's words are added in a fixed order,
+ *     the tiles of a member in tile order, without floating-point atomics.  Bit equality is NOT promised between calls
+ *     that differ in tile geometry (the largest capacity of the batch) or in probBits; the bound holds for all.
+ *   - Everything else the call leaves -- accumulators, outSuccess_dev, outSize_dev, archives, archive sizes -- is bit for
+ *     bit what the scaled call with the same arguments leaves.
+ *   - scale as in the scaled calls; here 1.0f multiplies nothing either (a signalling NaN keeps its bits).  sourceKind
+ *     may be NULL: every source is an archive.
+ *   - Either output pointer may be NULL and is then not written; with both NULL the call IS the scaled call.
+ *     outSumSq_dev must be 8-byte aligned, outNonFinite_dev 4-byte aligned: otherwise DGPU_ERR_INVALID_ARGUMENT with a
+ *     dgpu_last_error() text, like every argument error before anything is enqueued.
+ *   - Temp memory: one float64 and one uint32 per member and tile, at most
+ *     dgpu_float_reduce_norm_temp_bytes(floatType, numInBatch, max outCapacity, compress) with compress != 0 for
+ *     reduce-compress (whose own temp memory it includes); *tempUsed reports it; too little falls back to library-owned
+ *     overflow memory.  These are the only decode-side calls that use temp memory.
+ *   - No host synchronisation; capturable into a HIP graph after one identical warm call. */
+size_t dgpu_float_reduce_norm_temp_bytes(uint32_t floatType, uint32_t numInBatch, uint32_t maxWords, int compress);
+int dgpu_float_decode_reduce_norm(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources,
+    const void* const* in /* [numInBatch * numSources] */, const uint32_t* inBytes /* same shape */,
+    const uint8_t* sourceKind /* HOST, same shape: 0 archive, 1 raw; NULL: all archives */, float scale,
+    void* const* out /* float32, [numInBatch] */, const uint32_t* outCapacity /* float words, [numInBatch] */,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev,
+    double* outSumSq_dev /* [numInBatch], nullable */, uint32_t* outNonFinite_dev /* [numInBatch], nullable */, void* stream);
+int dgpu_float_reduce_compress_norm(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, uint32_t numSources,
+    const void* const* in /* [numInBatch * numSources] */, const uint32_t* inBytes /* same shape */,
+    const uint8_t* sourceKind /* HOST, same shape: 0 archive, 1 raw; NULL: all archives */, float scale,
+    void* const* acc /* float32, [numInBatch] */, const uint32_t* outCapacity /* float words */,
+    void* const* outArchive /* [numInBatch] */,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev /* words */, uint32_t* outArchiveSize_dev /* bytes */,
+    double* outSumSq_dev /* [numInBatch], nullable */, uint32_t* outNonFinite_dev /* [numInBatch], nullable */, void* stream);
 
 /* ---- float stride batches with capacities (no upstream equivalent) ---------------
  * For exchanging compressed rows at a FIXED width (README.md:68-72,104: compressed collectives): the rows of one

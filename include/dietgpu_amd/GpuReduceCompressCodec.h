@@ -61,4 +61,23 @@ inline void floatDecompressReduceCompressScaled(
                   "floatDecompressReduceCompressScaled");
 }
 
+// Reduce-compress with the norm outputs: floatDecompressReduceCompressScaled that also leaves, per member, the sum of
+// squares (float64) of the finite words of the ARCHIVE -- the sums rounded to config.floatType -- and the number of its
+// words that are inf or NaN; a failed member gets 0.0 and 0.  Either may be null.
+// dgpu_float_reduce_compress_norm of ../dietgpu_amd.h.
+inline void floatReduceCompressNorm(
+    StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, uint32_t numSources,
+    const void** in, const uint32_t* inBytes, const uint8_t* sourceKind, float scale, float** acc, const uint32_t* outCapacity,
+    void** outArchive, uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, double* outSumSq_dev,
+    uint32_t* outNonFinite_dev, hipStream_t stream) {
+  uint32_t maxWords = 0;
+  for (uint32_t i = 0; i < numInBatch; ++i) maxWords = std::max(maxWords, outCapacity[i]);
+  detail::TempRegion t(res, stream, dgpu_float_reduce_norm_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords, 1));
+  detail::checkRc(dgpu_float_reduce_compress_norm(t.ptr, t.bytes, &t.used, (uint32_t)config.floatType, config.ansConfig.probBits,
+                                                  accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, sourceKind, scale,
+                                                  (void* const*)acc, outCapacity, outArchive, outSuccess_dev, outSize_dev,
+                                                  outArchiveSize_dev, outSumSq_dev, outNonFinite_dev, stream),
+                  "floatReduceCompressNorm");
+}
+
 }  // namespace dietgpu
