@@ -18,6 +18,7 @@ from .ops import (  # noqa: F401
     decompress_data,
     decompress_data_accumulate,
     decompress_data_range,
+    decompress_data_scaled,
     decompress_data_reduce,
     decompress_data_reduce_compress,
     decompress_data_reduce_compress_mixed,

@@ -1502,6 +1502,40 @@ int decodeAccumulateImpl(
   return launchDecode(d, groups[0], dev.work, DecodeForm::kAccum, P, stream);
 }
 
+// Scaled decompress (k_ans_decode_scaled): the whole bounded float decode whose every word is multiplied by the member's
+// float32 factor and rounded back to the archive's type before it is stored.  scale_dev: device memory, read by the
+// kernel -- never here -- so the factor may be written by work enqueued before the call, and a captured call follows
+// the value the memory holds at each replay; null: the host float.  One group per call, as decode-accumulate: the
+// rectangle of a whole decode on 16- or 4-block tiles, or the tile list.  No temp memory, no host synchronisation.
+int decodeScaledImpl(
+    size_t* tempUsed, uint32_t ft, int P, uint32_t B, const void* const* in, const uint32_t* inBytes, void* const* out,
+    const uint32_t* outCapacity, float scale, const float* scale_dev, uint32_t scaleStride, uint8_t* outSuccess_dev,
+    uint32_t* outSize_dev, hipStream_t stream) {
+  DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
+  DGPU_REQUIRE(scaleStride <= 1u, "scaled decompress: scaleStride must be 0 (one factor) or 1 (one per member)");
+  DGPU_REQUIRE(scale_dev != nullptr || (std::isfinite(scale) && scale != 0.0f), "scaled decompress: a host scale must be finite and not zero");
+  DGPU_REQUIRE((uintptr_t)scale_dev % 4u == 0u, "scaled decompress: scale_dev must be 4-byte aligned");
+  bool done;
+  int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
+  if (done) return rc;
+  DGPU_REQUIRE(in && inBytes && out && outCapacity, "scaled decompress: null array with numInBatch > 0");
+  Batch b;
+  rc = pointerBatch(&b, B, ptrSide(in, 16, kMsgCompIn), ptrSide(out), outCapacity, inBytes);
+  if (rc) return rc;
+  // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
+  DGPU_REQUIRE(b.maxSize <= 0xfffff000u, "scaled decompress: outCapacity must not exceed 0xfffff000");
+  StreamLease streamLease(stream);
+  DeviceBatch dev;
+  std::vector<LaunchGroup> groups{decodeRectangle(divUp(b.maxSize, kBlockSize), false)};
+  rc = resolveBatch(b, true, streamLease, &dev, [&] { planDecodeCall(planPolicy(), b.sizes, b.maxSize, false, &groups, &b.work); });
+  if (rc) return rc;
+  DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
+  d.scale = scale;
+  d.scalePtr = scale_dev;
+  d.scaleStride = scaleStride;
+  return launchDecode(d, groups[0], dev.work, DecodeForm::kWholeScaled, P, stream);
+}
+
 // The sources of a mixed call (dgpu_float_decode_reduce_mixed, dgpu_float_reduce_compress_mixed): kinds[k] == 0, an
 // archive, 16-byte aligned like every compressed input; 1, a raw row of inBytes[k] / wordBytes words of the float type,
 // word-aligned like a compress input.  A raw row's address enters the parameter block with kReduceRawTag set, which is
@@ -2031,6 +2065,17 @@ int dgpu_float_decode_accumulate(
   (void)tempBytes;
   return decodeAccumulateImpl(tempUsed, floatType, probBits, accumulate, numInBatch, in, inBytes, out, outCapacity,
                               outSuccess_dev, outSize_dev, (hipStream_t)stream);
+}
+
+// ---- scaled decompress (no upstream equivalent) -----------------------------------
+int dgpu_float_decode_scaled(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, uint32_t numInBatch,
+    const void* const* in, const uint32_t* inBytes, void* const* out, const uint32_t* outCapacity, float scale,
+    const float* scale_dev, uint32_t scaleStride, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream) {
+  (void)temp_dev;
+  (void)tempBytes;
+  return decodeScaledImpl(tempUsed, floatType, probBits, numInBatch, in, inBytes, out, outCapacity, scale, scale_dev, scaleStride,
+                          outSuccess_dev, outSize_dev, (hipStream_t)stream);
 }
 
 // ---- decode-reduce (no upstream equivalent) ---------------------------------------

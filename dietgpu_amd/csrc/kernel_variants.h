@@ -175,6 +175,9 @@ inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, boo
 //   * DecodeForm::kReduceNorm / kReduceNormStats: k_ans_decode_reduce_mixed_norm / _mixed_stats_norm, the scaled forms
 //     that also measure the words they leave (DecodeArgs::normPartials) and take a factor of 1 as well; the LDS of the
 //     scaled forms and a ReduceNormTile behind it (decReduceNormLdsBytes).
+//   * DecodeForm::kWholeScaled: k_ans_decode_scaled, the whole decode that multiplies every word by the member's factor
+//     (DecodeArgs::scalePtr / scaleStride / scale); float types only (raw bytes: the float32 form), 16- and 4-block
+//     tiles (there is no scaled form of k_ans_decode_pair), the LDS of the whole form.
 inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, DecodeForm form = DecodeForm::kWhole) {
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> DecodeVariant {
     constexpr int kP = decltype(p)::value;
@@ -251,6 +254,14 @@ inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, Dec
         constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
         return {k_ans_decode_reduce_mixed_stats_norm<kP, kCastFT, kTB>, decThreads(kTB), decReduceNormLdsBytes(kP, kCastFT, kTB, true),
                 "k_ans_decode_reduce_mixed_stats_norm"};
+      };
+      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
+    }
+    if (form == DecodeForm::kWholeScaled) {
+      auto tiled = [](auto tb) -> DecodeVariant {
+        constexpr uint32_t kTB = decltype(tb)::value;
+        constexpr uint32_t kScFT = kFT ? kFT : kFloat32;
+        return {k_ans_decode_scaled<kP, kScFT, kTB>, decThreads(kTB), decScaledLdsBytes(kP, kScFT, kTB), "k_ans_decode_scaled"};
       };
       return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
     }

@@ -80,6 +80,10 @@ struct DecodeArgs {
   // numInBatch * maxTiles float64, the counts of its non-finite ones (decodeReduceTile, kNorm); k_reduce_norm_finish
   // adds a member's partials in tile order
   double* normPartials = nullptr;
+  // k_ans_decode_scaled only: the factor of member b is scalePtr[b * scaleStride] (device memory, read when the kernel
+  // runs; scaleStride 0: one factor for the call, 1: one per member), or `scale` above when scalePtr is null
+  const float* scalePtr = nullptr;
+  uint32_t scaleStride = 0;
 };
 __device__ __forceinline__ uint64_t decodeInBytes(const DecodeArgs& a, uint32_t b) {
   return a.inBytes ? (uint64_t)a.inBytes[b] : (a.uniformInBytes ? (uint64_t)a.uniformInBytes : ~0ull);
@@ -567,6 +571,51 @@ struct AccumSink<kFloat32, kSlots, kScaledSink, kUnitAware> : AccumScale<kScaled
 };
 
 // ---------------------------------------------------------------------------
+// Scaling sinks (k_ans_decode_scaled): RowSink<FT> whose joined word is widened to float32 as in the accumulating sinks,
+// multiplied by the member's factor -- ONE IEEE float32 multiply (accScale) -- and rounded ONCE back to FT (castRound,
+// the cast encoder's rounding: nearest even, float16 denormals produced, overflow to infinity, NaN to a quiet NaN)
+// before it is stored where RowSink stores it; float32 rows store the product.  Loads, staging and the shape of the
+// stores are RowSink's: the wide path scales the lane's 8 joined words in registers and still leaves ONE 16-byte store.
+// The factor is wave-uniform (one per member) and is set by decodeTile, which requests it with the header loads.
+template <uint32_t FT>
+struct ScaledSink : RowSink<FT> {  // kFloat16 / kBFloat16
+  static_assert(FT == kFloat16 || FT == kBFloat16, "");
+  float factor;
+  // h: the 16-bit word of FT in the LOW half -> the scaled word of FT in the low half
+  __device__ __forceinline__ uint32_t scaleWord(uint32_t h) const {
+    return castRound<FT>(accScale(__builtin_bit_cast(uint32_t, accWiden16<FT>(h)), factor));
+  }
+  // two words of FT -> two scaled words of FT
+  __device__ __forceinline__ uint32_t scalePair(uint32_t w) const {
+    if constexpr (FT == kBFloat16) {
+      const uint32_t p0 = accScale(w << 16, factor), p1 = accScale(w & 0xffff0000u, factor);
+      return __builtin_amdgcn_perm(castRoundHigh<kBFloat16>(p1), castRoundHigh<kBFloat16>(p0), 0x07060302u);
+    } else {
+      return __builtin_amdgcn_perm(scaleWord(w >> 16), scaleWord(w & 0xffffu), 0x05040100u);
+    }
+  }
+  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, uint32_t r) const {
+    const uint32_t v = RowSink<FT>::joinWord(e0, r);
+    streamStore<kNtDecStores>(&this->out[row * 32u], (uint16_t)scaleWord(v >> 16));
+  }
+  __device__ __forceinline__ void flushGroup(uint32_t xpose, uint32_t g, uint32_t hl, uint2 ncb) const {
+    u32x4w o = RowSink<FT>::joinGroup(xpose, hl, ncb);
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) o[k] = scalePair(o[k]);
+    u32x4w* dst = (u32x4w*)(this->out - hl + g * 256u + hl * 8u);
+    if (kNtDecStores) __builtin_nontemporal_store(o, dst);
+    else *dst = o;
+  }
+};
+template <>
+struct ScaledSink<kFloat32> : RowSink<kFloat32> {
+  float factor;
+  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, uint32_t r) const {
+    streamStore<kNtDecStores>(&this->out[row * 32u], accScale(RowSink<kFloat32>::joinWord(e0, r), factor));
+  }
+};
+
+// ---------------------------------------------------------------------------
 // Compressed-word ring: 4 chunks of 256 words (512 bytes) per block.  Chunk k of
 // the block's data lives in slot k & 3.  Words are consumed from the top of the
 // block downwards, at most 32 per row = 256 per 8-row group = one chunk per
@@ -876,7 +925,8 @@ __device__ __forceinline__ void decodeBlock(
 }
 
 // One workgroup of the tiled decoder: 32 threads per block of the tile (512 or 128), LDS = word rings + 64-bit LUT.
-// The body of k_ans_decode (DecodeForm::kWhole), k_ans_decode_range (kRanged) and k_ans_decode_accum (kAccum), below.
+// The body of k_ans_decode (DecodeForm::kWhole), k_ans_decode_range (kRanged), k_ans_decode_accum (kAccum) and
+// k_ans_decode_scaled (kWholeScaled), below.
 //
 // kRanged: blocks [firstBlock[b], firstBlock[b] + numBlocks[b]) of element b, clipped to the element's end, and block
 // firstBlock + k goes to out + k * 4096 words: the output buffer holds the range, not the element.
@@ -900,14 +950,20 @@ __device__ __forceinline__ void decodeBlock(
 // outSize are those of the whole decode, with one difference: EVERY tile makes tile 0's check of all the element's block
 // descriptors (8 bytes per block, from the L2, in the round trip of the tile's own descriptor), and no tile of an element
 // with a malformed descriptor stores -- a failing element leaves its accumulator as it was.
+//
+// kWholeScaled: the whole bounded decode of a float archive whose every word is multiplied by the member's float32 factor
+// and rounded back to FT before it is stored (ScaledSink).  Everything else -- checks, success, outSize, the words behind
+// a short element -- is kWhole's.  The factor (DecodeArgs::scalePtr / scaleStride, or the host's DecodeArgs::scale) is
+// wave-uniform and is requested with the header, so it is there long before the first store.
 // (kReduce: decodeReduceTile, below)
-enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats, kReduceNorm, kReduceNormStats };
+enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats, kReduceNorm, kReduceNormStats, kWholeScaled };
 template <int P, uint32_t FT, uint32_t kTileBlocks, DecodeForm kForm>
 __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
-  constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccum = kForm == DecodeForm::kAccum;
-  static_assert(kForm == DecodeForm::kWhole || kForm == DecodeForm::kRanged || kForm == DecodeForm::kAccum, "decode-reduce has a body of its own: decodeReduceTile");
-  static_assert(!kAccum || FT != 0u, "accumulating decode: float archives only");
-  using Sink = std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32>, RowSink<FT>>;
+  constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccum = kForm == DecodeForm::kAccum, kScaledForm = kForm == DecodeForm::kWholeScaled;
+  static_assert(kForm == DecodeForm::kWhole || kForm == DecodeForm::kRanged || kForm == DecodeForm::kAccum || kScaledForm,
+                "decode-reduce has a body of its own: decodeReduceTile");
+  static_assert(!(kAccum || kScaledForm) || FT != 0u, "accumulating and scaled decode: float archives only");
+  using Sink = std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32>, std::conditional_t<kScaledForm, ScaledSink<FT ? FT : kFloat32>, RowSink<FT>>>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks);
   // the LUT-build scratch (cdf, pdf: 2 KiB, read while the LUT is stored) sits in the ring area
   static_assert(kTileBlocks * kRingBytes >= 2048u, "");
@@ -992,6 +1048,8 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   const bool pdfEarly = extentKnown ? (uint64_t)ansOff + ansOverhead(0u) <= inBytes : FT != 0u;
   const bool blockEarly = FT != 0u && inRange && block < nbSpec && (!extentKnown || (uint64_t)ansOff + ansOverhead(nbSpec) <= inBytes);
   const AnsHeader header = *(const AnsHeader*)ans;
+  float factor = 1.0f;  // kScaledForm: the member's factor, in the round trip of the header
+  if constexpr (kScaledForm) factor = a.scalePtr ? a.scalePtr[(size_t)b * a.scaleStride] : a.scale;
   uint2 pdfRaw = make_uint2(0u, 0u);
   if (wave == 0) pdfRaw = *(const uint2*)(pdfEarly ? ans + sizeof(AnsHeader) + 8u * lane : ans);  // pdf[4 lane .. 4 lane + 3]
   uint2 bwMine = *(const uint2*)(blockEarly ? ans + ansBlockWordsOffset(nbSpec) + 8u * block : ans);
@@ -1077,6 +1135,7 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   const uint8_t* gwords = ans + ansOverhead(nb) + 2u * (size_t)start;
   Sink sink;
   if constexpr (kAccum) sink.accumulate = a.accumulate;
+  if constexpr (kScaledForm) sink.factor = factor;
   // (a half without a block points at its wave's first block: its prefetches must stay inside the archive -- kAccum:
   // and inside the accumulator)
   uint32_t sinkBlock = haveBlock ? block : (block & ~1u);
@@ -1843,6 +1902,15 @@ __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_range(De
 template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_accum(DecodeArgs a) {
   decodeTile<P, FT, kTileBlocks, DecodeForm::kAccum>(a);
+}
+
+// Scaled form: grid, order and LDS as k_ans_decode; every word leaves multiplied by the member's factor
+// (DecodeArgs::scalePtr / scaleStride / scale).  Built for the float types, 16- and 4-block tiles.
+__host__ __device__ constexpr uint32_t decScaledLdsBytes(int P, uint32_t ft, uint32_t tileBlocks) { return decLdsBytes(P, ft, tileBlocks); }
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_scaled(DecodeArgs a) {
+  static_assert(FT != 0u, "scaled decode: float archives only");
+  decodeTile<P, FT, kTileBlocks, DecodeForm::kWholeScaled>(a);
 }
 
 // Reducing form: grid and order as k_ans_decode_accum, DecodeArgs::numSources archives per accumulator (decodeReduceTile).

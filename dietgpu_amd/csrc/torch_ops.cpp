@@ -525,6 +525,41 @@ int64_t decompress_data_accumulate(
   return (int64_t)used;
 }
 
+// Scaled decompress (no reference op): the float decode of archive i into ts_out[i] with every word multiplied by a
+// float32 factor before it is stored (dgpu_float_decode_scaled).  scale_dev: a float32 tensor on the tensors' GPU
+// with 1 element (one factor) or one per archive; the kernel reads it, nothing here does.  Without it: `scale`.
+int64_t decompress_data_scaled(
+    const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tOuts, double scale, const std::optional<at::Tensor>& scaleDev,
+    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.size() == tOuts.size());
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tIns.size();
+  DecodeTensors m = marshalDecode(true, tIns, tOuts, dev, [&](size_t i) {
+    TORCH_CHECK(tOuts[i].scalar_type() == tOuts[0].scalar_type(), "dietgpu: outputs must share one float dtype");
+  });
+  const float* factors = nullptr;
+  uint32_t stride = 0;
+  if (scaleDev) {
+    const at::Tensor& s = *scaleDev;
+    TORCH_CHECK(s.device().is_cuda() && s.get_device() == dev && s.is_contiguous() && s.scalar_type() == at::ScalarType::Float,
+                "dietgpu: a tensor scale must be a contiguous float32 tensor on the tensors' GPU");
+    TORCH_CHECK(s.numel() == 1 || s.numel() == (int64_t)n, "dietgpu: a tensor scale holds 1 element or one per archive");
+    factors = (const float*)s.data_ptr();
+    stride = (s.numel() == 1) ? 0u : 1u;
+  }
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  size_t used = 0;
+  check(dgpu_float_decode_scaled(tmp.ptr, tmp.bytes, &used, floatTypeFromDtype(tOuts[0].scalar_type()), precision(), (uint32_t)n,
+                                     m.inPtrs.data(), m.inBytes.data(), m.outPtrs.data(), m.outCapacity.data(), (float)scale, factors,
+                                     stride, ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
+        "floatDecompressScaled", true);
+  return (int64_t)used;
+}
+
 // Decode-reduce (no reference op): num_sources archives per accumulator, ts_in flattened member-major (source s of
 // accumulator i is ts_in[i * num_sources + s]), summed left to right in one launch, all or nothing per accumulator
 // (dgpu_float_decode_reduce).  accumulate = false stores the first source: the accumulators are never read.
@@ -979,6 +1014,9 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "decompress_data_accumulate(Tensor[] ts_in, Tensor[] ts_acc, int float_type, bool accumulate=True, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
       &dietgpu_amd::decompress_data_accumulate);
+  m.def(
+      "decompress_data_scaled(Tensor[] ts_in, Tensor[] ts_out, float scale, Tensor? scale_dev=None, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_decompressed_words=None) -> int",
+      &dietgpu_amd::decompress_data_scaled);
   m.def(
       "decompress_data_reduce(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
       &dietgpu_amd::decompress_data_reduce);

@@ -152,8 +152,15 @@ class GpuFloatCodec:
         comp, sizes, _ = ops.compress_data_cast(tensors, dtype, self.temp_mem)
         return comp, sizes
 
-    def decompress(self, rows, outs):
+    def decompress(self, rows, outs, scale=None):
+        """`scale` (a number, or a float32 tensor of 1 or len(rows) elements on the device): every word is multiplied by
+        it in the decode kernel (ops.decompress_data_scaled); a tensor is never read by the host"""
         status = torch.zeros((len(rows),), dtype=torch.uint8, device=outs[0].device)
+        if scale is not None:
+            from . import ops
+
+            ops.decompress_data_scaled(rows, outs, scale, self.temp_mem, status, None)
+            return status
         self.ops.decompress_data(True, rows, outs, False, self.temp_mem, status, None)
         return status
 
@@ -219,23 +226,43 @@ class GpuFloatCodec:
         return status, comp, sizes
 
 
-def compressed_all_gather(tensors, codec=None):
+def compressed_all_gather(tensors, codec=None, scale=None):
     """All-gathers a list of equally-shaped float tensors per rank, moving compressed bytes.
 
     `tensors`: this rank's list (same count, shapes and dtype on every rank).
     Returns (gathered, stats): gathered[r][i] is rank r's i-th tensor, bit-exact;
     stats = {"raw_bytes", "wire_bytes", "payload_bytes"} per rank-to-rank copy.
     `codec` needs compress(list) -> (uint8 [n, cap], int32 [n]) and
-    decompress(list of uint8 rows, list of outputs) -> uint8 status [n]."""
+    decompress(list of uint8 rows, list of outputs) -> uint8 status [n].
+
+    `scale` (a number or a 0-dim / 1-element float32 tensor on the tensors' device, the same on every rank): every
+    gathered word is delivered as round(fl32(word * scale)) -- one float32 multiply, one rounding to the dtype.  A codec
+    whose `decompress` has a `scale` parameter applies it while it decodes (GpuFloatCodec: in the decode kernel, and a
+    tensor is never read by the host -- the building block for clipping several buckets by one norm); any other codec
+    is decoded as without it, and each output then takes one pass of torch.  None: nothing changes."""
     codec = codec or GpuFloatCodec()
     comp, sizes = codec.compress(tensors)
     raw = sum(t.numel() * t.element_size() for t in tensors)
-    return _all_gather_archives(comp, sizes, lambda r: [torch.empty_like(t) for t in tensors], raw, codec)
+    return _all_gather_archives(comp, sizes, lambda r: [torch.empty_like(t) for t in tensors], raw, codec, scale=scale)
 
 
-def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec):
+def _scaled_decompress(codec, rows, outs, scale):
+    """codec.decompress(rows, outs) with every word multiplied by `scale` (None: the call as it always was)."""
+    if scale is None:
+        return codec.decompress(rows, outs)
+    if _takes_scale(codec.decompress):
+        return codec.decompress(rows, outs, scale=scale)
+    status = codec.decompress(rows, outs)
+    f = torch.as_tensor(scale, dtype=torch.float32, device=outs[0].device).reshape(())
+    for o in outs:
+        o.copy_((o.float() * f).to(o.dtype))
+    return status
+
+
+def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec, scale=None):
     """The exchange of compressed_all_gather for rows that are compressed already: `comp` [n, cap] / `sizes` [n] as a
-    codec's compress returns them; `outs_of(r)` -> the n tensors rank r's rows are decompressed into."""
+    codec's compress returns them; `outs_of(r)` -> the n tensors rank r's rows are decompressed into.  `scale`: see
+    compressed_all_gather."""
     world = dist.get_world_size()
     n = comp.shape[0]
     sizes = sizes.to(torch.int32)
@@ -256,7 +283,7 @@ def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec):
     for r in range(world):
         rows = [gathered_payload[r][i, : int(all_sizes[r, i])] for i in range(n)]
         outs = outs_of(r)
-        status = codec.decompress(rows, outs)
+        status = _scaled_decompress(codec, rows, outs, scale)
         if not bool(status.all().item()):
             raise RuntimeError(f"decompression of rank {r}'s rows failed")
         gathered.append(outs)
@@ -475,7 +502,7 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
     return shard, stats
 
 
-def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False):
+def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False, clip_norm=None):
     """All-reduce (sum) of a flat fp16 / bf16 tensor, moving compressed bytes both ways and summing in float32.
 
     Three steps: `compressed_reduce_scatter` (this rank's float32 shard of the sum), the codec's `compress_cast` of that
@@ -506,9 +533,23 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
     int32), their sums over the ranks from one all-reduce of a float64 [2] tensor: the squared norm and the non-finite
     count of the tensor this call returns, the same on every rank.  On the one-call path they are filled by the codec's
     reduce-compress method where it has a `norm` parameter; otherwise by one torch pass over shard.to(dtype).  No host
-    read is added."""
+    read is added.
+
+    clip_norm (a positive float): the returned tensor is clipped to that 2-norm.  It implies the statistics of norm=True,
+    which describe the UNCLIPPED result (the norm is that of its finite words; "global_nonfinite" is reported as above
+    and whether to take the step stays the caller's decision).  Their all-reduce is made BEFORE the all-gather;
+    coef = min(clip_norm / (sqrt(global_sumsq) + 1e-6), 1.0) -- the formula of torch.nn.utils.clip_grad_norm_ -- is
+    computed in float64 on the device and rounded once to float32, and the all-gather decodes with that factor
+    (compressed_all_gather's `scale`: in the codec's decode kernel where its `decompress` has a `scale` parameter): every
+    word is round(fl32(word * coef)), bit-identical on every rank.  stats["clip_coef"] is the 0-dim float32 tensor.  No
+    pass over the tensor and no host read is added."""
     if tensor.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError("compressed_all_reduce: the tensor must be float16 or bfloat16")
+    if clip_norm is not None:
+        clip_norm = float(clip_norm)
+        if not (math.isfinite(clip_norm) and clip_norm > 0.0):
+            raise RuntimeError("compressed_all_reduce: clip_norm must be a positive finite float")
+        norm = True
     codec = codec or GpuFloatCodec()
     world = dist.get_world_size()
     factor = _reduce_factor(op, scale, world)
@@ -536,6 +577,21 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
         comp, sizes = codec.compress_cast([shard], tensor.dtype)
     out = torch.empty_like(tensor)
     rows = out.view(world, shard.numel())
+    if clip_norm is not None:
+        # the statistics first: the coefficient is known before the gather, whose decode applies it
+        if not pair[2]:  # (the words of the archive: the shard rounded as the cast rounds it)
+            _norm_by_torch(pair, shard.to(tensor.dtype))
+        both = torch.cat([pair[0], pair[1].to(torch.float64)])
+        dist.all_reduce(both)
+        # torch.nn.utils.clip_grad_norm_'s formula, in float64 on the device, rounded once to float32
+        coef = torch.clamp(clip_norm / (both[0].sqrt() + 1e-6), max=1.0).to(torch.float32)
+        _, ag = _all_gather_archives(comp, sizes, lambda r: [rows[r]], shard.numel() * tensor.element_size(), codec, scale=coef)
+        stats = {k: rs[k] + ag[k] for k in rs}
+        _norm_stats(stats, pair)
+        stats["global_sumsq"] = both[0]
+        stats["global_nonfinite"] = both[1].to(torch.int32)
+        stats["clip_coef"] = coef
+        return out, stats
     _, ag = _all_gather_archives(comp, sizes, lambda r: [rows[r]], shard.numel() * tensor.element_size(), codec)
     stats = {k: rs[k] + ag[k] for k in rs}
     if norm:

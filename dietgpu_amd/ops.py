@@ -663,6 +663,59 @@ def decompress_data_accumulate(ts_in, ts_acc, accumulate=True, temp_mem=None, ou
     return int(used.value)
 
 
+# ------------------------------------------------------------- scaled decompress
+# (no reference op: dgpu_float_decode_scaled, include/dietgpu_amd.h)
+def decompress_data_scaled(ts_in, ts_out, scale, temp_mem=None, out_status=None, out_decompressed_words=None,
+                           prob_bits=K_DEFAULT_PRECISION):
+    """decompress_data(True, ts_in, ts_out) whose every word is multiplied by a float32 factor before it is stored:
+    ts_out[i][k] = round_T(fl32(widen(word) * s)) -- one IEEE float32 multiply and one rounding to the tensors' dtype T
+    (nearest even, float16 denormals produced, overflow to infinity; a NaN product is a quiet NaN) -> temp bytes used (0).
+
+    `scale`: a Python number, rounded once to float32, which must be finite and not zero (one whose float32 is 1.0, or
+    None, is the plain decompress_data call); or a float32 CUDA tensor on the tensors' device, contiguous, with 1 element
+    (one factor for the call) or len(ts_in) elements (one per archive).  A tensor is read by the kernel when it runs and
+    never by the host: it may hold any value, it may be the result of work enqueued before this call (a clip
+    coefficient), and a captured call follows the value it holds at each replay.  All ts_out share one float dtype.
+    Status, sizes and the archive checks are decompress_data's.  There is no `checksum`: a checksum covers the stored
+    words of the original tensor, which this call does not leave."""
+    _check(len(ts_in) > 0)
+    _check(len(ts_in) == len(ts_out))
+    n = len(ts_in)
+    if isinstance(scale, torch.Tensor):
+        _check(scale.dtype == torch.float32, "a tensor scale must be float32")
+        _check(scale.numel() in (1, n), "a tensor scale holds 1 element or one per archive")
+        _check(scale.is_cuda and scale.is_contiguous(), "a tensor scale must be a contiguous tensor on the tensors' GPU")
+        host, dev_scale = 1.0, scale
+    else:
+        try:
+            host, dev_scale = _scale32(scale), None
+        except (TypeError, ValueError):
+            raise RuntimeError("scale must be a number or a float32 tensor") from None
+        if host is None:
+            return decompress_data(True, ts_in, ts_out, False, temp_mem, out_status, out_decompressed_words, prob_bits=prob_bits)
+    _check(ts_in[0].is_cuda, "tensors must be on the GPU")
+    dev = ts_in[0].get_device()
+    _check(dev_scale is None or dev_scale.get_device() == dev, "a tensor scale must be on the tensors' GPU")
+    if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_scaled"):
+        # (the op makes the per-tensor checks below itself, and raises RuntimeError like them)
+        torch.ops.dietgpu_amd.set_precision(prob_bits)
+        try:
+            return torch.ops.dietgpu_amd.decompress_data_scaled(ts_in, ts_out, host, dev_scale, temp_mem, out_status,
+                                                                out_decompressed_words)
+        finally:
+            torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+    caps = _decode_capacities(True, ts_in, ts_out, dev, same_dtype=True)
+    _validate_status(out_status, out_decompressed_words, n, dev)
+    with torch.cuda.device(dev):
+        tp, tb = _temp(temp_mem, dev)
+        used = C.c_size_t(0)
+        check(lib().dgpu_float_decode_scaled(
+            tp, tb, C.byref(used), _float_type(ts_out[0]), prob_bits, n, _ptr_array(ts_in), _in_bytes(ts_in),
+            _ptr_array(ts_out), _u32_array(caps), host, _ptr(dev_scale), 0 if dev_scale is None or dev_scale.numel() == 1 else 1,
+            _ptr(out_status), _ptr(out_decompressed_words), _stream()))
+    return int(used.value)
+
+
 # ------------------------------------------------------------------ decode-reduce
 # (no reference op: dgpu_float_decode_reduce, include/dietgpu_amd.h)
 MAX_REDUCE_SOURCES = 64

@@ -71,8 +71,8 @@ const char* dgpu_version(void);
  * dgpu_float_cast_compress, dgpu_float_decode_reduce, dgpu_float_reduce_compress,
  * dgpu_float_reduce_compress_temp_bytes, dgpu_float_rolling_compress, dgpu_float_decode_reduce_mixed,
  * dgpu_float_reduce_compress_mixed, dgpu_float_decode_reduce_scaled, dgpu_float_reduce_compress_scaled,
- * dgpu_float_reduce_norm_temp_bytes, dgpu_float_decode_reduce_norm and dgpu_float_reduce_compress_norm were added at
- * version 8). */
+ * dgpu_float_reduce_norm_temp_bytes, dgpu_float_decode_reduce_norm, dgpu_float_reduce_compress_norm and
+ * dgpu_float_decode_scaled were added at version 8). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -308,6 +308,40 @@ int dgpu_float_decode_accumulate(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
     uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
     void* const* out /* float32 */, const uint32_t* outCapacity /* float words */,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
+
+/* ---- scaled decompress (no upstream equivalent) ---------------------------------------
+ * dgpu_float_decompress_bounded (useChecksum = 0) that multiplies every word by a float32 factor before it stores it:
+ * the decode of the final all-gather of a compressed all-reduce applies the clip coefficient, which is known only
+ * after the reduce, without a second pass over the tensor and without the host ever reading the coefficient.
+ *   - For member i with factor s and the archive's type T: out[i][k] = round_T(fl32(widen(word_k) * s)).  Widening is
+ *     exact, as in dgpu_float_decode_accumulate; ONE IEEE float32 multiply, round to nearest even, denormals kept, not
+ *     contracted; ONE rounding to T as in dgpu_float_cast_compress (nearest even, float16 denormals produced, overflow
+ *     to infinity, the sign of zero kept); float32 archives store the product.  A NaN product is stored as a quiet NaN
+ *     of T, never as an infinity; its sign and payload are the platform's.
+ *   - The factor: scale_dev != NULL points at DEVICE memory, 4-byte aligned, of 1 float (scaleStride == 0: one factor
+ *     for the call) or numInBatch floats (scaleStride == 1: member i takes scale_dev[i]).  It is read when the kernel
+ *     runs and never by the host, so it may be the result of work enqueued earlier on the stream, and a captured call
+ *     follows the value the memory holds at each replay.  It may hold ANY value, and the arithmetic above is the
+ *     contract for all of them (0 gives signed zeros for finite words; +-inf gives +-inf for non-zero words and NaN for
+ *     zeros; 1 gives back the bits of every word that is not a NaN).  scale_dev == NULL: the host float `scale`, which
+ *     must be finite and not zero.
+ *   - Everything else is the whole bounded float decode: the archive checks, outSuccess_dev / outSize_dev, a capacity
+ *     larger than the element leaves the words behind the element untouched, a member of another float type or with a
+ *     malformed archive gets outSuccess_dev[i] = 0 and does not disturb the others.
+ *   - floatType must be DGPU_FLOAT16, DGPU_BFLOAT16 or DGPU_FLOAT32, probBits 9, 10 or 11, scaleStride 0 or 1,
+ *     in[i] 16-byte aligned, out[i] as dgpu_float_decompress_bounded takes it, outCapacity[i] <= 0xfffff000, no array
+ *     null when numInBatch > 0: DGPU_ERR_INVALID_ARGUMENT otherwise, before anything is enqueued.
+ *   - There is no useChecksum: a checksum covers the stored words of the original tensor, which this call does not
+ *     leave.  Archives written with one decode normally; the checksum is ignored.
+ *   - One kernel geometry per call, from its largest capacity (single-block members run on the 4-block tiles).
+ *   - No temp memory is used (*tempUsed = 0) and nothing synchronises: capturable into a HIP graph under the same
+ *     conditions as the other pointer-array decode calls (the arrays resident from an earlier identical call). */
+int dgpu_float_decode_scaled(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits,
+    uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
+    void* const* out, const uint32_t* outCapacity /* float words */,
+    float scale, const float* scale_dev /* nullable: the host float is used */, uint32_t scaleStride /* 0 or 1 */,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
 
 /* ---- decode-reduce (no upstream equivalent) ------------------------------------------
