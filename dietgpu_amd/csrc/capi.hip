@@ -1474,78 +1474,14 @@ int decodeRangeImpl(
   return launchDecode(d, group, dev.work, DecodeForm::kRanged, P, stream);
 }
 
-// Decode-accumulate (k_ans_decode_accum): every archive widened to float32 and stored to (accumulate == 0) or added into
-// (1) its float32 accumulator.  One group per call: the rectangle of a whole decode, or the tile list when the
-// capacities differ widely.  No temp memory, no host synchronisation.
-int decodeAccumulateImpl(
-    size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, const void* const* in, const uint32_t* inBytes,
-    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
-  DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
-  DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "decode-accumulate: accumulate must be 0 or 1");
-  bool done;
-  int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
-  if (done) return rc;
-  DGPU_REQUIRE(in && inBytes && out && outCapacity, "decode-accumulate: null array with numInBatch > 0");
-  Batch b;
-  rc = pointerBatch(&b, B, ptrSide(in, 16, kMsgCompIn), ptrSide(out, 4, "decode-accumulate: accumulators must be 4-byte aligned"), outCapacity,
-                    inBytes);
-  if (rc) return rc;
-  // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
-  DGPU_REQUIRE(b.maxSize <= 0xfffff000u, "decode-accumulate: outCapacity must not exceed 0xfffff000");
-  StreamLease streamLease(stream);
-  DeviceBatch dev;
-  std::vector<LaunchGroup> groups{decodeRectangle(divUp(b.maxSize, kBlockSize), false)};
-  rc = resolveBatch(b, true, streamLease, &dev, [&] { planDecodeCall(planPolicy(), b.sizes, b.maxSize, false, &groups, &b.work); });
-  if (rc) return rc;
-  DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
-  d.accumulate = (uint32_t)accumulate;
-  return launchDecode(d, groups[0], dev.work, DecodeForm::kAccum, P, stream);
-}
-
-// Scaled decompress (k_ans_decode_scaled): the whole bounded float decode whose every word is multiplied by the member's
-// float32 factor and rounded back to the archive's type before it is stored.  scale_dev: device memory, read by the
-// kernel -- never here -- so the factor may be written by work enqueued before the call, and a captured call follows
-// the value the memory holds at each replay; null: the host float.  One group per call, as decode-accumulate: the
-// rectangle of a whole decode on 16- or 4-block tiles, or the tile list.  No temp memory, no host synchronisation.
-int decodeScaledImpl(
-    size_t* tempUsed, uint32_t ft, int P, uint32_t B, const void* const* in, const uint32_t* inBytes, void* const* out,
-    const uint32_t* outCapacity, float scale, const float* scale_dev, uint32_t scaleStride, uint8_t* outSuccess_dev,
-    uint32_t* outSize_dev, hipStream_t stream) {
-  DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
-  DGPU_REQUIRE(scaleStride <= 1u, "scaled decompress: scaleStride must be 0 (one factor) or 1 (one per member)");
-  DGPU_REQUIRE(scale_dev != nullptr || (std::isfinite(scale) && scale != 0.0f), "scaled decompress: a host scale must be finite and not zero");
-  DGPU_REQUIRE((uintptr_t)scale_dev % 4u == 0u, "scaled decompress: scale_dev must be 4-byte aligned");
-  bool done;
-  int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
-  if (done) return rc;
-  DGPU_REQUIRE(in && inBytes && out && outCapacity, "scaled decompress: null array with numInBatch > 0");
-  Batch b;
-  rc = pointerBatch(&b, B, ptrSide(in, 16, kMsgCompIn), ptrSide(out), outCapacity, inBytes);
-  if (rc) return rc;
-  // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
-  DGPU_REQUIRE(b.maxSize <= 0xfffff000u, "scaled decompress: outCapacity must not exceed 0xfffff000");
-  StreamLease streamLease(stream);
-  DeviceBatch dev;
-  std::vector<LaunchGroup> groups{decodeRectangle(divUp(b.maxSize, kBlockSize), false)};
-  rc = resolveBatch(b, true, streamLease, &dev, [&] { planDecodeCall(planPolicy(), b.sizes, b.maxSize, false, &groups, &b.work); });
-  if (rc) return rc;
-  DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
-  d.scale = scale;
-  d.scalePtr = scale_dev;
-  d.scaleStride = scaleStride;
-  return launchDecode(d, groups[0], dev.work, DecodeForm::kWholeScaled, P, stream);
-}
-
 // The sources of a mixed call (dgpu_float_decode_reduce_mixed, dgpu_float_reduce_compress_mixed): kinds[k] == 0, an
 // archive, 16-byte aligned like every compressed input; 1, a raw row of inBytes[k] / wordBytes words of the float type,
 // word-aligned like a compress input.  A raw row's address enters the parameter block with kReduceRawTag set, which is
 // how the kernel tells the two apart (kernels_decode.h) and why a call that differs from a warm one in its kinds alone
 // hashes to another block.  *anyRaw: false = the batch, and its block, are those of the plain call.
-int mixedSourceAddresses(const char* nullMsg, const void* const* in, const uint32_t* inBytes, const uint8_t* kinds, uint32_t n, uint32_t wordBytes,
+int mixedSourceAddresses(const void* const* in, const uint32_t* inBytes, const uint8_t* kinds, uint32_t n, uint32_t wordBytes,
                          std::vector<uint64_t>* addr, bool* anyRaw) {
-  DGPU_REQUIRE(kinds, nullMsg);
   addr->resize(n);
-  *anyRaw = false;
   for (uint32_t k = 0; k < n; ++k) {
     const uint64_t at = (uint64_t)(uintptr_t)in[k];
     DGPU_REQUIRE(kinds[k] <= 1u, "sourceKind must be 0 (archive) or 1 (raw row)");
@@ -1562,19 +1498,92 @@ int mixedSourceAddresses(const char* nullMsg, const void* const* in, const uint3
   return DGPU_OK;
 }
 
-// Decode-reduce (k_ans_decode_reduce): S = numSources archives per float32 accumulator, summed left to right in one
-// launch, all or nothing per member.  The batch carries B * S archive pointers and inBytes (member-major) beside B
-// accumulators and capacities; the parameter block holds every one of them, so its hash -- the parameter-cache key --
-// covers each source pointer and size, and S through the block's length and layout.  The launch plan is that of a
-// decode-accumulate call with the same capacities.  No temp memory, no host synchronisation.
-// mixed (dgpu_float_decode_reduce_mixed): `kinds` says which sources are raw rows (mixedSourceAddresses); with one
-// among them the launch is k_ans_decode_reduce_mixed, for S == 1 too; with none the call is the plain one from here on.
-// scale (dgpu_float_decode_reduce_scaled): other than 1, the launch is k_ans_decode_reduce_mixed_scaled whatever the
-// kinds and for S == 1 too, with the factor as a kernel argument: the parameter block and its cache entry are those of
-// the unscaled call.  1 is the unscaled call.
-// norm (dgpu_float_decode_reduce_norm; either of outSumSq_dev / outNonFinite_dev given): the launch is
-// k_ans_decode_reduce_mixed_norm whatever the kinds and the scale, for S == 1 too, and k_reduce_norm_finish after it
-// (reduceNormBegin / reduceNormFinish).  The tile partials are the only temp memory of a decode-reduce call.
+// The batch of a float pointer-decode call with S sources per output: B * S inputs and inBytes (member-major) beside B
+// outputs and capacities -- pointerBatch for S == 1.  kinds: null, every input is an archive; else mixedSourceAddresses.
+// The parameter block holds every input, so its hash -- the parameter-cache key -- covers each source pointer and size,
+// and S through the block's length and layout.  tooLarge: the refusal of a capacity whose blocks would round up to 2^32
+// symbols (the tiles are planned in symbols, 32 bits); null: the caller has a tighter bound of its own.
+int floatDecodeBatch(Batch* b, uint32_t ft, uint32_t B, uint32_t S, const void* const* in, const uint32_t* inBytes, const uint8_t* kinds,
+                     const Side& out, const uint32_t* outCapacity, const char* tooLarge, bool* anyRaw = nullptr) {
+  int rc = kinds ? mixedSourceAddresses(in, inBytes, kinds, B * S, floatWordBytes(ft), &b->inPtrs, anyRaw)
+                 : sideAddresses(ptrSide(in, 16, kMsgCompIn), B * S, &b->inPtrs);
+  if (!rc) rc = sideAddresses(out, B, &b->outPtrs);
+  if (rc) return rc;
+  b->n = B;
+  b->sizes.assign(outCapacity, outCapacity + B);
+  b->inBytes.assign(inBytes, inBytes + (size_t)B * S);
+  for (uint32_t i = 0; i < B; ++i) b->maxSize = std::max(b->maxSize, outCapacity[i]);
+  DGPU_REQUIRE(!tooLarge || b->maxSize <= 0xfffff000u, tooLarge);
+  return DGPU_OK;
+}
+
+// The one launch group of such a call -- the rectangle of a whole decode on 16- or 4-block tiles, or the tile list when
+// the capacities differ widely -- and the batch resolved with it.
+int planFloatDecode(Batch& b, StreamLease& streamLease, DeviceBatch* dev, LaunchGroup* group) {
+  std::vector<LaunchGroup> groups{decodeRectangle(divUp(b.maxSize, kBlockSize), false)};
+  const int rc = resolveBatch(b, true, streamLease, dev, [&] { planDecodeCall(planPolicy(), b.sizes, b.maxSize, false, &groups, &b.work); });
+  *group = groups[0];
+  return rc;
+}
+
+// Decode-accumulate (k_ans_decode_accum): every archive widened to float32 and stored to (accumulate == 0) or added into
+// (1) its float32 accumulator.  No temp memory, no host synchronisation.
+int decodeAccumulateImpl(
+    size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, const void* const* in, const uint32_t* inBytes,
+    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+  DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
+  DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "decode-accumulate: accumulate must be 0 or 1");
+  bool done;
+  int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
+  if (done) return rc;
+  DGPU_REQUIRE(in && inBytes && out && outCapacity, "decode-accumulate: null array with numInBatch > 0");
+  Batch b;
+  rc = floatDecodeBatch(&b, ft, B, 1, in, inBytes, nullptr, ptrSide(out, 4, "decode-accumulate: accumulators must be 4-byte aligned"), outCapacity,
+                        "decode-accumulate: outCapacity must not exceed 0xfffff000");
+  if (rc) return rc;
+  StreamLease streamLease(stream);
+  DeviceBatch dev;
+  LaunchGroup group;
+  rc = planFloatDecode(b, streamLease, &dev, &group);
+  if (rc) return rc;
+  DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
+  d.accumulate = (uint32_t)accumulate;
+  return launchDecode(d, group, dev.work, DecodeForm::kAccum, P, stream);
+}
+
+// Scaled decompress (k_ans_decode_scaled): the whole bounded float decode whose every word is multiplied by the member's
+// float32 factor and rounded back to the archive's type before it is stored.  scale_dev: device memory, read by the
+// kernel -- never here -- so the factor may be written by work enqueued before the call, and a captured call follows
+// the value the memory holds at each replay; null: the host float.  No temp memory, no host synchronisation.
+int decodeScaledImpl(
+    size_t* tempUsed, uint32_t ft, int P, uint32_t B, const void* const* in, const uint32_t* inBytes, void* const* out,
+    const uint32_t* outCapacity, float scale, const float* scale_dev, uint32_t scaleStride, uint8_t* outSuccess_dev,
+    uint32_t* outSize_dev, hipStream_t stream) {
+  DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
+  DGPU_REQUIRE(scaleStride <= 1u, "scaled decompress: scaleStride must be 0 (one factor) or 1 (one per member)");
+  DGPU_REQUIRE(scale_dev != nullptr || (std::isfinite(scale) && scale != 0.0f), "scaled decompress: a host scale must be finite and not zero");
+  DGPU_REQUIRE((uintptr_t)scale_dev % 4u == 0u, "scaled decompress: scale_dev must be 4-byte aligned");
+  bool done;
+  int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
+  if (done) return rc;
+  DGPU_REQUIRE(in && inBytes && out && outCapacity, "scaled decompress: null array with numInBatch > 0");
+  Batch b;
+  rc = floatDecodeBatch(&b, ft, B, 1, in, inBytes, nullptr, ptrSide(out), outCapacity, "scaled decompress: outCapacity must not exceed 0xfffff000");
+  if (rc) return rc;
+  StreamLease streamLease(stream);
+  DeviceBatch dev;
+  LaunchGroup group;
+  rc = planFloatDecode(b, streamLease, &dev, &group);
+  if (rc) return rc;
+  DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
+  d.scale = scale;
+  d.scalePtr = scale_dev;
+  d.scaleStride = scaleStride;
+  return launchDecode(d, group, dev.work, DecodeForm::kWholeScaled, P, stream);
+}
+
+// The norm outputs of a reduce call (either given: the call measures what it leaves) and the temp region their tile
+// partials are carved from.
 struct ReduceNorm {
   double* outSumSq = nullptr;      // [B] device, nullable
   uint32_t* outNonFinite = nullptr;  // [B] device, nullable
@@ -1582,7 +1591,7 @@ struct ReduceNorm {
   size_t tempBytes = 0;
   bool wanted() const { return outSumSq != nullptr || outNonFinite != nullptr; }
 };
-// (before anything is enqueued)
+// (before anything is enqueued; an output that is not given passes)
 int reduceNormCheck(const ReduceNorm& norm) {
   DGPU_REQUIRE((uintptr_t)norm.outSumSq % 8u == 0u, "outSumSq_dev must be 8-byte aligned");
   DGPU_REQUIRE((uintptr_t)norm.outNonFinite % 4u == 0u, "outNonFinite_dev must be 4-byte aligned");
@@ -1608,62 +1617,68 @@ int reduceNormFinish(const ReduceNorm& norm, uint32_t B, const LaunchGroup& g, c
   return DGPU_OK;
 }
 
+// What each of the eight reduce entry points adds to the plain call.
+struct ReduceOptions {
+  bool mixed = false;              // `kinds` says which sources are raw rows (mixedSourceAddresses) and must be given
+  const uint8_t* kinds = nullptr;  // [B * S] host; null: every source is an archive
+  float scale = 1.0f;              // a kernel argument: the parameter block and its cache entry are the unscaled call's
+  ReduceNorm norm;
+};
+
+// The reduce kernel of a call, stated once.  stats: reduce-compress, which counts the exponent bytes of the rounded
+// sums.  A norm form serves every scale and every kind of source, a scaled form every kind of source, for S == 1 too;
+// with no raw row among the sources the call is the plain one.
+DecodeForm reduceForm(bool stats, bool anyRaw, bool scaled, bool norm) {
+  if (norm) return stats ? DecodeForm::kReduceNormStats : DecodeForm::kReduceNorm;
+  if (scaled) return stats ? DecodeForm::kReduceScaledStats : DecodeForm::kReduceScaled;
+  if (anyRaw) return stats ? DecodeForm::kReduceMixedStats : DecodeForm::kReduceMixed;
+  return stats ? DecodeForm::kReduceStats : DecodeForm::kReduce;
+}
+
+// Decode-reduce: S = numSources archives per float32 accumulator, summed left to right in one launch, all or nothing per
+// member.  The launch plan is that of a decode-accumulate call with the same capacities, and a call of one archive per
+// member with no factor and no norm IS that call.  No host synchronisation; with the norm outputs the launch is followed
+// by k_reduce_norm_finish (reduceNormBegin / reduceNormFinish), and the tile partials are the call's only temp memory.
 int decodeReduceImpl(
     size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, uint32_t S, const void* const* in, const uint32_t* inBytes,
-    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream, bool mixed = false,
-    const uint8_t* kinds = nullptr, float scale = 1.0f, const ReduceNorm& norm = ReduceNorm()) {
+    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream, const ReduceOptions& opt) {
   DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
-  const bool withNorm = norm.wanted();
-  const bool scaled = scale != 1.0f || withNorm;  // (neither goes the ways of the plain call)
-  if (withNorm) {
-    const int rcNorm = reduceNormCheck(norm);
-    if (rcNorm) return rcNorm;
-  }
+  const bool withNorm = opt.norm.wanted();
+  const bool plainKernel = opt.scale == 1.0f && !withNorm;  // (a factor or a norm never goes the ways of the plain call)
+  if (int rcNorm = reduceNormCheck(opt.norm)) return rcNorm;
   DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "decode-reduce: accumulate must be 0 or 1");
   DGPU_REQUIRE(S >= 1u && S <= kMaxReduceSources, "decode-reduce: numSources must be between 1 and 64");
   DGPU_REQUIRE((uint64_t)B * S <= 65535u, "decode-reduce: numInBatch * numSources must be <= 65535");
-  if (S == 1u && !mixed && !scaled) return decodeAccumulateImpl(tempUsed, ft, P, accumulate, B, in, inBytes, out, outCapacity, outSuccess_dev, outSize_dev, stream);
+  auto asAccumulate = [&] { return decodeAccumulateImpl(tempUsed, ft, P, accumulate, B, in, inBytes, out, outCapacity, outSuccess_dev, outSize_dev, stream); };
+  if (S == 1u && !opt.mixed && plainKernel) return asAccumulate();
   bool done;
   int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
   if (done) return rc;
   DGPU_REQUIRE(in && inBytes && out && outCapacity, "decode-reduce: null array with numInBatch > 0");
+  DGPU_REQUIRE(!opt.mixed || opt.kinds, "decode-reduce: sourceKind is null with numInBatch > 0");
+  if (S == 1u && plainKernel && opt.kinds && std::all_of(opt.kinds, opt.kinds + B, [](uint8_t k) { return k == 0u; })) return asAccumulate();
   Batch b;
   bool anyRaw = false;
-  // (pointerBatch, with S inputs per output)
-  if (mixed) {
-    rc = mixedSourceAddresses("decode-reduce: sourceKind is null with numInBatch > 0", in, inBytes, kinds, B * S, floatWordBytes(ft), &b.inPtrs, &anyRaw);
-    if (!rc && !anyRaw && S == 1u && !scaled) {
-      return decodeAccumulateImpl(tempUsed, ft, P, accumulate, B, in, inBytes, out, outCapacity, outSuccess_dev, outSize_dev, stream);
-    }
-  } else {
-    rc = sideAddresses(ptrSide(in, 16, kMsgCompIn), B * S, &b.inPtrs);
-  }
-  if (!rc) rc = sideAddresses(ptrSide(out, 4, "decode-reduce: accumulators must be 4-byte aligned"), B, &b.outPtrs);
+  rc = floatDecodeBatch(&b, ft, B, S, in, inBytes, opt.kinds, ptrSide(out, 4, "decode-reduce: accumulators must be 4-byte aligned"), outCapacity,
+                        "decode-reduce: outCapacity must not exceed 0xfffff000", &anyRaw);
   if (rc) return rc;
-  b.n = B;
-  b.sizes.assign(outCapacity, outCapacity + B);
-  b.inBytes.assign(inBytes, inBytes + (size_t)B * S);
-  for (uint32_t i = 0; i < B; ++i) b.maxSize = std::max(b.maxSize, outCapacity[i]);
-  // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
-  DGPU_REQUIRE(b.maxSize <= 0xfffff000u, "decode-reduce: outCapacity must not exceed 0xfffff000");
   StreamLease streamLease(stream);
   DeviceBatch dev;
-  std::vector<LaunchGroup> groups{decodeRectangle(divUp(b.maxSize, kBlockSize), false)};
-  rc = resolveBatch(b, true, streamLease, &dev, [&] { planDecodeCall(planPolicy(), b.sizes, b.maxSize, false, &groups, &b.work); });
+  LaunchGroup group;
+  rc = planFloatDecode(b, streamLease, &dev, &group);
   if (rc) return rc;
   DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
   d.accumulate = (uint32_t)accumulate;
   d.numSources = S;
-  d.scale = scale;
-  if (withNorm) {
-    TempArena arena(norm.temp, norm.tempBytes, streamLease);
-    rc = reduceNormBegin(arena, B, groups[0], &d, stream);
-    if (!rc) rc = launchDecode(d, groups[0], dev.work, DecodeForm::kReduceNorm, P, stream);
-    if (!rc) rc = reduceNormFinish(norm, B, groups[0], d, stream);
-    if (tempUsed) *tempUsed = arena.requested();
-    return rc;
-  }
-  return launchDecode(d, groups[0], dev.work, scaled ? DecodeForm::kReduceScaled : (anyRaw ? DecodeForm::kReduceMixed : DecodeForm::kReduce), P, stream);
+  d.scale = opt.scale;
+  const DecodeForm form = reduceForm(false, anyRaw, !plainKernel, withNorm);
+  if (!withNorm) return launchDecode(d, group, dev.work, form, P, stream);
+  TempArena arena(opt.norm.temp, opt.norm.tempBytes, streamLease);
+  rc = reduceNormBegin(arena, B, group, &d, stream);
+  if (!rc) rc = launchDecode(d, group, dev.work, form, P, stream);
+  if (!rc) rc = reduceNormFinish(opt.norm, B, group, d, stream);
+  if (tempUsed) *tempUsed = arena.requested();
+  return rc;
 }
 
 // Reduce-compress: decode-reduce into the accumulators, then cast-compress of the accumulators, without the cast
@@ -1673,22 +1688,16 @@ int decodeReduceImpl(
 // histogram counters (held under the stream lease; k_normalize reads them and puts them back to zero), otherwise a
 // region of temp memory cleared by one memset on the stream.  A member that fails the reduce has no counts: its table is
 // the flat one, which codes any data.  Everything is validated before the first enqueue; nothing synchronises.
-// mixed (dgpu_float_reduce_compress_mixed): as in decodeReduceImpl; the reduce kernel is k_ans_decode_reduce_mixed_stats.
-// scale (dgpu_float_reduce_compress_scaled): as in decodeReduceImpl; the reduce kernel is
-// k_ans_decode_reduce_mixed_stats_scaled, which stores, rounds and counts the scaled sums.  The encoder does not know.
-// norm (dgpu_float_reduce_compress_norm): as in decodeReduceImpl; the reduce kernel is k_ans_decode_reduce_mixed_stats_norm,
-// which measures the sums ROUNDED to the archive type; the partials come out of the call's temp memory like the counts.
+// The reduce kernels are the counting forms of decodeReduceImpl's (reduceForm): with a scale they store, round and count
+// the scaled sums -- the encoder does not know -- and with the norm outputs they measure the sums ROUNDED to the archive
+// type; the partials come out of the call's temp memory like the counts.
 int reduceCompressImpl(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, uint32_t S,
     const void* const* in, const uint32_t* inBytes, void* const* acc, const uint32_t* outCapacity, void* const* outArchive,
-    uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream, bool mixed = false,
-    const uint8_t* kinds = nullptr, float scale = 1.0f, const ReduceNorm& norm = ReduceNorm()) {
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream, const ReduceOptions& opt) {
   DGPU_REQUIRE(ft == kFloat16 || ft == kBFloat16, "reduce-compress: floatType must be float16 or bfloat16 (float32: decode-reduce, then dgpu_float_compress)");
-  const bool withNorm = norm.wanted();
-  if (withNorm) {
-    const int rcNorm = reduceNormCheck(norm);
-    if (rcNorm) return rcNorm;
-  }
+  const bool withNorm = opt.norm.wanted();
+  if (int rcNorm = reduceNormCheck(opt.norm)) return rcNorm;
   DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "reduce-compress: accumulate must be 0 or 1");
   DGPU_REQUIRE(S >= 1u && S <= kMaxReduceSources, "reduce-compress: numSources must be between 1 and 64");
   DGPU_REQUIRE((uint64_t)B * S <= 65535u, "reduce-compress: numInBatch * numSources must be <= 65535");
@@ -1696,29 +1705,22 @@ int reduceCompressImpl(
   int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
   if (done) return rc;
   DGPU_REQUIRE(in && inBytes && acc && outCapacity && outArchive, "reduce-compress: null array with numInBatch > 0");
+  DGPU_REQUIRE(!opt.mixed || opt.kinds, "reduce-compress: sourceKind is null with numInBatch > 0");
   // the reduce side: B * S archives into B accumulators (decodeReduceImpl); the compress side: the accumulators into B archives
   Batch bd, be;
   bool anyRaw = false;
-  if (mixed) {
-    rc = mixedSourceAddresses("reduce-compress: sourceKind is null with numInBatch > 0", in, inBytes, kinds, B * S, floatWordBytes(ft), &bd.inPtrs, &anyRaw);
-  } else {
-    rc = sideAddresses(ptrSide(in, 16, kMsgCompIn), B * S, &bd.inPtrs);
-  }
-  if (!rc) rc = sideAddresses(ptrSide(acc, 4, "reduce-compress: accumulators must be 4-byte aligned"), B, &bd.outPtrs);
-  if (!rc) rc = pointerBatch(&be, B, ptrSide(acc, 4, "reduce-compress: accumulators must be 4-byte aligned"), ptrSide(outArchive, 16, kMsgCompOut), outCapacity);
+  const Side accSide = ptrSide(acc, 4, "reduce-compress: accumulators must be 4-byte aligned");
+  rc = floatDecodeBatch(&bd, ft, B, S, in, inBytes, opt.kinds, accSide, outCapacity, /*tooLarge: encodableSize*/ nullptr, &anyRaw);
+  if (!rc) rc = pointerBatch(&be, B, accSide, ptrSide(outArchive, 16, kMsgCompOut), outCapacity);
   if (rc) return rc;
-  bd.n = B;
-  bd.sizes = be.sizes;
-  bd.inBytes.assign(inBytes, inBytes + (size_t)B * S);
-  bd.maxSize = be.maxSize;
   DGPU_REQUIRE(encodableSize(be.maxSize),
                "reduce-compress: outCapacity larger than 1717538816 words: the maximum compressed size of its exponent plane exceeds INT32_MAX (GpuANSEncode.cu:22)");
 
   StreamLease streamLease(stream);
   TempArena arena(temp_dev, tempBytes, streamLease);
   DeviceBatch devD, devE;
-  std::vector<LaunchGroup> groupsD{decodeRectangle(divUp(bd.maxSize, kBlockSize), false)};
-  rc = resolveBatch(bd, true, streamLease, &devD, [&] { planDecodeCall(planPolicy(), bd.sizes, bd.maxSize, false, &groupsD, &bd.work); });
+  LaunchGroup groupD;
+  rc = planFloatDecode(bd, streamLease, &devD, &groupD);
   if (rc) return rc;
   const uint32_t castType = ft | kCastSource;
   std::vector<LaunchGroup> groupsE{encodeRectangle(be.maxSize, castType)};
@@ -1741,17 +1743,15 @@ int reduceCompressImpl(
   d.accumulate = (uint32_t)accumulate;
   d.numSources = S;
   d.stats = counts;
-  d.scale = scale;
-  const DecodeForm form = withNorm ? DecodeForm::kReduceNormStats
-                                   : (scale != 1.0f ? DecodeForm::kReduceScaledStats : (anyRaw ? DecodeForm::kReduceMixedStats : DecodeForm::kReduceStats));
+  d.scale = opt.scale;
   if (withNorm) {
-    rc = reduceNormBegin(arena, B, groupsD[0], &d, stream);
+    rc = reduceNormBegin(arena, B, groupD, &d, stream);
     if (rc) {  // (nothing is launched: the counters are still zero)
       if (tempUsed) *tempUsed = arena.requested();
       return rc;
     }
   }
-  rc = launchDecode(d, groupsD[0], devD.work, form, P, stream);
+  rc = launchDecode(d, groupD, devD.work, reduceForm(true, anyRaw, opt.scale != 1.0f, withNorm), P, stream);
   if (!rc) {
     EncodeShared shared;
     rc = encodeCommon(arena, streamLease, stream, P, false, B, devE.in, devE.out, castType, groupsE[0], devE.work, shared,
@@ -1760,7 +1760,7 @@ int reduceCompressImpl(
     if (rc && countsAtRest) (void)hipMemsetAsync(countsAtRest, 0, (size_t)B * kNumSymbols * 4, stream);
   }
   // (after the encoder: its failure handling above stays what it was; the partials are a region of their own, d.normPartials)
-  if (!rc && withNorm) rc = reduceNormFinish(norm, B, groupsD[0], d, stream);
+  if (!rc && withNorm) rc = reduceNormFinish(opt.norm, B, groupD, d, stream);
   if (tempUsed) *tempUsed = arena.requested();
   return rc;
 }
@@ -2078,7 +2078,11 @@ int dgpu_float_decode_scaled(
                           outSuccess_dev, outSize_dev, (hipStream_t)stream);
 }
 
-// ---- decode-reduce (no upstream equivalent) ---------------------------------------
+// ---- the reduce family (no upstream equivalent) -------------------------------------
+// Eight entry points over decodeReduceImpl / reduceCompressImpl: each states which ReduceOptions {mixed, kinds, scale,
+// norm} it passes.  Decode-reduce takes temp memory for the norm partials only.
+static bool scaleOk(float scale) { return std::isfinite(scale) && scale != 0.0f; }
+
 int dgpu_float_decode_reduce(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
     uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, void* const* out,
@@ -2086,20 +2090,19 @@ int dgpu_float_decode_reduce(
   (void)temp_dev;
   (void)tempBytes;
   return decodeReduceImpl(tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, out, outCapacity,
-                          outSuccess_dev, outSize_dev, (hipStream_t)stream);
+                          outSuccess_dev, outSize_dev, (hipStream_t)stream, ReduceOptions());
 }
 
-// ---- reduce-compress (no upstream equivalent) -------------------------------------
 int dgpu_float_reduce_compress(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
     uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, void* const* acc,
     const uint32_t* outCapacity, void* const* outArchive, uint8_t* outSuccess_dev, uint32_t* outSize_dev,
     uint32_t* outArchiveSize_dev, void* stream) {
   return reduceCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, acc,
-                            outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream);
+                            outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream, ReduceOptions());
 }
 
-// ---- mixed sources: archives and raw rows of floatType words (no upstream equivalent) ----------------
+// mixed sources: archives and raw rows of floatType words; sourceKind must be given
 int dgpu_float_decode_reduce_mixed(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
     uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, const uint8_t* sourceKind,
@@ -2107,7 +2110,7 @@ int dgpu_float_decode_reduce_mixed(
   (void)temp_dev;
   (void)tempBytes;
   return decodeReduceImpl(tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, out, outCapacity,
-                          outSuccess_dev, outSize_dev, (hipStream_t)stream, true, sourceKind);
+                          outSuccess_dev, outSize_dev, (hipStream_t)stream, ReduceOptions{true, sourceKind});
 }
 
 int dgpu_float_reduce_compress_mixed(
@@ -2116,13 +2119,12 @@ int dgpu_float_reduce_compress_mixed(
     void* const* acc, const uint32_t* outCapacity, void* const* outArchive, uint8_t* outSuccess_dev, uint32_t* outSize_dev,
     uint32_t* outArchiveSize_dev, void* stream) {
   return reduceCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, acc,
-                            outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream, true, sourceKind);
+                            outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream,
+                            ReduceOptions{true, sourceKind});
 }
 
-// ---- scaled: acc = fl32(sum * scale) in the reduce kernel (no upstream equivalent) ----------------
+// scaled: acc = fl32(sum * scale) in the reduce kernel
 // (sourceKind NULL: every source is an archive.  The scale is checked first: nothing is enqueued for a bad one.)
-static bool scaleOk(float scale) { return std::isfinite(scale) && scale != 0.0f; }
-
 int dgpu_float_decode_reduce_scaled(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
     uint32_t numInBatch, uint32_t numSources, const void* const* in, const uint32_t* inBytes, const uint8_t* sourceKind,
@@ -2131,7 +2133,7 @@ int dgpu_float_decode_reduce_scaled(
   (void)tempBytes;
   DGPU_REQUIRE(scaleOk(scale), "decode-reduce: scale must be finite and not zero");
   return decodeReduceImpl(tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, out, outCapacity,
-                          outSuccess_dev, outSize_dev, (hipStream_t)stream, sourceKind != nullptr, sourceKind, scale);
+                          outSuccess_dev, outSize_dev, (hipStream_t)stream, ReduceOptions{sourceKind != nullptr, sourceKind, scale});
 }
 
 int dgpu_float_reduce_compress_scaled(
@@ -2142,10 +2144,10 @@ int dgpu_float_reduce_compress_scaled(
   DGPU_REQUIRE(scaleOk(scale), "reduce-compress: scale must be finite and not zero");
   return reduceCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, acc,
                             outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream,
-                            sourceKind != nullptr, sourceKind, scale);
+                            ReduceOptions{sourceKind != nullptr, sourceKind, scale});
 }
 
-// ---- norm: the reduce call also reports the squared norm and the non-finite count of what it leaves ----------------
+// norm: the reduce call also reports the squared norm and the non-finite count of what it leaves
 // (both outputs NULL: the scaled call.  Scale and alignment are checked first: nothing is enqueued for a bad one.)
 size_t dgpu_float_reduce_norm_temp_bytes(uint32_t floatType, uint32_t numInBatch, uint32_t maxWords, int compress) {
   // (the tiles of the launch, bounded so that the figure never falls as maxWords grows: 8 blocks are two 4-block tiles,
@@ -2162,13 +2164,9 @@ int dgpu_float_decode_reduce_norm(
     float scale, void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev,
     double* outSumSq_dev, uint32_t* outNonFinite_dev, void* stream) {
   DGPU_REQUIRE(scaleOk(scale), "decode-reduce: scale must be finite and not zero");
-  ReduceNorm norm;
-  norm.outSumSq = outSumSq_dev;
-  norm.outNonFinite = outNonFinite_dev;
-  norm.temp = temp_dev;
-  norm.tempBytes = tempBytes;
   return decodeReduceImpl(tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, out, outCapacity,
-                          outSuccess_dev, outSize_dev, (hipStream_t)stream, sourceKind != nullptr, sourceKind, scale, norm);
+                          outSuccess_dev, outSize_dev, (hipStream_t)stream,
+                          ReduceOptions{sourceKind != nullptr, sourceKind, scale, {outSumSq_dev, outNonFinite_dev, temp_dev, tempBytes}});
 }
 
 int dgpu_float_reduce_compress_norm(
@@ -2177,12 +2175,10 @@ int dgpu_float_reduce_compress_norm(
     float scale, void* const* acc, const uint32_t* outCapacity, void* const* outArchive, uint8_t* outSuccess_dev,
     uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, double* outSumSq_dev, uint32_t* outNonFinite_dev, void* stream) {
   DGPU_REQUIRE(scaleOk(scale), "reduce-compress: scale must be finite and not zero");
-  ReduceNorm norm;
-  norm.outSumSq = outSumSq_dev;
-  norm.outNonFinite = outNonFinite_dev;
+  // (the partials come out of the arena of the call: the norm has no region of its own)
   return reduceCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, accumulate, numInBatch, numSources, in, inBytes, acc,
                             outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, (hipStream_t)stream,
-                            sourceKind != nullptr, sourceKind, scale, norm);
+                            ReduceOptions{sourceKind != nullptr, sourceKind, scale, {outSumSq_dev, outNonFinite_dev}});
 }
 
 // ---- float stride batches with capacities on both sides (the compressed collectives) --------------------

@@ -157,121 +157,61 @@ inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, boo
   });
 }
 
-// The decoder of tiles of `tileBlocks` blocks; batches whose every capacity is one block go to k_ans_decode_pair (two
-// elements per wavefront, kernels_pairs.h).
-//   * DecodeForm::kRanged: k_ans_decode_range, which decodes a block range of every element; it exists for 16- and
-//     4-block tiles (a range of one or two blocks takes the 4-block form);
-//   * DecodeForm::kAccum: k_ans_decode_accum, which widens to float32 and stores to / adds into float32 accumulators;
-//     float types only (raw bytes: the float32 form), 16- and 4-block tiles;
-//   * DecodeForm::kReduce: k_ans_decode_reduce, the same with DecodeArgs::numSources archives per accumulator;
-//   * DecodeForm::kReduceStats: k_ans_decode_reduce_stats, which also counts the exponent bytes of the rounded sums
-//     (DecodeArgs::stats); float16 and bfloat16 only (anything else: the bfloat16 form), 16- and 4-block tiles, with
-//     the LDS of the bins behind that of the plain form;
-//   * DecodeForm::kReduceMixed / kReduceMixedStats: k_ans_decode_reduce_mixed / k_ans_decode_reduce_mixed_stats, the two
-//     above with sources that are archives or raw rows (DecodeArgs::sourceKind); the same types, tiles and LDS;
-//   * DecodeForm::kReduceScaled / kReduceScaledStats: k_ans_decode_reduce_mixed_scaled / _mixed_stats_scaled, the mixed
-//     forms that multiply the last source's store by DecodeArgs::scale; they serve all-archive members too.  The
-//     counting form keeps the factor in LDS behind its bins (decReduceStatsScaledLdsBytes).
-//   * DecodeForm::kReduceNorm / kReduceNormStats: k_ans_decode_reduce_mixed_norm / _mixed_stats_norm, the scaled forms
-//     that also measure the words they leave (DecodeArgs::normPartials) and take a factor of 1 as well; the LDS of the
-//     scaled forms and a ReduceNormTile behind it (decReduceNormLdsBytes).
-//   * DecodeForm::kWholeScaled: k_ans_decode_scaled, the whole decode that multiplies every word by the member's factor
-//     (DecodeArgs::scalePtr / scaleStride / scale); float types only (raw bytes: the float32 form), 16- and 4-block
-//     tiles (there is no scaled form of k_ans_decode_pair), the LDS of the whole form.
+// The archive type a decode form is built for, given the call's.
+constexpr uint32_t sameType(uint32_t ft) { return ft; }
+constexpr uint32_t floatsOnly(uint32_t ft) { return ft ? ft : kFloat32; }                         // raw bytes: the float32 form
+constexpr uint32_t halvesOnly(uint32_t ft) { return ft == kFloat16 ? kFloat16 : kBFloat16; }  // anything but fp16: the bf16 form
+
+// Every decode form but the whole decode, once: X(form, kernel template, archive-type substitution, LDS bytes of the
+// instantiation <P, T, TB>).  The kernel's name is its profiling name.  Each exists for 16- and 4-block tiles; a new
+// form is one line here.
+//   * kAccum: widens to float32 and stores to / adds into float32 accumulators; float types only;
+//   * kReduce: the same with DecodeArgs::numSources archives per accumulator;
+//   * kReduceStats: also counts the exponent bytes of the rounded sums (DecodeArgs::stats); float16 and bfloat16 only,
+//     with the LDS of the bins behind that of the plain form;
+//   * kReduceMixed / kReduceMixedStats: the two above with sources that are archives or raw rows (DecodeArgs::sourceKind);
+//     the same types, tiles and LDS;
+//   * kReduceScaled / kReduceScaledStats: the mixed forms that multiply the last source's store by DecodeArgs::scale;
+//     they serve all-archive members too.  The counting form keeps the factor in LDS behind its bins;
+//   * kReduceNorm / kReduceNormStats: the scaled forms that also measure the words they leave (DecodeArgs::normPartials)
+//     and take a factor of 1 as well; the LDS of the scaled forms and a ReduceNormTile behind it;
+//   * kWholeScaled: the whole decode that multiplies every word by the member's factor (DecodeArgs::scalePtr /
+//     scaleStride / scale); float types only, the LDS of the whole form.  There is no scaled form of k_ans_decode_pair:
+//     single-block batches run on 4-block tiles;
+//   * kRanged: decodes a block range of every element (a range of one or two blocks takes the 4-block form).
+#define DGPU_DECODE_FORMS(X)                                                                                           \
+  X(kAccum, k_ans_decode_accum, floatsOnly, decLdsBytes(P, T, TB))                                                     \
+  X(kReduce, k_ans_decode_reduce, floatsOnly, decLdsBytes(P, T, TB))                                                   \
+  X(kReduceStats, k_ans_decode_reduce_stats, halvesOnly, decReduceStatsLdsBytes(P, T, TB))                             \
+  X(kReduceMixed, k_ans_decode_reduce_mixed, floatsOnly, decLdsBytes(P, T, TB))                                        \
+  X(kReduceMixedStats, k_ans_decode_reduce_mixed_stats, halvesOnly, decReduceStatsLdsBytes(P, T, TB))                  \
+  X(kReduceScaled, k_ans_decode_reduce_mixed_scaled, floatsOnly, decLdsBytes(P, T, TB))                                \
+  X(kReduceScaledStats, k_ans_decode_reduce_mixed_stats_scaled, halvesOnly, decReduceStatsScaledLdsBytes(P, T, TB))    \
+  X(kReduceNorm, k_ans_decode_reduce_mixed_norm, floatsOnly, decReduceNormLdsBytes(P, T, TB, false))                   \
+  X(kReduceNormStats, k_ans_decode_reduce_mixed_stats_norm, halvesOnly, decReduceNormLdsBytes(P, T, TB, true))         \
+  X(kWholeScaled, k_ans_decode_scaled, floatsOnly, decScaledLdsBytes(P, T, TB))                                        \
+  X(kRanged, k_ans_decode_range, sameType, decLdsBytes(P, T, TB))
+
+// The decoder of tiles of `tileBlocks` blocks.  A form of the list above takes the 4-block instantiation for tiles of
+// up to 4 blocks and the 16-block one otherwise.  The whole decode (k_ans_decode) also exists for 2-block tiles, and
+// batches whose every capacity is one block go to k_ans_decode_pair (two elements per wavefront, kernels_pairs.h).
 inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, DecodeForm form = DecodeForm::kWhole) {
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> DecodeVariant {
     constexpr int kP = decltype(p)::value;
     constexpr uint32_t kFT = decltype(f)::value;
-    if (form == DecodeForm::kAccum) {
-      auto tiled = [](auto tb) -> DecodeVariant {
-        constexpr uint32_t kTB = decltype(tb)::value;
-        constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
-        return {k_ans_decode_accum<kP, kAccFT, kTB>, decThreads(kTB), decLdsBytes(kP, kAccFT, kTB), "k_ans_decode_accum"};
-      };
+    auto smallOrFull = [&](auto tiled) -> DecodeVariant {
       return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
-    }
-    if (form == DecodeForm::kReduce) {
-      auto tiled = [](auto tb) -> DecodeVariant {
-        constexpr uint32_t kTB = decltype(tb)::value;
-        constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
-        return {k_ans_decode_reduce<kP, kAccFT, kTB>, decThreads(kTB), decLdsBytes(kP, kAccFT, kTB), "k_ans_decode_reduce"};
-      };
-      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
-    }
-    if (form == DecodeForm::kReduceStats) {
-      auto tiled = [](auto tb) -> DecodeVariant {
-        constexpr uint32_t kTB = decltype(tb)::value;
-        constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
-        return {k_ans_decode_reduce_stats<kP, kCastFT, kTB>, decThreads(kTB), decReduceStatsLdsBytes(kP, kCastFT, kTB), "k_ans_decode_reduce_stats"};
-      };
-      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
-    }
-    if (form == DecodeForm::kReduceMixed) {
-      auto tiled = [](auto tb) -> DecodeVariant {
-        constexpr uint32_t kTB = decltype(tb)::value;
-        constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
-        return {k_ans_decode_reduce_mixed<kP, kAccFT, kTB>, decThreads(kTB), decLdsBytes(kP, kAccFT, kTB), "k_ans_decode_reduce_mixed"};
-      };
-      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
-    }
-    if (form == DecodeForm::kReduceMixedStats) {
-      auto tiled = [](auto tb) -> DecodeVariant {
-        constexpr uint32_t kTB = decltype(tb)::value;
-        constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
-        return {k_ans_decode_reduce_mixed_stats<kP, kCastFT, kTB>, decThreads(kTB), decReduceStatsLdsBytes(kP, kCastFT, kTB),
-                "k_ans_decode_reduce_mixed_stats"};
-      };
-      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
-    }
-    if (form == DecodeForm::kReduceScaled) {
-      auto tiled = [](auto tb) -> DecodeVariant {
-        constexpr uint32_t kTB = decltype(tb)::value;
-        constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
-        return {k_ans_decode_reduce_mixed_scaled<kP, kAccFT, kTB>, decThreads(kTB), decLdsBytes(kP, kAccFT, kTB), "k_ans_decode_reduce_mixed_scaled"};
-      };
-      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
-    }
-    if (form == DecodeForm::kReduceScaledStats) {
-      auto tiled = [](auto tb) -> DecodeVariant {
-        constexpr uint32_t kTB = decltype(tb)::value;
-        constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
-        return {k_ans_decode_reduce_mixed_stats_scaled<kP, kCastFT, kTB>, decThreads(kTB), decReduceStatsScaledLdsBytes(kP, kCastFT, kTB),
-                "k_ans_decode_reduce_mixed_stats_scaled"};
-      };
-      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
-    }
-    if (form == DecodeForm::kReduceNorm) {
-      auto tiled = [](auto tb) -> DecodeVariant {
-        constexpr uint32_t kTB = decltype(tb)::value;
-        constexpr uint32_t kAccFT = kFT ? kFT : kFloat32;
-        return {k_ans_decode_reduce_mixed_norm<kP, kAccFT, kTB>, decThreads(kTB), decReduceNormLdsBytes(kP, kAccFT, kTB, false), "k_ans_decode_reduce_mixed_norm"};
-      };
-      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
-    }
-    if (form == DecodeForm::kReduceNormStats) {
-      auto tiled = [](auto tb) -> DecodeVariant {
-        constexpr uint32_t kTB = decltype(tb)::value;
-        constexpr uint32_t kCastFT = kFT == kFloat16 ? kFloat16 : kBFloat16;
-        return {k_ans_decode_reduce_mixed_stats_norm<kP, kCastFT, kTB>, decThreads(kTB), decReduceNormLdsBytes(kP, kCastFT, kTB, true),
-                "k_ans_decode_reduce_mixed_stats_norm"};
-      };
-      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
-    }
-    if (form == DecodeForm::kWholeScaled) {
-      auto tiled = [](auto tb) -> DecodeVariant {
-        constexpr uint32_t kTB = decltype(tb)::value;
-        constexpr uint32_t kScFT = kFT ? kFT : kFloat32;
-        return {k_ans_decode_scaled<kP, kScFT, kTB>, decThreads(kTB), decScaledLdsBytes(kP, kScFT, kTB), "k_ans_decode_scaled"};
-      };
-      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
-    }
-    if (form == DecodeForm::kRanged) {
-      auto tiled = [](auto tb) -> DecodeVariant {
-        constexpr uint32_t kTB = decltype(tb)::value;
-        return {k_ans_decode_range<kP, kFT, kTB>, decThreads(kTB), decLdsBytes(kP, kFT, kTB), "k_ans_decode_range"};
-      };
-      return tileBlocks <= kDecBlocksPerSmallTile ? tiled(UintC<kDecBlocksPerSmallTile>{}) : tiled(UintC<kDecBlocksPerTile>{});
-    }
+    };
+#define DGPU_DECODE_FORM_CASE(formName, kernel, typeOf, ldsBytes)                \
+  if (form == DecodeForm::formName) {                                            \
+    return smallOrFull([](auto tb) -> DecodeVariant {                            \
+      constexpr int P = kP;                                                      \
+      constexpr uint32_t T = typeOf(kFT), TB = decltype(tb)::value;              \
+      return {kernel<P, T, TB>, decThreads(TB), ldsBytes, #kernel};              \
+    });                                                                          \
+  }
+    DGPU_DECODE_FORMS(DGPU_DECODE_FORM_CASE)
+#undef DGPU_DECODE_FORM_CASE
     if (tileBlocks == kDecBlocksPerSingleTile) return {k_ans_decode_pair<kP, kFT>, 64u, decPairLdsBytes(kP, kFT), "k_ans_decode_pair"};
     auto tiled = [](auto tb) -> DecodeVariant {
       constexpr uint32_t kTB = decltype(tb)::value;

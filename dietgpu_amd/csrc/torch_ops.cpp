@@ -560,42 +560,6 @@ int64_t decompress_data_scaled(
   return (int64_t)used;
 }
 
-// Decode-reduce (no reference op): num_sources archives per accumulator, ts_in flattened member-major (source s of
-// accumulator i is ts_in[i * num_sources + s]), summed left to right in one launch, all or nothing per accumulator
-// (dgpu_float_decode_reduce).  accumulate = false stores the first source: the accumulators are never read.
-int64_t decompress_data_reduce(
-    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, bool accumulate,
-    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes) {
-  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
-  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
-  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
-  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
-  TORCH_CHECK(floatType >= (int64_t)DGPU_FLOAT16 && floatType <= (int64_t)DGPU_FLOAT32, "dietgpu: float_type must be 1, 2 or 3");
-  int dev = tIns.front().get_device();
-  c10::hip::HIPGuard guard(dev);
-  Temp tmp = tempOf(tempMem, dev);
-  const size_t n = tAccs.size();
-  // (every source beside its accumulator: the checks of a decode call, then the accumulators once)
-  std::vector<at::Tensor> accOfSource(tIns.size());
-  for (size_t i = 0; i < tIns.size(); ++i) accOfSource[i] = tAccs[i / (size_t)numSources];
-  DecodeTensors sources = marshalDecode(true, tIns, accOfSource, dev, [&](size_t i) {
-    TORCH_CHECK(accOfSource[i].scalar_type() == at::ScalarType::Float, "dietgpu: accumulators must be float32");
-  });
-  std::vector<void*> outPtrs(n);
-  std::vector<uint32_t> outCapacity(n);
-  for (size_t i = 0; i < n; ++i) {
-    outPtrs[i] = sources.outPtrs[i * (size_t)numSources];
-    outCapacity[i] = sources.outCapacity[i * (size_t)numSources];
-  }
-  validateStatus(outStatus, outSizes, (int64_t)n, dev);
-  size_t used = 0;
-  check(dgpu_float_decode_reduce(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
-                                 (uint32_t)numSources, sources.inPtrs.data(), sources.inBytes.data(), outPtrs.data(), outCapacity.data(),
-                                 ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
-        "floatDecompressReduce", true);
-  return (int64_t)used;
-}
-
 // Cast-compress (no reference op): float32 tensor i rounded to float_type (1 = float16, 2 = bfloat16) in registers and
 // compressed into an ordinary archive of that type (dgpu_float_cast_compress).  Output conventions of compress_data.
 std::tuple<at::Tensor, at::Tensor, int64_t> compress_data_cast(
@@ -682,54 +646,24 @@ std::tuple<at::Tensor, at::Tensor, int64_t> compress_data_rolling(
   return {std::move(comp), std::move(sizes), (int64_t)used};
 }
 
-// Reduce-compress (no reference op): decompress_data_reduce into ts_acc and compress_data_cast of ts_acc in one call
-// (dgpu_float_reduce_compress).  ts_in as decompress_data_reduce's; float_type (1 = float16, 2 = bfloat16) is that of the
-// sources and of the archives.  Output conventions of compress_data_cast.
-std::tuple<at::Tensor, at::Tensor, int64_t> decompress_data_reduce_compress(
-    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, bool accumulate,
-    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes,
-    const std::optional<at::Tensor>& outCompressed, const std::optional<at::Tensor>& outCompressedSizes) {
-  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
-  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
-  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
-  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
-  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
-  int dev = tIns.front().get_device();
-  c10::hip::HIPGuard guard(dev);
-  Temp tmp = tempOf(tempMem, dev);
-  const size_t n = tAccs.size();
-  std::vector<at::Tensor> accOfSource(tIns.size());
-  for (size_t i = 0; i < tIns.size(); ++i) accOfSource[i] = tAccs[i / (size_t)numSources];
-  DecodeTensors sources = marshalDecode(true, tIns, accOfSource, dev, [&](size_t i) {
-    TORCH_CHECK(accOfSource[i].scalar_type() == at::ScalarType::Float, "dietgpu: accumulators must be float32");
-  });
-  std::vector<void*> accPtrs(n);
-  std::vector<uint32_t> capacity(n);
-  int64_t maxWords = 0;
-  for (size_t i = 0; i < n; ++i) {
-    accPtrs[i] = sources.outPtrs[i * (size_t)numSources];
-    capacity[i] = sources.outCapacity[i * (size_t)numSources];
-    maxWords = std::max<int64_t>(maxWords, tAccs[i].numel());
-  }
-  validateStatus(outStatus, outSizes, (int64_t)n, dev);
-  at::Tensor comp, sizes;
-  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)maxWords), dev,
-                  tAccs[0].device(), comp, sizes);
-  std::vector<void*> compPtrs(n);
-  for (size_t i = 0; i < n; ++i) compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
-  size_t used = 0;
-  check(dgpu_float_reduce_compress(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
-                                   (uint32_t)numSources, sources.inPtrs.data(), sources.inBytes.data(), accPtrs.data(), capacity.data(),
-                                   compPtrs.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes),
-                                   (uint32_t*)sizes.data_ptr(), streamOf(dev)),
-        "floatReduceCompress", true);
-  return {std::move(comp), std::move(sizes), (int64_t)used};
-}
-
-// The sources of the mixed ops: a uint8 tensor is an archive; a tensor of the dtype float_type names is a RAW row
-// (1-D, contiguous, on the device); anything else is an error.  Accumulators as in decompress_data_reduce.
+// The reduce family (no reference ops): num_sources sources per accumulator, ts_in flattened member-major (source s of
+// accumulator i is ts_in[i * num_sources + s]), summed left to right in one launch, all or nothing per accumulator;
+// accumulate = false stores the first source: the accumulators are never read.  Eight ops over one implementation:
+//   * decompress_data_reduce{,_mixed,_scaled,_norm} leave the sums in ts_acc (float_type 1 / 2 / 3);
+//   * decompress_data_reduce_compress{,_mixed,_scaled,_norm} also compress_data_cast them in the same call (float_type 1 =
+//     float16 or 2 = bfloat16, of the sources and of the archives; output conventions of compress_data_cast);
+//   * plain: every source is a uint8 archive.  The others: a uint8 tensor is an archive, a tensor of the dtype float_type
+//     names a RAW row (1-D, contiguous, on the device), anything else an error;
+//   * _scaled: the sums are multiplied by `scale` in the reduce kernel -- a float32 value (ops.py rounds it once), finite
+//     and not zero, as the C ABI demands;
+//   * _norm: the scaled ops that also report, per accumulator, the squared norm (float64) and the non-finite count (int32)
+//     of what the call leaves.  A scale of 1.0 is no scale.  Either output may be absent; with both absent the call is
+//     the scaled one.
 namespace {
-struct MixedTensors {
+enum class Reduce { kPlain, kMixed, kScaled, kNorm };
+const std::optional<at::Tensor> kAbsent;
+
+struct ReduceTensors {
   std::vector<const void*> inPtrs;
   std::vector<uint32_t> inBytes;
   std::vector<uint8_t> kinds;
@@ -737,11 +671,11 @@ struct MixedTensors {
   std::vector<uint32_t> capacity;
   int64_t maxWords = 0;
 };
-MixedTensors marshalMixed(const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tAccs, int64_t floatType, int dev) {
+ReduceTensors marshalReduce(const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tAccs, int64_t floatType, int dev, bool rawAllowed) {
   const at::ScalarType rawType = floatType == (int64_t)DGPU_FLOAT16 ? at::ScalarType::Half
       : (floatType == (int64_t)DGPU_BFLOAT16 ? at::ScalarType::BFloat16 : at::ScalarType::Float);
   const size_t n = tAccs.size();
-  MixedTensors m;
+  ReduceTensors m;
   m.inPtrs.resize(tIns.size());
   m.inBytes.resize(tIns.size());
   m.kinds.resize(tIns.size());
@@ -751,6 +685,7 @@ MixedTensors marshalMixed(const std::vector<at::Tensor>& tIns, const std::vector
     auto& t = tIns[k];
     TORCH_CHECK(t.device().is_cuda() && t.get_device() == dev && t.is_contiguous(), "dietgpu: sources must be contiguous tensors on one GPU");
     const bool raw = t.scalar_type() != at::ScalarType::Byte;
+    TORCH_CHECK(!raw || rawAllowed, "dietgpu: a source must be a uint8 archive");
     TORCH_CHECK(!raw || t.scalar_type() == rawType, "dietgpu: a source is a uint8 archive or a raw row of the dtype float_type names");
     TORCH_CHECK(!raw || t.dim() == 1, "dietgpu: a raw source must be 1-D");
     const int64_t bytes = t.numel() * (int64_t)t.element_size();
@@ -770,131 +705,7 @@ MixedTensors marshalMixed(const std::vector<at::Tensor>& tIns, const std::vector
   }
   return m;
 }
-}  // namespace
 
-// decompress_data_reduce with sources that are archives or raw rows (dgpu_float_decode_reduce_mixed).
-int64_t decompress_data_reduce_mixed(
-    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, bool accumulate,
-    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes) {
-  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
-  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
-  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
-  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
-  TORCH_CHECK(floatType >= (int64_t)DGPU_FLOAT16 && floatType <= (int64_t)DGPU_FLOAT32, "dietgpu: float_type must be 1, 2 or 3");
-  int dev = tIns.front().get_device();
-  c10::hip::HIPGuard guard(dev);
-  Temp tmp = tempOf(tempMem, dev);
-  const size_t n = tAccs.size();
-  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
-  validateStatus(outStatus, outSizes, (int64_t)n, dev);
-  size_t used = 0;
-  check(dgpu_float_decode_reduce_mixed(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
-                                       (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), m.accPtrs.data(),
-                                       m.capacity.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
-        "floatDecompressReduceMixed", true);
-  return (int64_t)used;
-}
-
-// decompress_data_reduce_compress with sources that are archives or raw rows (dgpu_float_reduce_compress_mixed).
-std::tuple<at::Tensor, at::Tensor, int64_t> decompress_data_reduce_compress_mixed(
-    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, bool accumulate,
-    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes,
-    const std::optional<at::Tensor>& outCompressed, const std::optional<at::Tensor>& outCompressedSizes) {
-  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
-  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
-  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
-  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
-  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
-  int dev = tIns.front().get_device();
-  c10::hip::HIPGuard guard(dev);
-  Temp tmp = tempOf(tempMem, dev);
-  const size_t n = tAccs.size();
-  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
-  validateStatus(outStatus, outSizes, (int64_t)n, dev);
-  at::Tensor comp, sizes;
-  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)m.maxWords), dev,
-                  tAccs[0].device(), comp, sizes);
-  std::vector<void*> compPtrs(n);
-  for (size_t i = 0; i < n; ++i) compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
-  size_t used = 0;
-  check(dgpu_float_reduce_compress_mixed(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
-                                         (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), m.accPtrs.data(),
-                                         m.capacity.data(), compPtrs.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes),
-                                         (uint32_t*)sizes.data_ptr(), streamOf(dev)),
-        "floatReduceCompressMixed", true);
-  return {std::move(comp), std::move(sizes), (int64_t)used};
-}
-
-// The scaled ops: `scale` is a float32 value (ops.py rounds it once); finite and not zero, as the C ABI demands.
-namespace {
-float checkedScale(double scale) {
-  const float f = (float)scale;
-  TORCH_CHECK(std::isfinite(f) && f != 0.0f, "dietgpu: scale must be finite and not zero");
-  return f;
-}
-}  // namespace
-
-// decompress_data_reduce_mixed whose sums are multiplied by `scale` in the reduce kernel (dgpu_float_decode_reduce_scaled).
-int64_t decompress_data_reduce_scaled(
-    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, double scale,
-    bool accumulate, const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus,
-    const std::optional<at::Tensor>& outSizes) {
-  const float f = checkedScale(scale);
-  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
-  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
-  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
-  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
-  TORCH_CHECK(floatType >= (int64_t)DGPU_FLOAT16 && floatType <= (int64_t)DGPU_FLOAT32, "dietgpu: float_type must be 1, 2 or 3");
-  int dev = tIns.front().get_device();
-  c10::hip::HIPGuard guard(dev);
-  Temp tmp = tempOf(tempMem, dev);
-  const size_t n = tAccs.size();
-  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
-  validateStatus(outStatus, outSizes, (int64_t)n, dev);
-  size_t used = 0;
-  check(dgpu_float_decode_reduce_scaled(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
-                                        (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), f, m.accPtrs.data(),
-                                        m.capacity.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
-        "floatDecompressReduceScaled", true);
-  return (int64_t)used;
-}
-
-// decompress_data_reduce_compress_mixed of the scaled sums (dgpu_float_reduce_compress_scaled).
-std::tuple<at::Tensor, at::Tensor, int64_t> decompress_data_reduce_compress_scaled(
-    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, double scale,
-    bool accumulate, const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus,
-    const std::optional<at::Tensor>& outSizes, const std::optional<at::Tensor>& outCompressed,
-    const std::optional<at::Tensor>& outCompressedSizes) {
-  const float f = checkedScale(scale);
-  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
-  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
-  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
-  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
-  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
-  int dev = tIns.front().get_device();
-  c10::hip::HIPGuard guard(dev);
-  Temp tmp = tempOf(tempMem, dev);
-  const size_t n = tAccs.size();
-  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
-  validateStatus(outStatus, outSizes, (int64_t)n, dev);
-  at::Tensor comp, sizes;
-  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)m.maxWords), dev,
-                  tAccs[0].device(), comp, sizes);
-  std::vector<void*> compPtrs(n);
-  for (size_t i = 0; i < n; ++i) compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
-  size_t used = 0;
-  check(dgpu_float_reduce_compress_scaled(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
-                                          (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), f, m.accPtrs.data(),
-                                          m.capacity.data(), compPtrs.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes),
-                                          (uint32_t*)sizes.data_ptr(), streamOf(dev)),
-        "floatReduceCompressScaled", true);
-  return {std::move(comp), std::move(sizes), (int64_t)used};
-}
-
-// The norm ops: the scaled ops that also report, per accumulator, the squared norm (float64) and the non-finite count
-// (int32) of what the call leaves (dgpu_float_decode_reduce_norm, dgpu_float_reduce_compress_norm).  A scale of 1.0 is no
-// scale.  Either output may be absent; with both absent the call is the scaled one.
-namespace {
 void validateNorm(const std::optional<at::Tensor>& outSumSq, const std::optional<at::Tensor>& outNonFinite, int64_t n, int dev) {
   if (outSumSq) {
     TORCH_CHECK(outSumSq->scalar_type() == at::ScalarType::Double, "dietgpu: out_sumsq must be a float64 tensor");
@@ -907,66 +718,139 @@ void validateNorm(const std::optional<at::Tensor>& outSumSq, const std::optional
     TORCH_CHECK(outNonFinite->device().is_cuda() && outNonFinite->get_device() == dev, "dietgpu: out_nonfinite must be on the GPU of the other tensors");
   }
 }
+
+// -> (comp, sizes, temp bytes used); without `compress` the two tensors are undefined.
+std::tuple<at::Tensor, at::Tensor, int64_t> reduceCall(
+    Reduce kind, bool compress, const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType,
+    double scale, bool accumulate, const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus,
+    const std::optional<at::Tensor>& outSizes, const std::optional<at::Tensor>& outCompressed = kAbsent,
+    const std::optional<at::Tensor>& outCompressedSizes = kAbsent, const std::optional<at::Tensor>& outSumSq = kAbsent,
+    const std::optional<at::Tensor>& outNonFinite = kAbsent) {
+  const float f = (float)scale;
+  TORCH_CHECK(kind < Reduce::kScaled || (std::isfinite(f) && f != 0.0f), "dietgpu: scale must be finite and not zero");
+  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
+  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
+  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  if (compress) {
+    TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
+  } else {
+    TORCH_CHECK(floatType >= (int64_t)DGPU_FLOAT16 && floatType <= (int64_t)DGPU_FLOAT32, "dietgpu: float_type must be 1, 2 or 3");
+  }
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tAccs.size();
+  ReduceTensors m = marshalReduce(tIns, tAccs, floatType, dev, kind != Reduce::kPlain);
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  if (kind == Reduce::kNorm) validateNorm(outSumSq, outNonFinite, (int64_t)n, dev);
+  at::Tensor comp, sizes;
+  std::vector<void*> compPtrs(compress ? n : 0);
+  if (compress) {
+    validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)m.maxWords), dev,
+                    tAccs[0].device(), comp, sizes);
+    for (size_t i = 0; i < n; ++i) compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
+  }
+  size_t used = 0;
+  const uint32_t ft = (uint32_t)floatType, B = (uint32_t)n, S = (uint32_t)numSources;
+  const int P = precision(), acc = accumulate ? 1 : 0;
+  const void* const* in = m.inPtrs.data();
+  const uint32_t* inBytes = m.inBytes.data();
+  const uint8_t* kinds = m.kinds.data();
+  void* const* accs = m.accPtrs.data();
+  const uint32_t* cap = m.capacity.data();
+  uint8_t* status = ptrOrNull<uint8_t>(outStatus);
+  uint32_t* words = ptrOrNull<uint32_t>(outSizes);
+  uint32_t* archBytes = compress ? (uint32_t*)sizes.data_ptr() : nullptr;
+  double* sumSq = ptrOrNull<double>(outSumSq);
+  uint32_t* nonFinite = ptrOrNull<uint32_t>(outNonFinite);
+  void* stream = streamOf(dev);
+  // (each op calls the entry point of its own name)
+  if (!compress) {
+    switch (kind) {
+      case Reduce::kPlain:
+        check(dgpu_float_decode_reduce(tmp.ptr, tmp.bytes, &used, ft, P, acc, B, S, in, inBytes, accs, cap, status, words, stream), "floatDecompressReduce", true);
+        break;
+      case Reduce::kMixed:
+        check(dgpu_float_decode_reduce_mixed(tmp.ptr, tmp.bytes, &used, ft, P, acc, B, S, in, inBytes, kinds, accs, cap, status, words, stream),
+              "floatDecompressReduceMixed", true);
+        break;
+      case Reduce::kScaled:
+        check(dgpu_float_decode_reduce_scaled(tmp.ptr, tmp.bytes, &used, ft, P, acc, B, S, in, inBytes, kinds, f, accs, cap, status, words, stream),
+              "floatDecompressReduceScaled", true);
+        break;
+      case Reduce::kNorm:
+        check(dgpu_float_decode_reduce_norm(tmp.ptr, tmp.bytes, &used, ft, P, acc, B, S, in, inBytes, kinds, f, accs, cap, status, words, sumSq, nonFinite, stream),
+              "floatDecompressReduceNorm", true);
+        break;
+    }
+  } else {
+    void* const* arch = compPtrs.data();
+    switch (kind) {
+      case Reduce::kPlain:
+        check(dgpu_float_reduce_compress(tmp.ptr, tmp.bytes, &used, ft, P, acc, B, S, in, inBytes, accs, cap, arch, status, words, archBytes, stream),
+              "floatReduceCompress", true);
+        break;
+      case Reduce::kMixed:
+        check(dgpu_float_reduce_compress_mixed(tmp.ptr, tmp.bytes, &used, ft, P, acc, B, S, in, inBytes, kinds, accs, cap, arch, status, words, archBytes, stream),
+              "floatReduceCompressMixed", true);
+        break;
+      case Reduce::kScaled:
+        check(dgpu_float_reduce_compress_scaled(tmp.ptr, tmp.bytes, &used, ft, P, acc, B, S, in, inBytes, kinds, f, accs, cap, arch, status, words, archBytes, stream),
+              "floatReduceCompressScaled", true);
+        break;
+      case Reduce::kNorm:
+        check(dgpu_float_reduce_compress_norm(tmp.ptr, tmp.bytes, &used, ft, P, acc, B, S, in, inBytes, kinds, f, accs, cap, arch, status, words, archBytes, sumSq,
+                                              nonFinite, stream),
+              "floatReduceCompressNorm", true);
+        break;
+    }
+  }
+  return {std::move(comp), std::move(sizes), (int64_t)used};
+}
 }  // namespace
 
-int64_t decompress_data_reduce_norm(
-    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, double scale,
-    bool accumulate, const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus,
-    const std::optional<at::Tensor>& outSizes, const std::optional<at::Tensor>& outSumSq, const std::optional<at::Tensor>& outNonFinite) {
-  const float f = checkedScale(scale);
-  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
-  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
-  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
-  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
-  TORCH_CHECK(floatType >= (int64_t)DGPU_FLOAT16 && floatType <= (int64_t)DGPU_FLOAT32, "dietgpu: float_type must be 1, 2 or 3");
-  int dev = tIns.front().get_device();
-  c10::hip::HIPGuard guard(dev);
-  Temp tmp = tempOf(tempMem, dev);
-  const size_t n = tAccs.size();
-  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
-  validateStatus(outStatus, outSizes, (int64_t)n, dev);
-  validateNorm(outSumSq, outNonFinite, (int64_t)n, dev);
-  size_t used = 0;
-  check(dgpu_float_decode_reduce_norm(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
-                                      (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), f, m.accPtrs.data(),
-                                      m.capacity.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes),
-                                      ptrOrNull<double>(outSumSq), ptrOrNull<uint32_t>(outNonFinite), streamOf(dev)),
-        "floatDecompressReduceNorm", true);
-  return (int64_t)used;
-}
+using Tensors = std::vector<at::Tensor>;
+using Opt = std::optional<at::Tensor>;
+using Compressed = std::tuple<at::Tensor, at::Tensor, int64_t>;
 
-std::tuple<at::Tensor, at::Tensor, int64_t> decompress_data_reduce_compress_norm(
-    const std::vector<at::Tensor>& tIns, int64_t numSources, const std::vector<at::Tensor>& tAccs, int64_t floatType, double scale,
-    bool accumulate, const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus,
-    const std::optional<at::Tensor>& outSizes, const std::optional<at::Tensor>& outCompressed,
-    const std::optional<at::Tensor>& outCompressedSizes, const std::optional<at::Tensor>& outSumSq,
-    const std::optional<at::Tensor>& outNonFinite) {
-  const float f = checkedScale(scale);
-  TORCH_CHECK(!tIns.empty() && !tAccs.empty());
-  TORCH_CHECK(numSources >= 1 && numSources <= 64, "dietgpu: num_sources must be between 1 and 64");
-  TORCH_CHECK(tIns.size() == tAccs.size() * (size_t)numSources, "dietgpu: ts_in holds num_sources tensors per accumulator");
-  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
-  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
-  int dev = tIns.front().get_device();
-  c10::hip::HIPGuard guard(dev);
-  Temp tmp = tempOf(tempMem, dev);
-  const size_t n = tAccs.size();
-  MixedTensors m = marshalMixed(tIns, tAccs, floatType, dev);
-  validateStatus(outStatus, outSizes, (int64_t)n, dev);
-  validateNorm(outSumSq, outNonFinite, (int64_t)n, dev);
-  at::Tensor comp, sizes;
-  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)m.maxWords), dev,
-                  tAccs[0].device(), comp, sizes);
-  std::vector<void*> compPtrs(n);
-  for (size_t i = 0; i < n; ++i) compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
-  size_t used = 0;
-  check(dgpu_float_reduce_compress_norm(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
-                                        (uint32_t)numSources, m.inPtrs.data(), m.inBytes.data(), m.kinds.data(), f, m.accPtrs.data(),
-                                        m.capacity.data(), compPtrs.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes),
-                                        (uint32_t*)sizes.data_ptr(), ptrOrNull<double>(outSumSq), ptrOrNull<uint32_t>(outNonFinite),
-                                        streamOf(dev)),
-        "floatReduceCompressNorm", true);
-  return {std::move(comp), std::move(sizes), (int64_t)used};
+int64_t decompress_data_reduce(const Tensors& tIns, int64_t numSources, const Tensors& tAccs, int64_t floatType, bool accumulate, const Opt& tempMem,
+                               const Opt& outStatus, const Opt& outSizes) {
+  return std::get<2>(reduceCall(Reduce::kPlain, false, tIns, numSources, tAccs, floatType, 1.0, accumulate, tempMem, outStatus, outSizes));
+}
+int64_t decompress_data_reduce_mixed(const Tensors& tIns, int64_t numSources, const Tensors& tAccs, int64_t floatType, bool accumulate, const Opt& tempMem,
+                                     const Opt& outStatus, const Opt& outSizes) {
+  return std::get<2>(reduceCall(Reduce::kMixed, false, tIns, numSources, tAccs, floatType, 1.0, accumulate, tempMem, outStatus, outSizes));
+}
+int64_t decompress_data_reduce_scaled(const Tensors& tIns, int64_t numSources, const Tensors& tAccs, int64_t floatType, double scale, bool accumulate,
+                                      const Opt& tempMem, const Opt& outStatus, const Opt& outSizes) {
+  return std::get<2>(reduceCall(Reduce::kScaled, false, tIns, numSources, tAccs, floatType, scale, accumulate, tempMem, outStatus, outSizes));
+}
+int64_t decompress_data_reduce_norm(const Tensors& tIns, int64_t numSources, const Tensors& tAccs, int64_t floatType, double scale, bool accumulate,
+                                    const Opt& tempMem, const Opt& outStatus, const Opt& outSizes, const Opt& outSumSq, const Opt& outNonFinite) {
+  return std::get<2>(reduceCall(Reduce::kNorm, false, tIns, numSources, tAccs, floatType, scale, accumulate, tempMem, outStatus, outSizes, kAbsent, kAbsent,
+                                outSumSq, outNonFinite));
+}
+Compressed decompress_data_reduce_compress(const Tensors& tIns, int64_t numSources, const Tensors& tAccs, int64_t floatType, bool accumulate,
+                                           const Opt& tempMem, const Opt& outStatus, const Opt& outSizes, const Opt& outCompressed,
+                                           const Opt& outCompressedSizes) {
+  return reduceCall(Reduce::kPlain, true, tIns, numSources, tAccs, floatType, 1.0, accumulate, tempMem, outStatus, outSizes, outCompressed, outCompressedSizes);
+}
+Compressed decompress_data_reduce_compress_mixed(const Tensors& tIns, int64_t numSources, const Tensors& tAccs, int64_t floatType, bool accumulate,
+                                                 const Opt& tempMem, const Opt& outStatus, const Opt& outSizes, const Opt& outCompressed,
+                                                 const Opt& outCompressedSizes) {
+  return reduceCall(Reduce::kMixed, true, tIns, numSources, tAccs, floatType, 1.0, accumulate, tempMem, outStatus, outSizes, outCompressed, outCompressedSizes);
+}
+Compressed decompress_data_reduce_compress_scaled(const Tensors& tIns, int64_t numSources, const Tensors& tAccs, int64_t floatType, double scale,
+                                                  bool accumulate, const Opt& tempMem, const Opt& outStatus, const Opt& outSizes,
+                                                  const Opt& outCompressed, const Opt& outCompressedSizes) {
+  return reduceCall(Reduce::kScaled, true, tIns, numSources, tAccs, floatType, scale, accumulate, tempMem, outStatus, outSizes, outCompressed, outCompressedSizes);
+}
+Compressed decompress_data_reduce_compress_norm(const Tensors& tIns, int64_t numSources, const Tensors& tAccs, int64_t floatType, double scale,
+                                                bool accumulate, const Opt& tempMem, const Opt& outStatus, const Opt& outSizes, const Opt& outCompressed,
+                                                const Opt& outCompressedSizes, const Opt& outSumSq, const Opt& outNonFinite) {
+  return reduceCall(Reduce::kNorm, true, tIns, numSources, tAccs, floatType, scale, accumulate, tempMem, outStatus, outSizes, outCompressed, outCompressedSizes,
+                    outSumSq, outNonFinite);
 }
 
 void set_precision(int64_t probBits) {

@@ -172,10 +172,16 @@ class GpuFloatCodec:
         ops.decompress_data_accumulate(rows, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype)
         return status
 
-    @staticmethod
-    def _norm_kwargs(norm):
+    def _reduce(self, name, mixed, rows_per_acc, accs, accumulate, scale, norm):
+        """The reduce call `name` of ops -> (status, what it returned).  The call's float type: with `mixed`, what a raw
+        row says it is; without one, what the last compress call held."""
+        from . import ops
+
+        dtype = next((t.dtype for rows in rows_per_acc for t in rows if t.dtype != torch.uint8), self.dtype) if mixed else self.dtype
         # (no `norm`: the call of ops is the one it always was)
-        return {} if norm is None else {"out_sumsq": norm[0], "out_nonfinite": norm[1]}
+        norm_kwargs = {} if norm is None else {"out_sumsq": norm[0], "out_nonfinite": norm[1]}
+        status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
+        return status, getattr(ops, name)(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=dtype, scale=scale, **norm_kwargs)
 
     def decompress_reduce(self, rows_per_acc, accs, accumulate, scale=None, norm=None):
         """rows_per_acc[i]: equally long lists of rows, summed left to right into (accumulate) or stored as their sum to
@@ -184,45 +190,22 @@ class GpuFloatCodec:
         `norm` (here and below): a pair (float64 [len(accs)], int32 [len(accs)]) of tensors that the same launch fills
         with the squared norm of the finite words it leaves and the count of the others -- of the accumulators here,
         of the archives in the reduce-compress methods"""
-        from . import ops
-
-        status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
-        ops.decompress_data_reduce(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype, scale=scale,
-                                   **self._norm_kwargs(norm))
-        return status
+        return self._reduce("decompress_data_reduce", False, rows_per_acc, accs, accumulate, scale, norm)[0]
 
     def decompress_reduce_compress(self, rows_per_acc, accs, accumulate, scale=None, norm=None):
         """decompress_reduce and compress_cast of the accumulators back to the rows' dtype in ONE call, without the cast's
         histogram pass over the accumulators -> (status, comp, sizes): as the two calls return them"""
-        from . import ops
-
-        status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
-        comp, sizes, _ = ops.decompress_data_reduce_compress(rows_per_acc, accs, accumulate, self.temp_mem, status, None,
-                                                             dtype=self.dtype, scale=scale, **self._norm_kwargs(norm))
+        status, (comp, sizes, _) = self._reduce("decompress_data_reduce_compress", False, rows_per_acc, accs, accumulate, scale, norm)
         return status, comp, sizes
-
-    def _mixed_dtype(self, rows_per_acc):
-        # (a raw row says what the call's float type is; without one, what the last compress call held)
-        return next((t.dtype for rows in rows_per_acc for t in rows if t.dtype != torch.uint8), self.dtype)
 
     def decompress_reduce_mixed(self, rows_per_acc, accs, accumulate, scale=None, norm=None):
         """decompress_reduce whose rows are uint8 archives or UNCOMPRESSED 1-D tensors of the rows' dtype, which are widened
         and added in their place -> status, one per accumulator"""
-        from . import ops
-
-        status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
-        ops.decompress_data_reduce_mixed(rows_per_acc, accs, accumulate, self.temp_mem, status, None, dtype=self._mixed_dtype(rows_per_acc),
-                                         scale=scale, **self._norm_kwargs(norm))
-        return status
+        return self._reduce("decompress_data_reduce_mixed", True, rows_per_acc, accs, accumulate, scale, norm)[0]
 
     def decompress_reduce_compress_mixed(self, rows_per_acc, accs, accumulate, scale=None, norm=None):
         """decompress_reduce_compress with rows as in decompress_reduce_mixed -> (status, comp, sizes)"""
-        from . import ops
-
-        status = torch.zeros((len(accs),), dtype=torch.uint8, device=accs[0].device)
-        comp, sizes, _ = ops.decompress_data_reduce_compress_mixed(rows_per_acc, accs, accumulate, self.temp_mem, status, None,
-                                                                   dtype=self._mixed_dtype(rows_per_acc), scale=scale,
-                                                                   **self._norm_kwargs(norm))
+        status, (comp, sizes, _) = self._reduce("decompress_data_reduce_compress_mixed", True, rows_per_acc, accs, accumulate, scale, norm)
         return status, comp, sizes
 
 

@@ -112,6 +112,23 @@ def _load_fast_ops():
     return torch.ops.dietgpu
 
 
+def _amd_op(prob_bits, name):
+    """torch.ops.dietgpu_amd.<name> (the ops beside the reference's ten) with the op library's precision set around the
+    call and put back, or None when the ctypes route serves this call: the route is off, or the library lacks the op."""
+    if _fast_ops(prob_bits) is None or not hasattr(torch.ops.dietgpu_amd, name):
+        return None
+    op = getattr(torch.ops.dietgpu_amd, name)
+
+    def call(*args):
+        torch.ops.dietgpu_amd.set_precision(prob_bits)
+        try:
+            return op(*args)
+        finally:
+            torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+
+    return call
+
+
 def _check(cond, msg="argument check failed"):
     if not cond:
         raise RuntimeError(msg)
@@ -336,12 +353,9 @@ def compress_data_cast(ts_in, dtype, temp_mem=None, out_compressed=None, out_com
     for t in ts_in:
         _check(t.is_cuda and t.is_contiguous() and t.get_device() == dev)
         _check(t.dtype == torch.float32, "the inputs of a cast call must be float32")
-    if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "compress_data_cast"):
-        torch.ops.dietgpu_amd.set_precision(prob_bits)
-        try:
-            return torch.ops.dietgpu_amd.compress_data_cast(ts_in, ft, temp_mem, out_compressed, out_compressed_sizes)
-        finally:
-            torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+    op = _amd_op(prob_bits, "compress_data_cast")
+    if op is not None:
+        return op(ts_in, ft, temp_mem, out_compressed, out_compressed_sizes)
     _, mx = _total_and_max(ts_in)
     rows, cols = len(ts_in), _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
     with torch.cuda.device(dev):
@@ -393,13 +407,9 @@ def compress_data_rolling(ts_in, counts_in, counts_out, dtype=None, temp_mem=Non
     rows = len(ts_in)
     _validate_counts(counts_in, rows, dev, "counts_in")
     _validate_counts(counts_out, rows, dev, "counts_out")
-    if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "compress_data_rolling"):
-        torch.ops.dietgpu_amd.set_precision(prob_bits)
-        try:
-            return torch.ops.dietgpu_amd.compress_data_rolling(ts_in, counts_in, counts_out, ft, cast, temp_mem, out_compressed,
-                                                               out_compressed_sizes)
-        finally:
-            torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+    op = _amd_op(prob_bits, "compress_data_rolling")
+    if op is not None:
+        return op(ts_in, counts_in, counts_out, ft, cast, temp_mem, out_compressed, out_compressed_sizes)
     _, mx = _total_and_max(ts_in)
     cols = _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
     with torch.cuda.device(dev):
@@ -586,14 +596,10 @@ def decompress_data_range(compress_as_float, ts_in, ts_out, first_block, num_blo
     first_block, num_blocks = list(first_block), list(num_blocks)
     _check(len(first_block) == len(ts_in) and len(num_blocks) == len(ts_in), "one first_block and num_blocks per tensor")
     _check(ts_in[0].is_cuda, "tensors must be on the GPU")
-    if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_range"):
+    op = _amd_op(prob_bits, "decompress_data_range")
+    if op is not None:
         # (the op makes the per-tensor checks below itself, and raises RuntimeError like them)
-        torch.ops.dietgpu_amd.set_precision(prob_bits)
-        try:
-            return torch.ops.dietgpu_amd.decompress_data_range(compress_as_float, ts_in, ts_out, first_block, num_blocks, temp_mem,
-                                                               out_status, out_decompressed_words)
-        finally:
-            torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+        return op(compress_as_float, ts_in, ts_out, first_block, num_blocks, temp_mem, out_status, out_decompressed_words)
     dev = ts_in[0].get_device()
     for f in first_block:
         _check(0 <= f <= _U32_MAX, "first_block out of range")
@@ -649,13 +655,9 @@ def decompress_data_accumulate(ts_in, ts_acc, accumulate=True, temp_mem=None, ou
         else:
             ft = _header_info(True, ts_in[:1], tp, tb)[1][0]
             _check(ft in _FT_TO_DTYPE, "ts_in[0] is not a float archive")
-        if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_accumulate"):
-            torch.ops.dietgpu_amd.set_precision(prob_bits)
-            try:
-                return torch.ops.dietgpu_amd.decompress_data_accumulate(ts_in, ts_acc, ft, bool(accumulate), temp_mem, out_status,
-                                                                        out_sizes)
-            finally:
-                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+        op = _amd_op(prob_bits, "decompress_data_accumulate")
+        if op is not None:
+            return op(ts_in, ts_acc, ft, bool(accumulate), temp_mem, out_status, out_sizes)
         used = C.c_size_t(0)
         check(lib().dgpu_float_decode_accumulate(
             tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, _ptr_array(ts_in), _in_bytes(ts_in),
@@ -696,14 +698,10 @@ def decompress_data_scaled(ts_in, ts_out, scale, temp_mem=None, out_status=None,
     _check(ts_in[0].is_cuda, "tensors must be on the GPU")
     dev = ts_in[0].get_device()
     _check(dev_scale is None or dev_scale.get_device() == dev, "a tensor scale must be on the tensors' GPU")
-    if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_scaled"):
+    op = _amd_op(prob_bits, "decompress_data_scaled")
+    if op is not None:
         # (the op makes the per-tensor checks below itself, and raises RuntimeError like them)
-        torch.ops.dietgpu_amd.set_precision(prob_bits)
-        try:
-            return torch.ops.dietgpu_amd.decompress_data_scaled(ts_in, ts_out, host, dev_scale, temp_mem, out_status,
-                                                                out_decompressed_words)
-        finally:
-            torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
+        return op(ts_in, ts_out, host, dev_scale, temp_mem, out_status, out_decompressed_words)
     caps = _decode_capacities(True, ts_in, ts_out, dev, same_dtype=True)
     _validate_status(out_status, out_decompressed_words, n, dev)
     with torch.cuda.device(dev):
@@ -743,6 +741,95 @@ def _norm_outputs(out_sumsq, out_nonfinite, n, dev=None):
     return out_sumsq is not None or out_nonfinite is not None
 
 
+def _mixed_sources(ts_in, ts_acc, dtype, allowed, raw_allowed=True):
+    """Checks of the reduce calls -> (flat member-major sources, sources per accumulator, device, float type or None).
+    A uint8 tensor is an archive; with `raw_allowed`, a 1-D tensor of the call's float dtype is a raw row.  The float type
+    is `dtype`, else that of the first raw row, else None (the caller reads it from the first archive's header)."""
+    _check(len(ts_in) > 0)
+    _check(len(ts_in) == len(ts_acc), "one list of sources per accumulator")
+    sources = len(ts_in[0])
+    _check(1 <= sources <= MAX_REDUCE_SOURCES, "between 1 and 64 sources per accumulator")
+    for srcs in ts_in:
+        _check(len(srcs) == sources, "every accumulator takes the same number of sources")
+    flat = [t for srcs in ts_in for t in srcs]  # member-major
+    _check(flat[0].is_cuda, "tensors must be on the GPU")
+    dev = flat[0].get_device()
+    if dtype is not None and dtype not in allowed:  # (the message is not built for a call that passes)
+        _check(False, "dtype must be one of " + ", ".join(str(d).replace("torch.", "") for d in allowed))
+    if dtype is None:
+        dtype = next((t.dtype for t in flat if t.dtype != torch.uint8), None)
+    # (these two loops are most of a warm call's host time: the checks that pass make no function call)
+    for ti in flat:
+        if not (ti.is_cuda and ti.get_device() == dev and ti.is_contiguous()):
+            raise RuntimeError("sources must be contiguous tensors on one GPU")
+        if ti.dtype != torch.uint8:
+            _check(raw_allowed, "sources must be uint8 archives")
+            _check(ti.dtype == dtype and dtype in allowed, "a source is a uint8 archive or a raw row of the call's float dtype")
+            _check(ti.dim() == 1, "a raw source must be 1-D")
+            _check(ti.numel() * ti.element_size() <= _U32_MAX)
+    for ta in ts_acc:
+        if not (ta.is_cuda and ta.get_device() == dev and ta.is_contiguous()):
+            raise RuntimeError("accumulators must be contiguous tensors on the GPU")
+        if ta.dtype != torch.float32:
+            raise RuntimeError("accumulators must be float32")
+        _check(ta.numel() <= _U32_MAX)
+    return flat, sources, dev, (_DTYPE_TO_FT[dtype] if dtype is not None else None)
+
+
+def _source_kinds(flat):
+    return _cached_array(C.c_uint8, tuple(0 if t.dtype == torch.uint8 else 1 for t in flat))
+
+
+# (norm outputs given, scale given, raw rows allowed) -> what the names of the torch op and of the C entry point end in.
+# The norm kernels are forms of the scaled ones and the scaled of the mixed, which take all-archive members as well.
+_REDUCE_ENTRY = {
+    (False, False, False): "", (False, False, True): "_mixed",
+    (False, True, False): "_scaled", (False, True, True): "_scaled",
+    (True, False, False): "_norm", (True, False, True): "_norm", (True, True, False): "_norm", (True, True, True): "_norm",
+}
+
+
+def _reduce_call(ts_in, ts_acc, raw_allowed, compress, accumulate, temp_mem, out_status, out_sizes, out_compressed,
+                 out_compressed_sizes, prob_bits, dtype, scale, out_sumsq, out_nonfinite):
+    """The eight reduce calls: dgpu_float_decode_reduce{,_mixed,_scaled,_norm}, or with `compress`
+    dgpu_float_reduce_compress{,_mixed,_scaled,_norm}, through the torch op of the same name where there is one
+    -> temp bytes used, or with `compress` (comp, sizes, temp bytes used).  Every argument is checked here, once."""
+    scale = _scale32(scale)
+    norm = _norm_outputs(out_sumsq, out_nonfinite, len(ts_acc))
+    allowed = (torch.float16, torch.bfloat16) if compress else (torch.float16, torch.bfloat16, torch.float32)
+    flat, sources, dev, ft = _mixed_sources(ts_in, ts_acc, dtype, allowed, raw_allowed)
+    n = len(ts_acc)
+    _validate_status(out_status, out_sizes, n, dev)
+    if norm:  # (now that the device is known)
+        _norm_outputs(out_sumsq, out_nonfinite, n, dev)
+    entry = _REDUCE_ENTRY[norm, scale is not None, raw_allowed]
+    factor = [] if not (norm or scale is not None) else [1.0 if scale is None else scale]
+    norm_out = [out_sumsq, out_nonfinite] if norm else []
+    with torch.cuda.device(dev):
+        tp, tb = _temp(temp_mem, dev)
+        if ft is None:
+            ft = _header_info(True, flat[:1], tp, tb)[1][0]
+            _check(_FT_TO_DTYPE.get(ft) in allowed, "ts_in[0][0] is not a float16 / bfloat16 archive" if compress else "ts_in[0][0] is not a float archive")
+        op = _amd_op(prob_bits, ("decompress_data_reduce_compress" if compress else "decompress_data_reduce") + entry)
+        if op is not None:
+            return op(flat, sources, ts_acc, ft, *factor, bool(accumulate), temp_mem, out_status, out_sizes,
+                      *([out_compressed, out_compressed_sizes] if compress else []), *norm_out)
+        caps = _u32_array([t.numel() for t in ts_acc])
+        archives, archive_sizes = [], []
+        if compress:
+            _, mx = _total_and_max(ts_acc)
+            cols = _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
+            comp, sizes = _validate_out(out_compressed, out_compressed_sizes, n, cols, dev, ts_acc[0].device)
+            row = comp.size(1)
+            archives, archive_sizes = [(C.c_void_p * n)(*[comp.data_ptr() + i * row for i in range(n)])], [_ptr(sizes)]
+        used = C.c_size_t(0)
+        check(getattr(lib(), ("dgpu_float_reduce_compress" if compress else "dgpu_float_decode_reduce") + entry)(
+            tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
+            *([_source_kinds(flat)] if entry else []), *factor, _ptr_array(ts_acc), caps, *archives, _ptr(out_status), _ptr(out_sizes),
+            *archive_sizes, *[_ptr(t) for t in norm_out], _stream()))
+    return (comp, sizes, int(used.value)) if compress else int(used.value)
+
+
 def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
                            prob_bits=K_DEFAULT_PRECISION, dtype=None, scale=None, out_sumsq=None, out_nonfinite=None):
     """Sums SEVERAL float archives per accumulator in one launch: ts_in is a list, one entry per accumulator, of equally
@@ -766,50 +853,8 @@ def decompress_data_reduce(ts_in, ts_acc, accumulate=False, temp_mem=None, out_s
     within relative words * 2**-52 of the exact value) and the number of words that are inf or NaN -- what clipping by
     global norm and the overflow check of loss scaling otherwise read the shard again for.  A member with out_status 0
     gets 0.0 and 0.  The same call leaves the same bits every time."""
-    scale = _scale32(scale)
-    norm = _norm_outputs(out_sumsq, out_nonfinite, len(ts_acc))
-    _check(len(ts_in) > 0)
-    _check(len(ts_in) == len(ts_acc), "one list of sources per accumulator")
-    sources = len(ts_in[0])
-    _check(1 <= sources <= MAX_REDUCE_SOURCES, "between 1 and 64 sources per accumulator")
-    for srcs in ts_in:
-        _check(len(srcs) == sources, "every accumulator takes the same number of sources")
-    flat = [t for srcs in ts_in for t in srcs]  # member-major
-    _check(flat[0].is_cuda, "tensors must be on the GPU")
-    dev = flat[0].get_device()
-    for ti in flat:
-        _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous() and ti.dtype == torch.uint8)
-    for ta in ts_acc:
-        _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
-        _check(ta.dtype == torch.float32, "accumulators must be float32")
-        _check(ta.numel() <= _U32_MAX)
-    if norm:  # the norm kernels are forms of the scaled ones
-        return decompress_data_reduce_mixed(ts_in, ts_acc, accumulate, temp_mem, out_status, out_sizes, prob_bits, dtype, scale=scale,
-                                            out_sumsq=out_sumsq, out_nonfinite=out_nonfinite)
-    if scale is not None:  # the scaled kernels are forms of the mixed ones, which take all-archive members as well
-        return decompress_data_reduce_mixed(ts_in, ts_acc, accumulate, temp_mem, out_status, out_sizes, prob_bits, dtype, scale=scale)
-    n = len(ts_acc)
-    _validate_status(out_status, out_sizes, n, dev)
-    with torch.cuda.device(dev):
-        tp, tb = _temp(temp_mem, dev)
-        if dtype is not None:
-            _check(dtype in _DTYPE_TO_FT, "dtype must be float16, bfloat16 or float32")
-            ft = _DTYPE_TO_FT[dtype]
-        else:
-            ft = _header_info(True, flat[:1], tp, tb)[1][0]
-            _check(ft in _FT_TO_DTYPE, "ts_in[0][0] is not a float archive")
-        if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce"):
-            torch.ops.dietgpu_amd.set_precision(prob_bits)
-            try:
-                return torch.ops.dietgpu_amd.decompress_data_reduce(flat, sources, ts_acc, ft, bool(accumulate), temp_mem,
-                                                                    out_status, out_sizes)
-            finally:
-                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
-        used = C.c_size_t(0)
-        check(lib().dgpu_float_decode_reduce(
-            tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
-            _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), _ptr(out_status), _ptr(out_sizes), _stream()))
-    return int(used.value)
+    return _reduce_call(ts_in, ts_acc, False, False, accumulate, temp_mem, out_status, out_sizes, None, None, prob_bits, dtype, scale,
+                        out_sumsq, out_nonfinite)
 
 
 # ---------------------------------------------------------------- reduce-compress
@@ -829,94 +874,12 @@ def decompress_data_reduce_compress(ts_in, ts_acc, accumulate=False, temp_mem=No
     those of the scaled sums, rounded once.  `out_sumsq` / `out_nonfinite` as in decompress_data_reduce, but of the words
     of the ARCHIVES -- the sums rounded to `dtype` -- which is the tensor every rank holds after the all-gather: a float32
     sum that is finite and rounds to a float16 infinity counts as non-finite."""
-    scale = _scale32(scale)
-    norm = _norm_outputs(out_sumsq, out_nonfinite, len(ts_acc))
-    _check(len(ts_in) > 0)
-    _check(len(ts_in) == len(ts_acc), "one list of sources per accumulator")
-    sources = len(ts_in[0])
-    _check(1 <= sources <= MAX_REDUCE_SOURCES, "between 1 and 64 sources per accumulator")
-    for srcs in ts_in:
-        _check(len(srcs) == sources, "every accumulator takes the same number of sources")
-    flat = [t for srcs in ts_in for t in srcs]  # member-major
-    _check(flat[0].is_cuda, "tensors must be on the GPU")
-    dev = flat[0].get_device()
-    for ti in flat:
-        _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous() and ti.dtype == torch.uint8)
-    for ta in ts_acc:
-        _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
-        _check(ta.dtype == torch.float32, "accumulators must be float32")
-    _check(dtype is None or dtype in (torch.float16, torch.bfloat16), "dtype (of sources and archives) must be float16 or bfloat16")
-    if norm:  # the norm kernels are forms of the scaled ones
-        return decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate, temp_mem, out_status, out_sizes, out_compressed,
-                                                     out_compressed_sizes, prob_bits, dtype, scale=scale, out_sumsq=out_sumsq,
-                                                     out_nonfinite=out_nonfinite)
-    if scale is not None:  # the scaled kernels are forms of the mixed ones, which take all-archive members as well
-        return decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate, temp_mem, out_status, out_sizes, out_compressed,
-                                                     out_compressed_sizes, prob_bits, dtype, scale=scale)
-    n = len(ts_acc)
-    _validate_status(out_status, out_sizes, n, dev)
-    with torch.cuda.device(dev):
-        tp, tb = _temp(temp_mem, dev)
-        if dtype is not None:
-            ft = _DTYPE_TO_FT[dtype]
-        else:
-            ft = _header_info(True, flat[:1], tp, tb)[1][0]
-            _check(ft in (_DTYPE_TO_FT[torch.float16], _DTYPE_TO_FT[torch.bfloat16]), "ts_in[0][0] is not a float16 / bfloat16 archive")
-        if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_compress"):
-            torch.ops.dietgpu_amd.set_precision(prob_bits)
-            try:
-                return torch.ops.dietgpu_amd.decompress_data_reduce_compress(flat, sources, ts_acc, ft, bool(accumulate), temp_mem,
-                                                                             out_status, out_sizes, out_compressed, out_compressed_sizes)
-            finally:
-                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
-        _, mx = _total_and_max(ts_acc)
-        cols = _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
-        comp, sizes = _validate_out(out_compressed, out_compressed_sizes, n, cols, dev, ts_acc[0].device)
-        row = comp.size(1)
-        out_ptrs = (C.c_void_p * n)(*[comp.data_ptr() + i * row for i in range(n)])
-        used = C.c_size_t(0)
-        check(lib().dgpu_float_reduce_compress(
-            tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
-            _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), out_ptrs, _ptr(out_status), _ptr(out_sizes), _ptr(sizes),
-            _stream()))
-    return comp, sizes, int(used.value)
+    return _reduce_call(ts_in, ts_acc, False, True, accumulate, temp_mem, out_status, out_sizes, out_compressed, out_compressed_sizes,
+                        prob_bits, dtype, scale, out_sumsq, out_nonfinite)
 
 
 # ------------------------------------------------------------------ mixed sources
 # (no reference ops: dgpu_float_decode_reduce_mixed / dgpu_float_reduce_compress_mixed, include/dietgpu_amd.h)
-def _mixed_sources(ts_in, ts_acc, dtype, allowed):
-    """Checks of the two mixed calls -> (flat member-major sources, sources per accumulator, device, float type or None).
-    A uint8 tensor is an archive; a 1-D tensor of the call's float dtype a raw row.  The float type is `dtype`, else that
-    of the first raw row, else None (the caller reads it from the first archive's header)."""
-    _check(len(ts_in) > 0)
-    _check(len(ts_in) == len(ts_acc), "one list of sources per accumulator")
-    sources = len(ts_in[0])
-    _check(1 <= sources <= MAX_REDUCE_SOURCES, "between 1 and 64 sources per accumulator")
-    for srcs in ts_in:
-        _check(len(srcs) == sources, "every accumulator takes the same number of sources")
-    flat = [t for srcs in ts_in for t in srcs]  # member-major
-    _check(flat[0].is_cuda, "tensors must be on the GPU")
-    dev = flat[0].get_device()
-    _check(dtype is None or dtype in allowed, "dtype must be one of " + ", ".join(str(d).replace("torch.", "") for d in allowed))
-    if dtype is None:
-        dtype = next((t.dtype for t in flat if t.dtype != torch.uint8), None)
-    for ti in flat:
-        _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous(), "sources must be contiguous tensors on one GPU")
-        if ti.dtype != torch.uint8:
-            _check(ti.dtype == dtype and dtype in allowed, "a source is a uint8 archive or a raw row of the call's float dtype")
-            _check(ti.dim() == 1, "a raw source must be 1-D")
-            _check(ti.numel() * ti.element_size() <= _U32_MAX)
-    for ta in ts_acc:
-        _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
-        _check(ta.dtype == torch.float32, "accumulators must be float32")
-        _check(ta.numel() <= _U32_MAX)
-    return flat, sources, dev, (_DTYPE_TO_FT[dtype] if dtype is not None else None)
-
-
-def _source_kinds(flat):
-    return _cached_array(C.c_uint8, tuple(0 if t.dtype == torch.uint8 else 1 for t in flat))
-
-
 def decompress_data_reduce_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
                                  prob_bits=K_DEFAULT_PRECISION, dtype=None, scale=None, out_sumsq=None, out_nonfinite=None):
     """`decompress_data_reduce` whose sources may be UNCOMPRESSED: an entry of ts_in[i] is a uint8 archive or a raw row --
@@ -926,59 +889,8 @@ def decompress_data_reduce_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None,
     reported in out_sizes[i] when it is the first source).  Raw rows must not overlap the accumulators.  `dtype`: given,
     else that of the first raw row, else read from the header of the first archive -> temp bytes used (0; with the norm
     outputs, their tile partials).  `scale`, `out_sumsq` and `out_nonfinite` as in decompress_data_reduce."""
-    scale = _scale32(scale)
-    norm = _norm_outputs(out_sumsq, out_nonfinite, len(ts_acc))
-    flat, sources, dev, ft = _mixed_sources(ts_in, ts_acc, dtype, (torch.float16, torch.bfloat16, torch.float32))
-    n = len(ts_acc)
-    _validate_status(out_status, out_sizes, n, dev)
-    _norm_outputs(out_sumsq, out_nonfinite, n, dev)
-    with torch.cuda.device(dev):
-        tp, tb = _temp(temp_mem, dev)
-        if ft is None:
-            ft = _header_info(True, flat[:1], tp, tb)[1][0]
-            _check(ft in _FT_TO_DTYPE, "ts_in[0][0] is not a float archive")
-        if norm:
-            factor = 1.0 if scale is None else scale
-            if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_norm"):
-                torch.ops.dietgpu_amd.set_precision(prob_bits)
-                try:
-                    return torch.ops.dietgpu_amd.decompress_data_reduce_norm(flat, sources, ts_acc, ft, factor, bool(accumulate), temp_mem,
-                                                                             out_status, out_sizes, out_sumsq, out_nonfinite)
-                finally:
-                    torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
-            used = C.c_size_t(0)
-            check(lib().dgpu_float_decode_reduce_norm(
-                tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
-                _source_kinds(flat), factor, _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), _ptr(out_status),
-                _ptr(out_sizes), _ptr(out_sumsq), _ptr(out_nonfinite), _stream()))
-            return int(used.value)
-        if scale is not None:
-            if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_scaled"):
-                torch.ops.dietgpu_amd.set_precision(prob_bits)
-                try:
-                    return torch.ops.dietgpu_amd.decompress_data_reduce_scaled(flat, sources, ts_acc, ft, scale, bool(accumulate),
-                                                                               temp_mem, out_status, out_sizes)
-                finally:
-                    torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
-            used = C.c_size_t(0)
-            check(lib().dgpu_float_decode_reduce_scaled(
-                tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
-                _source_kinds(flat), scale, _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), _ptr(out_status),
-                _ptr(out_sizes), _stream()))
-            return int(used.value)
-        if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_mixed"):
-            torch.ops.dietgpu_amd.set_precision(prob_bits)
-            try:
-                return torch.ops.dietgpu_amd.decompress_data_reduce_mixed(flat, sources, ts_acc, ft, bool(accumulate), temp_mem,
-                                                                          out_status, out_sizes)
-            finally:
-                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
-        used = C.c_size_t(0)
-        check(lib().dgpu_float_decode_reduce_mixed(
-            tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
-            _source_kinds(flat), _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), _ptr(out_status), _ptr(out_sizes),
-            _stream()))
-    return int(used.value)
+    return _reduce_call(ts_in, ts_acc, True, False, accumulate, temp_mem, out_status, out_sizes, None, None, prob_bits, dtype, scale,
+                        out_sumsq, out_nonfinite)
 
 
 def decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate=False, temp_mem=None, out_status=None, out_sizes=None,
@@ -987,69 +899,8 @@ def decompress_data_reduce_compress_mixed(ts_in, ts_acc, accumulate=False, temp_
     """`decompress_data_reduce_compress` whose sources may be uncompressed rows, as in decompress_data_reduce_mixed (every
     source, raw or not, must hold EXACTLY ts_acc[i].numel() words) -> (comp, sizes, temp bytes used).  `dtype`: float16 or
     bfloat16.  `scale`, `out_sumsq` and `out_nonfinite` as in decompress_data_reduce_compress."""
-    scale = _scale32(scale)
-    norm = _norm_outputs(out_sumsq, out_nonfinite, len(ts_acc))
-    flat, sources, dev, ft = _mixed_sources(ts_in, ts_acc, dtype, (torch.float16, torch.bfloat16))
-    n = len(ts_acc)
-    _validate_status(out_status, out_sizes, n, dev)
-    _norm_outputs(out_sumsq, out_nonfinite, n, dev)
-    with torch.cuda.device(dev):
-        tp, tb = _temp(temp_mem, dev)
-        if ft is None:
-            ft = _header_info(True, flat[:1], tp, tb)[1][0]
-            _check(ft in (_DTYPE_TO_FT[torch.float16], _DTYPE_TO_FT[torch.bfloat16]), "ts_in[0][0] is not a float16 / bfloat16 archive")
-        if norm:
-            factor = 1.0 if scale is None else scale
-            if _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_compress_norm"):
-                torch.ops.dietgpu_amd.set_precision(prob_bits)
-                try:
-                    return torch.ops.dietgpu_amd.decompress_data_reduce_compress_norm(
-                        flat, sources, ts_acc, ft, factor, bool(accumulate), temp_mem, out_status, out_sizes, out_compressed,
-                        out_compressed_sizes, out_sumsq, out_nonfinite)
-                finally:
-                    torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
-            _, mx = _total_and_max(ts_acc)
-            cols = _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
-            comp, sizes = _validate_out(out_compressed, out_compressed_sizes, n, cols, dev, ts_acc[0].device)
-            row = comp.size(1)
-            out_ptrs = (C.c_void_p * n)(*[comp.data_ptr() + i * row for i in range(n)])
-            used = C.c_size_t(0)
-            check(lib().dgpu_float_reduce_compress_norm(
-                tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
-                _source_kinds(flat), factor, _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), out_ptrs, _ptr(out_status),
-                _ptr(out_sizes), _ptr(sizes), _ptr(out_sumsq), _ptr(out_nonfinite), _stream()))
-            return comp, sizes, int(used.value)
-        if scale is not None and _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_compress_scaled"):
-            torch.ops.dietgpu_amd.set_precision(prob_bits)
-            try:
-                return torch.ops.dietgpu_amd.decompress_data_reduce_compress_scaled(
-                    flat, sources, ts_acc, ft, scale, bool(accumulate), temp_mem, out_status, out_sizes, out_compressed, out_compressed_sizes)
-            finally:
-                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
-        if scale is None and _fast_ops(prob_bits) is not None and hasattr(torch.ops.dietgpu_amd, "decompress_data_reduce_compress_mixed"):
-            torch.ops.dietgpu_amd.set_precision(prob_bits)
-            try:
-                return torch.ops.dietgpu_amd.decompress_data_reduce_compress_mixed(
-                    flat, sources, ts_acc, ft, bool(accumulate), temp_mem, out_status, out_sizes, out_compressed, out_compressed_sizes)
-            finally:
-                torch.ops.dietgpu_amd.set_precision(K_DEFAULT_PRECISION)
-        _, mx = _total_and_max(ts_acc)
-        cols = _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
-        comp, sizes = _validate_out(out_compressed, out_compressed_sizes, n, cols, dev, ts_acc[0].device)
-        row = comp.size(1)
-        out_ptrs = (C.c_void_p * n)(*[comp.data_ptr() + i * row for i in range(n)])
-        used = C.c_size_t(0)
-        if scale is not None:
-            check(lib().dgpu_float_reduce_compress_scaled(
-                tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
-                _source_kinds(flat), scale, _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), out_ptrs, _ptr(out_status),
-                _ptr(out_sizes), _ptr(sizes), _stream()))
-            return comp, sizes, int(used.value)
-        check(lib().dgpu_float_reduce_compress_mixed(
-            tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, sources, _ptr_array(flat), _in_bytes(flat),
-            _source_kinds(flat), _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), out_ptrs, _ptr(out_status),
-            _ptr(out_sizes), _ptr(sizes), _stream()))
-    return comp, sizes, int(used.value)
+    return _reduce_call(ts_in, ts_acc, True, True, accumulate, temp_mem, out_status, out_sizes, out_compressed, out_compressed_sizes,
+                        prob_bits, dtype, scale, out_sumsq, out_nonfinite)
 
 
 def _check_slice_args(compress_as_float, ts_in, dtype):

@@ -86,6 +86,17 @@ struct TempRegion {
   void* ptr;
   size_t used = 0;
 };
+// The temp region of a reduce call: what `tempBytes(maxWords)` asks for the largest of the call's capacities.
+struct ReduceTemp : TempRegion {
+  template <typename TempBytes>
+  ReduceTemp(StackDeviceMemory& r, hipStream_t s, const uint32_t* outCapacity, uint32_t numInBatch, TempBytes tempBytes)
+      : TempRegion(r, s, tempBytes(largest(outCapacity, numInBatch))) {}
+  static uint32_t largest(const uint32_t* v, uint32_t n) {
+    uint32_t m = 0;
+    for (uint32_t i = 0; i < n; ++i) m = std::max(m, v[i]);
+    return m;
+  }
+};
 }  // namespace detail
 
 inline void ansEncodeBatchStride(

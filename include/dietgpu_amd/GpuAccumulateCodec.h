@@ -78,9 +78,8 @@ inline void floatDecodeReduceNorm(
     StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, uint32_t numSources,
     const void** in, const uint32_t* inBytes, const uint8_t* sourceKind, float scale, float** out, const uint32_t* outCapacity,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, double* outSumSq_dev, uint32_t* outNonFinite_dev, hipStream_t stream) {
-  uint32_t maxWords = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) maxWords = std::max(maxWords, outCapacity[i]);
-  detail::TempRegion t(res, stream, dgpu_float_reduce_norm_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords, 0));
+  detail::ReduceTemp t(res, stream, outCapacity, numInBatch,
+                       [&](uint32_t maxWords) { return dgpu_float_reduce_norm_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords, 0); });
   detail::checkRc(dgpu_float_decode_reduce_norm(t.ptr, t.bytes, &t.used, (uint32_t)config.floatType, config.ansConfig.probBits,
                                                 accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, sourceKind, scale,
                                                 (void* const*)out, outCapacity, outSuccess_dev, outSize_dev, outSumSq_dev,

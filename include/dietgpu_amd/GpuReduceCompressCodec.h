@@ -18,9 +18,8 @@ inline void floatDecompressReduceCompress(
     StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, uint32_t numSources,
     const void** in, const uint32_t* inBytes, float** acc, const uint32_t* outCapacity, void** outArchive,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream) {
-  uint32_t maxWords = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) maxWords = std::max(maxWords, outCapacity[i]);
-  detail::TempRegion t(res, stream, dgpu_float_reduce_compress_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords));
+  detail::ReduceTemp t(res, stream, outCapacity, numInBatch,
+                       [&](uint32_t maxWords) { return dgpu_float_reduce_compress_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords); });
   detail::checkRc(dgpu_float_reduce_compress(t.ptr, t.bytes, &t.used, (uint32_t)config.floatType, config.ansConfig.probBits,
                                              accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, (void* const*)acc,
                                              outCapacity, outArchive, outSuccess_dev, outSize_dev, outArchiveSize_dev, stream),
@@ -34,9 +33,8 @@ inline void floatDecompressReduceCompressMixed(
     StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, uint32_t numSources,
     const void** in, const uint32_t* inBytes, const uint8_t* sourceKind, float** acc, const uint32_t* outCapacity, void** outArchive,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream) {
-  uint32_t maxWords = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) maxWords = std::max(maxWords, outCapacity[i]);
-  detail::TempRegion t(res, stream, dgpu_float_reduce_compress_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords));
+  detail::ReduceTemp t(res, stream, outCapacity, numInBatch,
+                       [&](uint32_t maxWords) { return dgpu_float_reduce_compress_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords); });
   detail::checkRc(dgpu_float_reduce_compress_mixed(t.ptr, t.bytes, &t.used, (uint32_t)config.floatType, config.ansConfig.probBits,
                                                    accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, sourceKind,
                                                    (void* const*)acc, outCapacity, outArchive, outSuccess_dev, outSize_dev,
@@ -51,9 +49,8 @@ inline void floatDecompressReduceCompressScaled(
     StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, uint32_t numSources,
     const void** in, const uint32_t* inBytes, const uint8_t* sourceKind, float scale, float** acc, const uint32_t* outCapacity,
     void** outArchive, uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, hipStream_t stream) {
-  uint32_t maxWords = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) maxWords = std::max(maxWords, outCapacity[i]);
-  detail::TempRegion t(res, stream, dgpu_float_reduce_compress_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords));
+  detail::ReduceTemp t(res, stream, outCapacity, numInBatch,
+                       [&](uint32_t maxWords) { return dgpu_float_reduce_compress_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords); });
   detail::checkRc(dgpu_float_reduce_compress_scaled(t.ptr, t.bytes, &t.used, (uint32_t)config.floatType, config.ansConfig.probBits,
                                                     accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, sourceKind, scale,
                                                     (void* const*)acc, outCapacity, outArchive, outSuccess_dev, outSize_dev,
@@ -70,9 +67,8 @@ inline void floatReduceCompressNorm(
     const void** in, const uint32_t* inBytes, const uint8_t* sourceKind, float scale, float** acc, const uint32_t* outCapacity,
     void** outArchive, uint8_t* outSuccess_dev, uint32_t* outSize_dev, uint32_t* outArchiveSize_dev, double* outSumSq_dev,
     uint32_t* outNonFinite_dev, hipStream_t stream) {
-  uint32_t maxWords = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) maxWords = std::max(maxWords, outCapacity[i]);
-  detail::TempRegion t(res, stream, dgpu_float_reduce_norm_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords, 1));
+  detail::ReduceTemp t(res, stream, outCapacity, numInBatch,
+                       [&](uint32_t maxWords) { return dgpu_float_reduce_norm_temp_bytes((uint32_t)config.floatType, numInBatch, maxWords, 1); });
   detail::checkRc(dgpu_float_reduce_compress_norm(t.ptr, t.bytes, &t.used, (uint32_t)config.floatType, config.ansConfig.probBits,
                                                   accumulate ? 1 : 0, numInBatch, numSources, in, inBytes, sourceKind, scale,
                                                   (void* const*)acc, outCapacity, outArchive, outSuccess_dev, outSize_dev,

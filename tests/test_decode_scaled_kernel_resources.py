@@ -76,4 +76,6 @@ def test_scaled_decoder_costs_no_occupancy_and_leaves_the_plain_decoder_alone(tm
 
 def test_the_launch_uses_the_lds_the_static_assert_speaks_of():
     text = open(os.path.join(ROOT, "dietgpu_amd", "csrc", "kernel_variants.h")).read()
-    assert '{k_ans_decode_scaled<kP, kScFT, kTB>, decThreads(kTB), decScaledLdsBytes(kP, kScFT, kTB), "k_ans_decode_scaled"}' in text
+    # (the row of the decode forms' table, and what every row of it becomes)
+    assert "X(kWholeScaled, k_ans_decode_scaled, floatsOnly, decScaledLdsBytes(P, T, TB))" in text
+    assert "return {kernel<P, T, TB>, decThreads(TB), ldsBytes, #kernel};" in text

@@ -11,7 +11,8 @@ of 2, 4 and 8 blocks, the 8-block ones with at most 32 tiles per element (wide s
 dispatch left to the policy, forced persistent and forced to the hardware; ordinary histogram loads; one batch of size
 classes (1 large + many small) and one ragged batch; a caller-supplied histogram; ranged decodes on 16-block and 4-block
 tiles and of nothing but empty requests; decode-accumulate as a rectangle and from a list; cast-compress as a rectangle,
-ragged and split into classes that hold single-block members.  The digest is over the lines (kernel name with its
+ragged and split into classes that hold single-block members; the reduce family (REDUCE_SHAPES, reduce_family below) on
+the ctypes route and on the torch route.  The digest is over the lines (kernel name with its
 template arguments, grid, workgroup size, LDS bytes) in launch order and, with --temp, the temp bytes every call of the
 list reported (tempUsed), in call order."""
 import argparse
@@ -26,6 +27,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 # (words per element, elements): one block; tiles of 2 / 4 blocks, more of them than fit on the chip at once; 8-block
 # tiles with 4 tiles per element; with 40 tiles per element, more tiles than resident workgroups
 SHAPES = [(3000, 64), (8000, 2048), (16000, 2048), (100000, 16), (40 * 32768, 64)]
+
+
+# The reduce family's batches (words per member): one 4-block tile each; two 16-block tiles each; a ragged batch that
+# planDecodeCall turns into a tile list ("equal_tiles_other_sizes" of tests/cpp/plan_dump.cpp); more members than
+# kAccElements (64), so that reduce-compress takes its counts, and the norm its partials, from temp memory.
+REDUCE_SHAPES = {
+    "4block": [8000] * 3,
+    "16block": [70000] * 3,
+    "ragged": [40000, 60000, 50000, 65536, 33000, 300000, 120000, 70000, 131072, 66000],
+    "b65": [8000] * 65,
+}
 
 
 def digest(db, lines_out, temp):
@@ -134,10 +146,83 @@ def main(temp_out):
         outs = [torch.empty([n], dtype=torch.bfloat16, device=dev) for n in words]
         used("decompress", dg.decompress_data(True, rows_of(comp, sizes), outs, False, prob_bits=10))
         assert all(torch.equal(o.view(torch.int16), t.to(torch.bfloat16).view(torch.int16)) for o, t in zip(outs, ts)), "cast-compress mismatch"
+    reduce_family(dg, torch, tensors, rows_of, used)
     if temp_out:
         with open(temp_out, "w") as f:
             f.write("\n".join(temp_lines) + "\n")
     print("launch sequence done")
+
+
+def reduce_family(dg, torch, tensors, rows_of, used):
+    """Decode-accumulate, scaled decompress and the eight reduce calls, each on both routes: S = 1 and 2; bf16 and fp16
+    (fp32: decode-reduce only); every form -- plain, mixed with and without a raw row, scale 1/3 and 1.0, norm with both
+    outputs (scaled), with one, and with scale 1.0; probBits 10, and 11 for one batch."""
+    dev = torch.device("cuda:0")
+    third = 1.0 / 3.0
+    s32 = torch.tensor(third, dtype=torch.float32).item()
+    # (keywords of the call beyond the sources; whether source S-1 of member 0 is passed as a raw row)
+    forms = [("plain", {}, False), ("mixed_raw", {}, True), ("mixed_archives", {}, None), ("scale_third", {"scale": third}, False),
+             ("scale_one", {"scale": 1.0}, False), ("norm_both", {"scale": third, "sumsq": True, "nonfinite": True}, False),
+             ("norm_one", {"nonfinite": True}, False), ("norm_scale_one", {"scale": 1.0, "sumsq": True, "nonfinite": True}, False)]
+
+    def sources(dtype, words, prob_bits):
+        ts = [tensors(dtype, words) for _ in range(2)]
+        rows = []
+        for t in ts:
+            comp, sizes, temp = dg.compress_data(True, t, False, prob_bits=prob_bits)
+            used("compress", temp)
+            rows.append(rows_of(comp, sizes))
+        return ts, rows
+
+    def reduce_calls(route, dtype, shape, ts, rows, prob_bits, compress):
+        words, n = REDUCE_SHAPES[shape], len(ts[0])
+        for S in (1, 2):
+            total = ts[0] if S == 1 else [a.float() + b.float() for a, b in zip(ts[0], ts[1])]
+            for name, kw, raw in forms:
+                src = [[rows[s][i] for s in range(S)] for i in range(n)]
+                if raw:
+                    src[0][S - 1] = ts[S - 1][0]
+                accs = [torch.full([w], 7.0, dtype=torch.float32, device=dev) for w in words]
+                status = torch.zeros([n], dtype=torch.uint8, device=dev)
+                extra = {"scale": kw["scale"]} if "scale" in kw else {}
+                if kw.get("sumsq"):
+                    extra["out_sumsq"] = torch.zeros([n], dtype=torch.float64, device=dev)
+                if kw.get("nonfinite"):
+                    extra["out_nonfinite"] = torch.ones([n], dtype=torch.int32, device=dev)
+                mixed = raw is not False
+                fn = getattr(dg, "decompress_data_reduce" + ("_compress" if compress else "") + ("_mixed" if mixed else ""))
+                out = fn(src, accs, False, None, status, None, prob_bits=prob_bits, dtype=dtype, **extra)
+                used(f"{fn.__name__} {route} {shape} {str(dtype)[6:]} S={S} {name}", out[2] if compress else out)
+                assert bool(status.all()), f"{fn.__name__} {name}: a member failed"
+                factor = s32 if kw.get("scale") == third else 1.0
+                for a, t in zip(accs, total):
+                    assert torch.equal(a, t.float() * factor), f"{fn.__name__} {name}: wrong sum"
+                if "out_nonfinite" in extra:
+                    assert int(extra["out_nonfinite"].sum()) == 0, f"{fn.__name__} {name}: non-finite words counted"
+
+    for route, torch_route in (("ctypes", False), ("torch", True)):
+        dg.ops.prefer_torch_ops(torch_route)
+        for dtype in (torch.bfloat16, torch.float16, torch.float32):
+            for shape, words in REDUCE_SHAPES.items():
+                if shape == "b65" and dtype == torch.float32:
+                    continue
+                ts, rows = sources(dtype, words, 10)
+                n = len(words)
+                if shape != "b65":
+                    accs = [torch.ones([w], dtype=torch.float32, device=dev) for w in words]
+                    used(f"decompress_accumulate {route} {shape}", dg.decompress_data_accumulate(rows[0], accs, True, prob_bits=10, dtype=dtype))
+                    assert all(torch.equal(a, t.float() + 1) for a, t in zip(accs, ts[0])), "decode-accumulate mismatch"
+                    for scale in (0.5, torch.full([1], 0.5, device=dev), torch.full([n], 0.5, device=dev)):
+                        outs = [torch.empty([w], dtype=dtype, device=dev) for w in words]
+                        used(f"decompress_scaled {route} {shape}", dg.decompress_data_scaled(rows[0], outs, scale, prob_bits=10))
+                        assert all(torch.equal(o, t * 0.5) for o, t in zip(outs, ts[0])), "scaled decompress mismatch"
+                    reduce_calls(route, dtype, shape, ts, rows, 10, False)
+                if dtype != torch.float32:
+                    reduce_calls(route, dtype, shape, ts, rows, 10, True)
+        ts, rows = sources(torch.bfloat16, REDUCE_SHAPES["4block"], 11)
+        for compress in (False, True):
+            reduce_calls(route, torch.bfloat16, "4block", ts, rows, 11, compress)
+    dg.ops.prefer_torch_ops(False)
 
 
 if __name__ == "__main__":
