@@ -11,6 +11,7 @@ from ._lib import DietGpuError, EXPORTED_SYMBOLS, lib  # noqa: F401
 from .ops import (  # noqa: F401
     compress_data,
     compress_data_cast,
+    compress_data_feedback,
     compress_data_rolling,
     compress_data_simple,
     compress_data_split_size,

@@ -726,7 +726,8 @@ uint32_t maxCompressedSizeHost(uint32_t bytes) {
 bool encodableSize(uint32_t symbols) { return symbols <= kMaxEncodableBytes; }
 
 // One call's batch as its entry point describes it: HOST arrays of device pointers and sizes (packed and uploaded as
-// [in ptrs][out ptrs][sizes][inBytes][work], the block the parameter cache hashes) or, when `strided`, two stride views.
+// [in ptrs][out ptrs][sizes][inBytes][work][residual ptrs], the block the parameter cache hashes) or, when `strided`, two
+// stride views.
 struct Batch {
   uint32_t n = 0;  // elements
   bool strided = false;
@@ -737,6 +738,8 @@ struct Batch {
   uint32_t uniformInBytes = 0;    // ... of a strided decode (0 = unknown)
   std::vector<uint32_t> work;     // work lists of a batch whose elements differ widely in size (work_plan.h)
   uint32_t maxSize = 0;           // the largest size / capacity
+  // dgpu_float_feedback_compress: the residual that is added (empty: none yet) and the one that is stored, per element
+  std::vector<uint64_t> resInPtrs, resOutPtrs;
 };
 
 // One side of a batch as an entry point receives it: a HOST array of device pointers, or (ptrs == nullptr) a base and
@@ -824,12 +827,14 @@ struct DeviceBatch {
   BatchView in, out;
   const uint32_t* inBytes = nullptr;
   const uint32_t* work = nullptr;
+  BatchView resIn{}, resOut{};  // feedback calls (all zero: no such side)
   ParamLease lease;
 };
 
 int uploadParams(const Batch& b, bool sizesOnOut, StreamLease& stream, DeviceBatch* d) {
   const size_t outAt = b.inPtrs.size() * 8, sizesAt = outAt + b.outPtrs.size() * 8, inBytesAt = sizesAt + alignUp(b.sizes.size() * 4, 8),
-               workAt = inBytesAt + alignUp(b.inBytes.size() * 4, 8), bytes = workAt + alignUp(b.work.size() * 4, 8);
+               workAt = inBytesAt + alignUp(b.inBytes.size() * 4, 8), resInAt = workAt + alignUp(b.work.size() * 4, 8),
+               resOutAt = resInAt + b.resInPtrs.size() * 8, bytes = resOutAt + b.resOutPtrs.size() * 8;
   if (bytes == 0) return DGPU_OK;
   static thread_local std::vector<uint8_t> block;
   block.assign(bytes, 0);
@@ -839,6 +844,8 @@ int uploadParams(const Batch& b, bool sizesOnOut, StreamLease& stream, DeviceBat
   if (!b.sizes.empty()) memcpy(h + sizesAt, b.sizes.data(), b.sizes.size() * 4);
   if (!b.inBytes.empty()) memcpy(h + inBytesAt, b.inBytes.data(), b.inBytes.size() * 4);
   if (!b.work.empty()) memcpy(h + workAt, b.work.data(), b.work.size() * 4);
+  if (!b.resInPtrs.empty()) memcpy(h + resInAt, b.resInPtrs.data(), b.resInPtrs.size() * 8);
+  if (!b.resOutPtrs.empty()) memcpy(h + resOutAt, b.resOutPtrs.data(), b.resOutPtrs.size() * 8);
   ParamCache::Entry* entry = nullptr;
   bool miss = false;
   const bool capturing = stream.capturing();
@@ -853,6 +860,8 @@ int uploadParams(const Batch& b, bool sizesOnOut, StreamLease& stream, DeviceBat
   d->out = viewPointers((const uint64_t*)at(outAt, sizesAt > outAt), sizesOnOut ? sizes : nullptr, 0);
   d->inBytes = (const uint32_t*)at(inBytesAt, !b.inBytes.empty());
   d->work = (const uint32_t*)at(workAt, !b.work.empty());
+  if (!b.resInPtrs.empty()) d->resIn = viewPointers((const uint64_t*)at(resInAt, true), nullptr, 0);
+  if (!b.resOutPtrs.empty()) d->resOut = viewPointers((const uint64_t*)at(resOutAt, true), nullptr, 0);
   return DGPU_OK;
 }
 
@@ -881,6 +890,15 @@ bool asStrideViews(const Batch& b, bool sizesOnOut, BatchView* in, BatchView* ou
   *out = viewStride((const void*)(uintptr_t)b.outPtrs[0], outStride, sizesOnOut ? u : 0u);
   return true;
 }
+// ... and the residual sides of a feedback call, which must be progressions too
+bool residualStrideViews(const Batch& b, BatchView* resIn, BatchView* resOut) {
+  uint64_t inStride = 0, outStride = 0;
+  if (!b.resInPtrs.empty() && !progression(b.resInPtrs, &inStride)) return false;
+  if (!b.resOutPtrs.empty() && !progression(b.resOutPtrs, &outStride)) return false;
+  if (!b.resInPtrs.empty()) *resIn = viewStride((const void*)(uintptr_t)b.resInPtrs[0], inStride, 0u);
+  if (!b.resOutPtrs.empty()) *resOut = viewStride((const void*)(uintptr_t)b.resOutPtrs[0], outStride, 0u);
+  return true;
+}
 
 // How a batch reaches the kernels: the caller's stride views, stride views of a pointer batch that is a progression, or
 // the uploaded block -- then with the work lists `planWork` puts into b.work (only then: a progression has equal sizes).
@@ -893,7 +911,8 @@ int resolveBatch(Batch& b, bool sizesOnOut, StreamLease& stream, DeviceBatch* d,
     d->out = b.out;
     return DGPU_OK;
   }
-  if (asStrideViews(b, sizesOnOut, &d->in, &d->out)) return DGPU_OK;
+  if (asStrideViews(b, sizesOnOut, &d->in, &d->out) && residualStrideViews(b, &d->resIn, &d->resOut)) return DGPU_OK;
+  d->resIn = d->resOut = BatchView{};
   planWork();
   return uploadParams(b, sizesOnOut, stream, d);
 }
@@ -1059,7 +1078,8 @@ int encodeCommon(
     uint32_t outCapacity /* bytes at every archive pointer; block data beyond it is dropped */,
     uint32_t* histAcc_dev = nullptr /* the histogram in the stream's zero-at-rest counters instead of hist_dev (reduce-compress):
                                        the normalisation reads them and puts them back to zero */,
-    const RollingCounts& rolling = RollingCounts{}) {
+    const RollingCounts& rolling = RollingCounts{},
+    const DeviceBatch* residual = nullptr /* feedback source: its resIn / resOut */) {
   // (kCountingSource is the planner's: from here on the source is what the kernels are instantiated for)
   sourceType &= ~kCountingSource;
   // (rolling.countsIn arrives as hist_dev -- encodeBatch passes it as the call's histogram; here it only says that the
@@ -1217,6 +1237,7 @@ int encodeCommon(
     n.histAcc = fuse.acc;
     n.histParts = histList ? 1u : grid.x;
     fuse.norm = n;
+    fuse.residual = residual ? residual->resIn : BatchView{};
     // bins with 32 lane slots unless a workgroup sees too little data to pay for zeroing / folding them
     const bool smallBins = histList ? listedHistPartBytes <= 64u * 1024u : (uint64_t)maxSize * wordBytes / grid.x <= 64u * 1024u;
     rc = launchVariant(histogramVariant(sourceType, smallBins, histogramLoadsNonTemporal(floatType)), grid, stream, in, histTemp, 1u, fuse);
@@ -1256,6 +1277,8 @@ int encodeCommon(
     e.checksum = (useChecksum && floatType) ? checksumTemp : nullptr;
     e.capAtMax = foreignTable ? 1u : 0u;
     e.countsOut = rolling.countsOut;
+    e.resIn = residual ? residual->resIn : BatchView{};
+    e.resOut = residual ? residual->resOut : BatchView{};
     int rc = launchVariant(enc, dim3(grid), stream, e);
     if (rc) return rc;
   }
@@ -1274,14 +1297,17 @@ int encodeBatch(
   StreamLease streamLease(stream);
   TempArena arena(temp_dev, tempBytes, streamLease);
   DeviceBatch d;
-  std::vector<LaunchGroup> groups{encodeRectangle(b.maxSize, ft)};
-  int rc = resolveBatch(b, false, streamLease, &d, [&] { planEncodeCall(planPolicy(), b.sizes, ft, b.maxSize, histogram_dev != nullptr, &groups, &b.work); });
+  // (a feedback call is planned as the cast call it extends: same geometry, same lists, same cached plan)
+  const uint32_t planType = ft & ~kFeedbackSource;
+  std::vector<LaunchGroup> groups{encodeRectangle(b.maxSize, planType)};
+  int rc = resolveBatch(b, false, streamLease, &d, [&] { planEncodeCall(planPolicy(), b.sizes, planType, b.maxSize, histogram_dev != nullptr, &groups, &b.work); });
   if (rc) return rc;
   // (float inputs: no exponent plane in temp memory, the encoder splits the float words itself)
   // every group on the kernels of its own geometry, one after the other
   EncodeShared shared;
   for (const LaunchGroup& g : groups) {
-    rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, g, d.work, shared, histogram_dev, outSize_dev, outCapacity, nullptr, rolling);
+    rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, g, d.work, shared, histogram_dev, outSize_dev, outCapacity, nullptr, rolling,
+                      encIsFeedback(ft) ? &d : nullptr);
     if (rc) break;
   }
   if (tempUsed) *tempUsed = arena.requested();
@@ -1298,16 +1324,18 @@ int ansEncodeImpl(
   return encodeBatch(temp_dev, tempBytes, tempUsed, 0u, P, useChecksum, b, histogram_dev, outSize_dev, stream);
 }
 
-// (cast: the batch holds float32 words and ft is the archive's 16-bit type)
+// (cast: the batch holds float32 words and ft is the archive's 16-bit type; feedback: a cast call whose batch carries
+// residual pointers)
 int floatCompressImpl(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b, uint32_t* outSize_dev,
-    hipStream_t stream, bool cast = false, const RollingCounts& rolling = RollingCounts{}) {
+    hipStream_t stream, bool cast = false, const RollingCounts& rolling = RollingCounts{}, bool feedback = false) {
   bool done;
   int rc = checkCall(P, b.n, ft, tempUsed, /*errBatch*/ nullptr, &done,
                      "tensor larger than 1717538816 words: the maximum compressed size of its exponent plane exceeds INT32_MAX (GpuANSEncode.cu:22)",
                      b.maxSize);
   if (done) return rc;
-  return encodeBatch(temp_dev, tempBytes, tempUsed, cast ? (ft | kCastSource) : ft, P, useChecksum, b, nullptr, outSize_dev, stream, 0xffffffffu, rolling);
+  const uint32_t source = feedback ? (ft | kCastSource | kFeedbackSource) : (cast ? (ft | kCastSource) : ft);
+  return encodeBatch(temp_dev, tempBytes, tempUsed, source, P, useChecksum, b, nullptr, outSize_dev, stream, 0xffffffffu, rolling);
 }
 
 // Order of k_ans_decode's workgroups (kernels_decode.h: decodeTileOf).  Measured on MI355X, cold round trip
@@ -2303,6 +2331,53 @@ int dgpu_float_cast_compress(
   return floatCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, 0, b, outSize_dev, (hipStream_t)stream, true);
 }
 
+// ---- feedback cast-compress (no upstream equivalent) -----------------------------------
+// Cast-compress of x + e with the rounding error stored back as the next call's e (kernels_encode.h,
+// ChunkSourceFeedback): the cast call with a source flag and two more pointer arrays in its batch.
+int dgpu_float_feedback_compress(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits,
+    uint32_t numInBatch, const void* const* in, const uint32_t* inSize, const void* const* residualIn,
+    void* const* residualOut, void* const* out, uint32_t* outSize_dev, void* stream) {
+  DGPU_REQUIRE(floatType == kFloat16 || floatType == kBFloat16, "floatType of a feedback archive must be float16 or bfloat16");
+  DGPU_REQUIRE(validProbBits(probBits), "probBits must be 9, 10 or 11");
+  DGPU_REQUIRE(numInBatch <= 65535u, "numInBatch must be <= 65535");
+  DGPU_REQUIRE(numInBatch == 0 || residualOut, "feedback compress: residualOut must not be null");
+  DGPU_REQUIRE(numInBatch == 0 || (in && inSize && out), "feedback compress: in, inSize and out must not be null");
+  // every range the call reads or writes, for the overlap rule: an element's residualOut may BE its residualIn
+  std::vector<std::pair<uint64_t, uint64_t>> ranges;
+  ranges.reserve((size_t)numInBatch * 4u);
+  for (uint32_t i = 0; i < numInBatch; ++i) {
+    DGPU_REQUIRE(in[i] && residualOut[i] && out[i] && (!residualIn || residualIn[i]), "feedback compress: null entry in a pointer array");
+    DGPU_REQUIRE(encodableSize(inSize[i]),
+                 "tensor larger than 1717538816 words: the maximum compressed size of its exponent plane exceeds INT32_MAX (GpuANSEncode.cu:22)");
+    const uint64_t x = (uint64_t)(uintptr_t)in[i], ro = (uint64_t)(uintptr_t)residualOut[i], bytes = (uint64_t)inSize[i] * 4u;
+    const uint64_t ri = residualIn ? (uint64_t)(uintptr_t)residualIn[i] : ro;
+    DGPU_REQUIRE(x % 4 == 0 && ro % 4 == 0 && ri % 4 == 0, "feedback compress: float32 input and residuals must be 4-byte aligned");
+    DGPU_REQUIRE(x % 16 == ro % 16 && x % 16 == ri % 16, "feedback compress: in[i], residualIn[i] and residualOut[i] must be congruent modulo 16");
+    if (bytes == 0) continue;
+    ranges.emplace_back(x, x + bytes);
+    ranges.emplace_back(ro, ro + bytes);
+    if (ri != ro) ranges.emplace_back(ri, ri + bytes);
+    const uint64_t o = (uint64_t)(uintptr_t)out[i];
+    ranges.emplace_back(o, o + dgpu_float_max_compressed_size(floatType, inSize[i]));
+  }
+  std::sort(ranges.begin(), ranges.end());
+  for (size_t k = 1; k < ranges.size(); ++k) {
+    DGPU_REQUIRE(ranges[k - 1].second <= ranges[k].first,
+                 "feedback compress: in, residualIn, residualOut and out must not overlap (residualOut[i] == residualIn[i] excepted)");
+  }
+  Batch b;
+  int rc = pointerBatch(&b, numInBatch, ptrSide(in, 4, "float32 input must be 4-byte aligned"), ptrSide(out, 16, kMsgCompOut), inSize);
+  if (rc) return rc;
+  b.resOutPtrs.resize(numInBatch);
+  for (uint32_t i = 0; i < numInBatch; ++i) b.resOutPtrs[i] = (uint64_t)(uintptr_t)residualOut[i];
+  if (residualIn) {
+    b.resInPtrs.resize(numInBatch);
+    for (uint32_t i = 0; i < numInBatch; ++i) b.resInPtrs[i] = (uint64_t)(uintptr_t)residualIn[i];
+  }
+  return floatCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, 0, b, outSize_dev, (hipStream_t)stream, true, RollingCounts{}, true);
+}
+
 // ---- rolling-table compress (no upstream equivalent) ------------------------------------
 // The table of this call from the counts of the last one (countsIn_dev: no histogram pass), the counts of this call for
 // the next one (countsOut_dev: the counting encoder).  float16 / bfloat16 archives only: the float32 encoder has no
@@ -2382,6 +2457,7 @@ int dgpu_ans_histogram_batch_stride(
   noFuse.arrive = nullptr;
   noFuse.acc = nullptr;
   noFuse.norm = NormalizeArgs{};
+  noFuse.residual = BatchView{};
   const HistogramVariant hist = histogramVariant(0u, false, true);
   hipLaunchKernelGGL(hist.fn, grid, dim3(hist.threads), hist.ldsBytes, (hipStream_t)stream, in, histogram_dev, 0u, noFuse);
   DGPU_HIP(hipGetLastError());

@@ -76,14 +76,17 @@ constexpr bool encodeSpills(uint32_t ft) { return ft != 0; }
 // blocks in the dispatch forms of the plain 16-bit call -- 2- and 4-block tiles persistent and hardware-dispatched,
 // 8-block tiles persistent -- without the wide stage, and as every histogram form.  There is no cast form of the
 // single-block kernels (k_ans_encode_pair, k_stats_single): single-block members of a cast call run on 2-block tiles.
-inline EncodeVariant encoderVariantCast(int P, uint32_t archiveType, uint32_t tileBlocks, bool hwDispatch) {
+// Feedback sources (kFeedbackSource as well: the residual added before the rounding, the rounding error stored) exist
+// in exactly the cast source's forms.
+inline EncodeVariant encoderVariantCast(int P, uint32_t archiveType, uint32_t tileBlocks, bool hwDispatch, bool feedback = false) {
   auto of = [&](auto p, auto f) -> EncodeVariant {
     constexpr int kP = decltype(p)::value;
     constexpr uint32_t kFT = decltype(f)::value | kCastSource;
     auto tiled = [](auto tb, auto persistent) -> EncodeVariant {
       constexpr uint32_t kTB = decltype(tb)::value;
       constexpr bool kPersistent = decltype(persistent)::value;
-      return {k_ans_encode<kP, kFT, true, kTB, kPersistent, false>, encThreads(kTB), encLdsBytes(kP, true, kFT, kTB), "k_ans_encode_cast"};
+      return {k_ans_encode<kP, kFT, true, kTB, kPersistent, false>, encThreads(kTB), encLdsBytes(kP, true, kFT, kTB),
+              encIsFeedback(kFT) ? "k_ans_encode_feedback" : "k_ans_encode_cast"};
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
@@ -92,6 +95,7 @@ inline EncodeVariant encoderVariantCast(int P, uint32_t archiveType, uint32_t ti
     return tiled(UintC<kBlocksPerTile>{}, yes);
   };
   return withProbBits(P, [&](auto p) {
+    if (feedback) return archiveType == kFloat16 ? of(p, UintC<kFloat16 | kFeedbackSource>{}) : of(p, UintC<kBFloat16 | kFeedbackSource>{});
     return archiveType == kFloat16 ? of(p, UintC<kFloat16>{}) : of(p, UintC<kBFloat16>{});
   });
 }
@@ -125,7 +129,7 @@ inline EncodeVariant encoderVariantCounting(int P, uint32_t ft, uint32_t tileBlo
 //     gain there);
 //   * wide: the wide stage (kSpillStageWordsWide) exists for persistent 8-block bf16 / fp32 tiles only.
 inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, bool hwDispatch, bool wide) {
-  if (encIsCast(ft)) return encoderVariantCast(P, encArchiveType(ft), tileBlocks, hwDispatch);
+  if (encIsCast(ft)) return encoderVariantCast(P, encArchiveType(ft), tileBlocks, hwDispatch, encIsFeedback(ft));
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> EncodeVariant {
     constexpr int kP = decltype(p)::value;
     constexpr uint32_t kFT = decltype(f)::value;
@@ -234,7 +238,8 @@ inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTe
       if constexpr (kFT == 0) {
         return {k_histogram<kS, kNt>, 256u, 0u, "k_histogram"};
       } else {
-        return {k_float_histogram<kFT, kS, kNt>, 256u, 0u, encIsCast(kFT) ? "k_float_histogram_cast" : "k_float_histogram"};
+        return {k_float_histogram<kFT, kS, kNt>, 256u, 0u,
+                encIsFeedback(kFT) ? "k_float_histogram_feedback" : (encIsCast(kFT) ? "k_float_histogram_cast" : "k_float_histogram")};
       }
     };
     constexpr UintC<kHistSlotsSmall> small{};
@@ -242,6 +247,9 @@ inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTe
     if (nonTemporal) return smallBins ? of(small, std::true_type{}) : of(large, std::true_type{});
     return smallBins ? of(small, std::false_type{}) : of(large, std::false_type{});
   };
+  if (encIsFeedback(ft)) {
+    return encArchiveType(ft) == kFloat16 ? pick(UintC<kFloat16 | kCastSource | kFeedbackSource>{}) : pick(UintC<kBFloat16 | kCastSource | kFeedbackSource>{});
+  }
   if (encIsCast(ft)) return encArchiveType(ft) == kFloat16 ? pick(UintC<kFloat16 | kCastSource>{}) : pick(UintC<kBFloat16 | kCastSource>{});
   return withFloatType(ft, pick);
 }

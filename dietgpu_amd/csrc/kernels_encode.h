@@ -159,6 +159,8 @@ struct EncodeArgs {
                              // is encMaxArchiveBytes(its size) instead of outCapacity
   uint32_t* countsOut;       // counting form only: [B][256], zeroed before launch (by the normalisation step); a tile's
                              // exponent-byte counts are added with relaxed agent-scope atomics
+  BatchView resIn, resOut;   // feedback source only: the float32 residual that is added (all zero: none yet) and the one
+                             // that is stored; resOut.ptr(b) may equal resIn.ptr(b)
 };
 
 struct TileShared {
@@ -580,6 +582,127 @@ template <>
 struct ChunkSource<kFloat16 | kCastSource> : ChunkSourceCast<kFloat16> {};
 template <>
 struct ChunkSource<kBFloat16 | kCastSource> : ChunkSourceCast<kBFloat16> {};
+
+// float32 bits of a word of the 16-bit type AT (exact)
+template <uint32_t AT>
+__device__ __forceinline__ uint32_t castWiden(uint32_t q) {
+  if (AT == kBFloat16) return q << 16;
+  return __builtin_bit_cast(uint32_t, (float)__builtin_bit_cast(_Float16, (uint16_t)q));
+}
+// The word that is rounded and the rounding error it leaves (dgpu_float_feedback_compress, on float32 bits):
+// v = x + e, one add, round to nearest even, denormals kept -- or x itself, untouched, when there is no residual yet
+// (-0 keeps its sign); the error v - widen(q) is exact whenever q is finite, and +0 when q is an infinity or a NaN.
+__device__ __forceinline__ uint32_t feedbackSum(uint32_t x, uint32_t e, bool haveResidual) {
+  const uint32_t s = __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, x) + __builtin_bit_cast(float, e));
+  return haveResidual ? s : x;
+}
+__device__ __forceinline__ uint32_t feedbackError(uint32_t v, uint32_t widened) {
+  const uint32_t d = __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, v) - __builtin_bit_cast(float, widened));
+  return (widened & 0x7f800000u) == 0x7f800000u ? 0u : d;
+}
+
+// Feedback source: the cast source with a float32 residual.  Two more 16-byte loads per lane and chunk (the residual of
+// the lane's 8 words, in flight with the words themselves), the add in front of castRoundPair, the new residual from the
+// packed rounded words, two 16-byte stores.  The residual may be updated IN PLACE (eOut == eIn): every word's store
+// depends on that word's load in the same lane, a chunk is loaded once, and a tile is coded by exactly one workgroup
+// (k_ans_encode's claim words).  Loads that cover words of ANOTHER lane or block -- the tail form's window that ends at the
+// block's last byte (loadSliceBounded), an idle half's word 0, the upper half of a wave that shadows its lower half's
+// block -- either drop those words or, the shadow, run in the same instructions as the lanes they repeat: what they read
+// never reaches memory in another form than the owner's.  The tail and scalar forms store only words below n.
+template <uint32_t AT>
+struct ChunkSourceFeedback : ChunkSourceCast<AT> {
+  using Base = ChunkSourceCast<AT>;
+  struct Raw { uint4 v[2], e[2]; };
+  const uint32_t* eIn;  // this half's block of the residual; null: no residual yet
+  uint32_t* eOut;       // ... of the new residual
+  __device__ __forceinline__ void initResidual(const uint8_t* resIn, uint8_t* resOut, uint32_t block) {
+    eIn = resIn ? (const uint32_t*)resIn + (size_t)block * kBlockSize : nullptr;
+    eOut = (uint32_t*)resOut + (size_t)block * kBlockSize;
+  }
+  __device__ __forceinline__ Raw load(uint32_t c, uint32_t hl) const {
+    const uint4* p = (const uint4*)(this->in + c * 256u + hl * 8u);
+    Raw r;
+    r.v[0] = streamLoad<kNtEncLoads>(&p[0]);
+    r.v[1] = streamLoad<kNtEncLoads>(&p[1]);
+    r.e[0] = r.e[1] = make_uint4(0, 0, 0, 0);
+    if (eIn) {  // (uniform)
+      const uint4* q = (const uint4*)(eIn + c * 256u + hl * 8u);
+      r.e[0] = streamLoad<kNtEncLoads>(&q[0]);
+      r.e[1] = streamLoad<kNtEncLoads>(&q[1]);
+    }
+    return r;
+  }
+  static constexpr uint32_t kCompRegs = 2;
+  // the 8 words that are rounded, the packed rounded words, the new residual
+  __device__ __forceinline__ void roundAll(const Raw& r, uint32_t (&x)[4], uint32_t (&err)[8]) const {
+    const bool have = eIn != nullptr;
+    const uint32_t xs[8] = {r.v[0].x, r.v[0].y, r.v[0].z, r.v[0].w, r.v[1].x, r.v[1].y, r.v[1].z, r.v[1].w};
+    const uint32_t es[8] = {r.e[0].x, r.e[0].y, r.e[0].z, r.e[0].w, r.e[1].x, r.e[1].y, r.e[1].z, r.e[1].w};
+    uint32_t v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = feedbackSum(xs[j], es[j], have);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x[j] = castRoundPair<AT>(v[2 * j], v[2 * j + 1]);
+      err[2 * j] = feedbackError(v[2 * j], castWiden<AT>(x[j] & 0xffffu));
+      err[2 * j + 1] = feedbackError(v[2 * j + 1], AT == kBFloat16 ? (x[j] & 0xffff0000u) : castWiden<AT>(x[j] >> 16));
+    }
+  }
+  __device__ __forceinline__ void splitStore(const Raw& r, uint32_t c, uint32_t hl, uint32_t (&comp)[kCompRegs]) const {
+    uint32_t x[4], err[8], rest[2];
+    roundAll(r, x, err);
+    uint4* o = (uint4*)(eOut + c * 256u + hl * 8u);
+    streamStore<kNtEncStores>(&o[0], make_uint4(err[0], err[1], err[2], err[3]));
+    streamStore<kNtEncStores>(&o[1], make_uint4(err[4], err[5], err[6], err[7]));
+    splitPacked16<AT, 4>(x, comp, rest);
+    *(uint2*)(this->nc + c * 256u + hl * 8u) = make_uint2(rest[0], rest[1]);
+  }
+  __device__ __forceinline__ void consume(const Raw& r, uint32_t c, uint32_t hl, uint8_t* ring) const {
+    uint32_t comp[2];
+    splitStore(r, c, hl, comp);
+    *(uint2*)(ring + hl * 8u) = make_uint2(comp[0], comp[1]);
+  }
+  // Tail forms: ChunkSourceCast's, both streams bounded by loadSliceBounded (the two are congruent modulo 16: one
+  // alignment case).  Words at or beyond n are set to zero before the add; only the residual words below n are stored.
+  __device__ __forceinline__ Raw loadTail(uint32_t c, uint32_t hl, uint32_t n) const {
+    const uint32_t first = c * 256u + hl * 8u;
+    Raw r;
+    loadSliceBounded<2>((const uint8_t*)this->in, first * 4u, n * 4u, r.v);
+    r.e[0] = r.e[1] = make_uint4(0, 0, 0, 0);
+    if (eIn) loadSliceBounded<2>((const uint8_t*)eIn, first * 4u, n * 4u, r.e);
+    return r;
+  }
+  __device__ __forceinline__ void consumeTail(const Raw& r, uint32_t c, uint32_t hl, uint8_t* ring, uint32_t n) const {
+    const uint32_t first = c * 256u + hl * 8u;
+    const uint32_t valid = n > first ? (n - first < 8u ? n - first : 8u) : 0u;
+    auto keep = [&](uint32_t x, uint32_t j) -> uint32_t { return valid > j ? x : 0u; };
+    Raw m;
+    m.v[0] = make_uint4(keep(r.v[0].x, 0), keep(r.v[0].y, 1), keep(r.v[0].z, 2), keep(r.v[0].w, 3));
+    m.v[1] = make_uint4(keep(r.v[1].x, 4), keep(r.v[1].y, 5), keep(r.v[1].z, 6), keep(r.v[1].w, 7));
+    m.e[0] = make_uint4(keep(r.e[0].x, 0), keep(r.e[0].y, 1), keep(r.e[0].z, 2), keep(r.e[0].w, 3));
+    m.e[1] = make_uint4(keep(r.e[1].x, 4), keep(r.e[1].y, 5), keep(r.e[1].z, 6), keep(r.e[1].w, 7));
+    uint32_t x[4], err[8], comp[2], rest[2];
+    roundAll(m, x, err);
+#pragma unroll
+    for (uint32_t j = 0; j < 8u; ++j) {
+      if (j < valid) eOut[first + j] = err[j];
+    }
+    splitPacked16<AT, 4>(x, comp, rest);
+    if (valid != 0u) *(uint2*)(this->nc + first) = make_uint2(rest[0], rest[1]);
+    *(uint2*)(ring + hl * 8u) = make_uint2(comp[0], comp[1]);
+  }
+  // scalar path: wordAt hands on the word that is rounded, splitAt rounds it and stores the residual of a word that exists
+  __device__ __forceinline__ uint32_t wordAt(uint32_t i) const { return feedbackSum(this->in[i], eIn ? eIn[i] : 0u, eIn != nullptr); }
+  __device__ __forceinline__ uint32_t splitAt(uint32_t i, uint32_t v, bool valid) const {
+    const uint32_t q = castRound<AT>(v);
+    if (valid) eOut[i] = feedbackError(v, castWiden<AT>(q));
+    return Base::splitAt(i, q, valid);
+  }
+};
+template <>
+struct ChunkSource<kFloat16 | kCastSource | kFeedbackSource> : ChunkSourceFeedback<kFloat16> {};
+template <>
+struct ChunkSource<kBFloat16 | kCastSource | kFeedbackSource> : ChunkSourceFeedback<kBFloat16> {};
 
 // ---------------------------------------------------------------------------
 // The emitting lanes of a full-block row store their word under the row's ballot as execution mask -- two scalar
@@ -1052,9 +1175,13 @@ __device__ __forceinline__ uint32_t lookBackTwoLevel(const uint64_t* desc, uint6
 // bins, puts them back to zero and adds the non-zero totals to a.countsOut[b] with relaxed agent-scope atomics.  A tile
 // is encoded by exactly one workgroup (the claim words decide), so it is counted exactly once, stolen or not.  Exists
 // for persistent spilling tiles of float16 / bfloat16 archives (plain and cast sources), without the wide stage.
+// (the feedback source keeps 16 registers of loads in flight per lane where the cast source keeps 8: it is allowed the
+// registers of 4 waves per SIMD, the residency at which the row loop still loses nothing -- DESIGN.md section 8.1)
+__host__ __device__ constexpr int encMinWavesPerSimd(uint32_t ft) { return encIsFeedback(ft) ? 4 : 6; }
 template <int P, uint32_t FT, bool kSpill, uint32_t kTB, bool kPersistent, bool kWide = false, bool kCount = false>
-__global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_ans_encode(EncodeArgs a) {
+__global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu(encMinWavesPerSimd(FT), 8))) void k_ans_encode(EncodeArgs a) {
   static_assert(kTB >= 2u, "single-block elements are k_ans_encode_pair's");
+  static_assert(!encIsFeedback(FT) || (encIsCast(FT) && kSpill && !kWide && !kCount), "the feedback source extends the cast source; no counting form");
   static_assert(!kCount || (kSpill && kPersistent && !kWide && (encArchiveType(FT) == kFloat16 || encArchiveType(FT) == kBFloat16)),
                 "the counting form exists for persistent 16-bit float tiles");
   constexpr uint32_t kCountSlots = kCount ? encCountSlots(kTB) : 0u;
@@ -1217,6 +1344,10 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
       ChunkSource<FT> src;
       // (otherwise an idle half reads, and discards, word 0 of block 0)
       src.init(in, archive, size, haveBlock ? block : (waveHalf ? firstBlockOfWave : 0u));
+      if constexpr (encIsFeedback(FT)) {
+        const bool haveResidual = a.resIn.ptrs != nullptr || a.resIn.base != 0ull;  // (uniform)
+        src.initResidual(haveResidual ? a.resIn.ptr(b) : nullptr, a.resOut.ptr(b), haveBlock ? block : (waveHalf ? firstBlockOfWave : 0u));
+      }
 
       uint32_t state;
       uint32_t words;        // words left in the LDS stage
@@ -1400,11 +1531,15 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
 // Cast form (FT = archive type | kCastSource): the element is float32 words and the bin is the exponent byte of the
 // word ROUNDED to the archive's type (castRound, as the encoder's cast source: a carry out of the mantissa changes it).
 // Its parts are laid out by the bytes of the ARCHIVE's words, as the plain call's are: same grids, same temp memory.
+// Feedback form (kFeedbackSource as well): the word that is rounded is x + e, with e from fuse.residual -- the encoder's
+// single add (feedbackSum), or the table would not cover the symbols the encoder codes.  The residual is congruent to
+// the element modulo 16, so both streams take their vectors from the same boundary.  The pass only reads.
 template <uint32_t FT, uint32_t S, bool kNt = true>
 __global__ __launch_bounds__(256) void k_float_histogram(BatchView in, uint32_t* __restrict__ hist, uint32_t partial, HistFuse fuse) {
   __shared__ uint32_t bins[kNumSymbols * S];
   const uint32_t tid = threadIdx.x;
   constexpr bool kCast = encIsCast(FT);
+  constexpr bool kFeedback = encIsFeedback(FT);
   constexpr uint32_t AT = encArchiveType(FT);
   const HistWork w = histWorkOf(fuse, in, AT == kFloat32 ? 4u : 2u);
   const uint32_t b = w.b;
@@ -1424,10 +1559,29 @@ __global__ __launch_bounds__(256) void k_float_histogram(BatchView in, uint32_t*
   const uint32_t numVec = (n - head) / kWordsPerVec;
   const uint32_t stride = w.parts * 256u;
   const uint4* pv = (const uint4*)(inBytes + (size_t)head * kWordBytes);
+  // feedback form: the residual (null: none yet), its vectors
+  [[maybe_unused]] const uint8_t* resBytes = nullptr;
+  if constexpr (kFeedback) {
+    if (fuse.residual.ptrs != nullptr || fuse.residual.base != 0ull) resBytes = fuse.residual.ptr(b);
+  }
+  [[maybe_unused]] const uint4* pe = (const uint4*)(resBytes + (size_t)head * kWordBytes);
+  const uint4 noResidual = make_uint4(0, 0, 0, 0);
+  auto loadRes = [&](uint32_t i) -> uint4 {
+    if constexpr (kFeedback) {
+      if (resBytes) return streamLoad<kNt>(&pe[i]);
+    }
+    return noResidual;
+  };
 
   constexpr uint32_t kShift16 = AT == kFloat16 ? 8u : 7u;  // exponent byte of a 16-bit word
-  auto addVec = [&](const uint4& x) {
-    if (kCast) {
+  auto addVec = [&](const uint4& x, [[maybe_unused]] const uint4& e) {
+    if (kFeedback) {
+      const uint32_t xw[4] = {x.x, x.y, x.z, x.w}, ew[4] = {e.x, e.y, e.z, e.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        histAdd<S>(myBins, (castRound<kCast ? AT : kBFloat16>(feedbackSum(xw[j], ew[j], resBytes != nullptr)) >> kShift16) & 0xffu);
+      }
+    } else if (kCast) {
       const uint32_t xw[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) histAdd<S>(myBins, (castRound<kCast ? AT : kBFloat16>(xw[j]) >> kShift16) & 0xffu);
@@ -1457,19 +1611,23 @@ __global__ __launch_bounds__(256) void k_float_histogram(BatchView in, uint32_t*
   uint32_t v = vBegin + tid;
   for (; v + 768u < vEnd; v += 1024u) {
     const uint4 x0 = streamLoad<kNt>(&pv[v]), x1 = streamLoad<kNt>(&pv[v + 256u]), x2 = streamLoad<kNt>(&pv[v + 512u]), x3 = streamLoad<kNt>(&pv[v + 768u]);
-    addVec(x0);
-    addVec(x1);
-    addVec(x2);
-    addVec(x3);
+    const uint4 e0 = loadRes(v), e1 = loadRes(v + 256u), e2 = loadRes(v + 512u), e3 = loadRes(v + 768u);
+    addVec(x0, e0);
+    addVec(x1, e1);
+    addVec(x2, e2);
+    addVec(x3, e3);
   }
-  for (; v < vEnd; v += 256u) addVec(streamLoad<kNt>(&pv[v]));
+  for (; v < vEnd; v += 256u) addVec(streamLoad<kNt>(&pv[v]), loadRes(v));
 
   // head and tail, word by word (the whole element when the input is not even word-aligned)
   const uint32_t loose = n - numVec * kWordsPerVec;
   for (uint32_t j = w.part * 256u + tid; j < loose; j += stride) {
     const uint32_t i = j < head ? j : numVec * kWordsPerVec + j;
     uint32_t c;
-    if (kCast) c = (castRound<kCast ? AT : kBFloat16>(((const uint32_t*)inBytes)[i]) >> kShift16) & 0xffu;
+    if (kFeedback) {
+      const uint32_t e = resBytes ? ((const uint32_t*)resBytes)[i] : 0u;
+      c = (castRound<kCast ? AT : kBFloat16>(feedbackSum(((const uint32_t*)inBytes)[i], e, resBytes != nullptr)) >> kShift16) & 0xffu;
+    } else if (kCast) c = (castRound<kCast ? AT : kBFloat16>(((const uint32_t*)inBytes)[i]) >> kShift16) & 0xffu;
     else if (FT == kFloat32) c = (((const uint32_t*)inBytes)[i] >> 23) & 0xffu;
     else c = ((uint32_t)((const uint16_t*)inBytes)[i] >> (FT == kFloat16 ? 8u : 7u)) & 0xffu;
     histAdd<S>(myBins, c);

@@ -402,6 +402,7 @@ struct HistFuse {
   // parts of partBytes, instead of a (parts, B) rectangle laid out for the largest element.  nullptr: the rectangle.
   const uint32_t* workMap;
   uint32_t partBytes;
+  BatchView residual;  // feedback form of k_float_histogram only: the float32 residual added before the rounding (all zero: none)
 };
 
 // Which (element, part of how many) a histogram workgroup counts, and where its partial histogram goes.

@@ -27,7 +27,12 @@ DGPU_HD constexpr bool encIsCast(uint32_t ft) { return (ft & kCastSource) != 0u;
 // kCountingSource (a PLANNING flag only, never a template parameter): the call runs the counting form of the encoder
 // (kernels_encode.h, kCount), which like the cast sources exists as tiles of 2, 4 and 8 blocks only.
 constexpr uint32_t kCountingSource = 0x200u;
-DGPU_HD constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~(kCastSource | kCountingSource); }
+// kFeedbackSource (with kCastSource): a cast source with error feedback -- a float32 residual per word is added before
+// the rounding and the new rounding error stored back (kernels_encode.h, ChunkSourceFeedback).  Planned and launched as
+// the cast source it extends; there is no counting form.
+constexpr uint32_t kFeedbackSource = 0x400u;
+DGPU_HD constexpr bool encIsFeedback(uint32_t ft) { return (ft & kFeedbackSource) != 0u; }
+DGPU_HD constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~(kCastSource | kCountingSource | kFeedbackSource); }
 // whether single-block elements of such a call have kernels of their own (k_ans_encode_pair, k_stats_single)
 DGPU_HD constexpr bool encHasSingleBlockKernels(uint32_t ft) { return (ft & (kCastSource | kCountingSource)) == 0u && ft != kFloat32; }
 

@@ -598,6 +598,49 @@ std::tuple<at::Tensor, at::Tensor, int64_t> compress_data_cast(
   return {std::move(comp), std::move(sizes), (int64_t)used};
 }
 
+// Feedback cast-compress (no reference op): compress_data_cast of ts_in[i] + ts_residual[i], with ts_residual[i] --
+// float32, of the tensor's size -- updated in place to the rounding error (dgpu_float_feedback_compress).  fresh: no
+// residual yet, the buffers are only written.
+std::tuple<at::Tensor, at::Tensor, int64_t> compress_data_feedback(
+    const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tResiduals, int64_t floatType, bool fresh,
+    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outCompressed, const std::optional<at::Tensor>& outCompressedSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.size() == tResiduals.size(), "dietgpu: one residual per tensor");
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tIns.size();
+  int64_t maxWords = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const at::Tensor &t = tIns[i], &r = tResiduals[i];
+    TORCH_CHECK(t.device().is_cuda() && t.is_contiguous() && t.get_device() == dev);
+    TORCH_CHECK(t.scalar_type() == at::ScalarType::Float, "dietgpu: the inputs of a feedback call must be float32");
+    TORCH_CHECK(r.device().is_cuda() && r.is_contiguous() && r.get_device() == dev && r.scalar_type() == at::ScalarType::Float &&
+                    r.numel() == t.numel(),
+                "dietgpu: a residual is a contiguous float32 tensor of its tensor's size on its GPU");
+    maxWords = std::max<int64_t>(maxWords, t.numel());
+  }
+  at::Tensor comp, sizes;
+  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)maxWords), dev,
+                  tIns[0].device(), comp, sizes);
+  std::vector<const void*> inPtrs(n), resIn(n);
+  std::vector<uint32_t> inSize(n);
+  std::vector<void*> compPtrs(n), resOut(n);
+  for (size_t i = 0; i < n; ++i) {
+    inPtrs[i] = tIns[i].data_ptr();
+    inSize[i] = (uint32_t)tIns[i].numel();
+    resIn[i] = resOut[i] = tResiduals[i].data_ptr();
+    compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
+  }
+  size_t used = 0;
+  check(dgpu_float_feedback_compress(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), (uint32_t)n, inPtrs.data(), inSize.data(),
+                                     fresh ? nullptr : resIn.data(), resOut.data(), compPtrs.data(), (uint32_t*)sizes.data_ptr(), streamOf(dev)),
+        "floatCompressFeedback", true);
+  return {std::move(comp), std::move(sizes), (int64_t)used};
+}
+
 // Rolling-table compress (no reference op): compress_data / compress_data_cast with the tables made from the counts the
 // last call left (counts_in) and this call's counts taken by the encoder (counts_out): dgpu_float_rolling_compress.
 // float_type (1 = float16, 2 = bfloat16) is that of the archives; source_float32: ts_in are float32 and are rounded.
@@ -907,6 +950,9 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "compress_data_cast(Tensor[] ts_in, int float_type, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::compress_data_cast);
+  m.def(
+      "compress_data_feedback(Tensor[] ts_in, Tensor[] ts_residual, int float_type, bool fresh=False, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
+      &dietgpu_amd::compress_data_feedback);
   m.def(
       "compress_data_rolling(Tensor[] ts_in, Tensor? counts_in, Tensor? counts_out, int float_type, bool source_float32=False, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::compress_data_rolling);

@@ -152,6 +152,17 @@ class GpuFloatCodec:
         comp, sizes, _ = ops.compress_data_cast(tensors, dtype, self.temp_mem)
         return comp, sizes
 
+    def compress_cast_feedback(self, tensors, residuals, dtype, fresh=False):
+        """compress_cast of tensors[i] + residuals[i] (float32, updated in place to the rounding error; `fresh`: no
+        residual yet, the buffers are only written): ops.compress_data_feedback.  It does not use the rolling tables -- a
+        `rolling=True` codec counts these tensors with the histogram pass (there is no counting form of the feedback
+        encoder)."""
+        from . import ops
+
+        self.dtype = dtype
+        comp, sizes, _ = ops.compress_data_feedback(tensors, residuals, dtype, fresh, self.temp_mem)
+        return comp, sizes
+
     def decompress(self, rows, outs, scale=None):
         """`scale` (a number, or a float32 tensor of 1 or len(rows) elements on the device): every word is multiplied by
         it in the decode kernel (ops.decompress_data_scaled); a tensor is never read by the host"""
@@ -281,11 +292,39 @@ def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec, scale=None):
 _MAX_REDUCE_SOURCES = 64  # of one decode-reduce call (dgpu_float_decode_reduce)
 
 
-def _exchange_shard_rows(tensor, codec, raw_local=False):
+_WIRE_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def _check_wire(what, tensor, codec, raw_local, wire_dtype, residual):
+    """The arguments of a float32 tensor on a 16-bit wire (wire_dtype, residual), before anything is exchanged."""
+    if wire_dtype is None:
+        if residual is not None:
+            raise RuntimeError(f"{what}: a residual needs wire_dtype (float16 or bfloat16)")
+        return
+    if wire_dtype not in _WIRE_DTYPES:
+        raise RuntimeError(f"{what}: wire_dtype must be float16 or bfloat16")
+    if tensor.dtype != torch.float32:
+        raise RuntimeError(f"{what}: wire_dtype is for float32 tensors (a 16-bit tensor travels as it is)")
+    if raw_local:
+        raise RuntimeError(f"{what}: raw_local cannot be combined with wire_dtype -- a float32 row is not a raw source of 16-bit "
+                           "archives, and the rank's own shard would escape the feedback")
+    if residual is None:
+        return
+    if (residual.dtype != torch.float32 or residual.dim() != 1 or residual.numel() != tensor.numel() or not residual.is_contiguous()
+            or residual.device != tensor.device):
+        raise RuntimeError(f"{what}: the residual must be a flat contiguous float32 tensor of the tensor's length on its device")
+    if not callable(getattr(codec, "compress_cast_feedback", None)):
+        raise RuntimeError(f"{what}: a residual needs a codec with compress_cast_feedback(tensors, residuals, dtype, fresh)")
+
+
+def _exchange_shard_rows(tensor, codec, raw_local=False, wire_dtype=None, residual=None, residual_fresh=False):
     """The exchange half of compressed_reduce_scatter: shard j of this rank's flat tensor, compressed, goes to rank j ->
     (words per shard, recv [source rank, width] uint8, all_sizes [source rank, destination rank] int32, width).
     raw_local: the rank's own shard is not compressed (the codec gets the other world - 1, none at all in a world of one);
-    its row of the exchange has size 0 and carries nothing."""
+    its row of the exchange has size 0 and carries nothing.
+    wire_dtype (float16 / bfloat16, for a float32 tensor): the shards are rounded to it by the compressor -- the codec's
+    compress_cast, or, with `residual` (a flat float32 tensor of the tensor's length, updated in place), its
+    compress_cast_feedback on the shards and the matching views of the residual."""
     world = dist.get_world_size()
     if tensor.dim() != 1 or tensor.numel() % world != 0:
         raise RuntimeError("compressed_reduce_scatter: the tensor must be flat, its length a multiple of the world size")
@@ -303,6 +342,10 @@ def _exchange_shard_rows(tensor, codec, raw_local=False):
             comp = torch.empty((world, comp_others.shape[1]), dtype=torch.uint8, device=tensor.device)
             comp[at] = comp_others[: len(others)]
             comp[me].zero_()  # (travels to this rank itself; nothing reads it)
+    elif wire_dtype is not None and residual is not None:
+        comp, sizes = codec.compress_cast_feedback(shards, list(residual.view(world, shard_words).unbind(0)), wire_dtype, bool(residual_fresh))
+    elif wire_dtype is not None:
+        comp, sizes = codec.compress_cast(shards, wire_dtype)
     else:
         comp, sizes = codec.compress(shards)  # all shards in one call
     sizes = sizes.to(torch.int32)
@@ -397,7 +440,8 @@ def _scale_shard(shard, factor):
     shard.mul_(torch.tensor(factor, dtype=torch.float32, device=shard.device))
 
 
-def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False):
+def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False, wire_dtype=None, residual=None,
+                              residual_fresh=False):
     """Reduce-scatter (sum) of a flat float tensor, moving compressed bytes and summing in float32.
 
     `tensor`: this rank's flat fp16 / bf16 / fp32 tensor; its length is a multiple of the world size and the same on
@@ -431,8 +475,17 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
     that are inf or NaN -- what clipping by global norm and a loss scaler's overflow check need of the shard.  They are
     filled by the codec's reduce call where its method has a `norm` parameter (GpuFloatCodec: by the reduce kernel), and
     by one torch pass over the shard otherwise; nothing is read back to the host.  With the default the codec is called
-    exactly as it always was."""
+    exactly as it always was.
+
+    wire_dtype (float16 or bfloat16), for a float32 `tensor`: the shards travel as archives of that type instead of as
+    float32 archives -- rounded inside the compressor (the codec's compress_cast), the receiving side unchanged on rows of
+    wire_dtype.  With `residual` -- a flat float32 tensor of the tensor's length, this rank's, kept between steps -- the
+    rounding has error feedback: the codec's compress_cast_feedback(shards, residual's shard views, wire_dtype, fresh) adds
+    the residual before it rounds and stores the new rounding error back, in place.  residual_fresh=True: the first step,
+    the residual is only written.  raw_local=True with wire_dtype, and a residual with a codec that has no
+    compress_cast_feedback, raise RuntimeError."""
     codec = codec or GpuFloatCodec()
+    _check_wire("compressed_reduce_scatter", tensor, codec, raw_local, wire_dtype, residual)
     world = dist.get_world_size()
     me = dist.get_rank()
     factor = _reduce_factor(op, scale, world)
@@ -454,7 +507,7 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
                 _norm_by_torch(pair, shard)
             _norm_stats(stats, pair)
         return shard, stats
-    shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec)
+    shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec, False, wire_dtype, residual, residual_fresh)
     shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
     has_reduce = callable(getattr(codec, "decompress_reduce", None))
     if not (has_reduce and world <= _MAX_REDUCE_SOURCES) and not callable(getattr(codec, "decompress_accumulate", None)):
@@ -485,7 +538,8 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
     return shard, stats
 
 
-def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False, clip_norm=None):
+def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False, clip_norm=None, wire_dtype=None,
+                          residual=None, residual_fresh=False):
     """All-reduce (sum) of a flat fp16 / bf16 tensor, moving compressed bytes both ways and summing in float32.
 
     Three steps: `compressed_reduce_scatter` (this rank's float32 shard of the sum), the codec's `compress_cast` of that
@@ -525,15 +579,22 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
     computed in float64 on the device and rounded once to float32, and the all-gather decodes with that factor
     (compressed_all_gather's `scale`: in the codec's decode kernel where its `decompress` has a `scale` parameter): every
     word is round(fl32(word * coef)), bit-identical on every rank.  stats["clip_coef"] is the 0-dim float32 tensor.  No
-    pass over the tensor and no host read is added."""
-    if tensor.dtype not in (torch.float16, torch.bfloat16):
-        raise RuntimeError("compressed_all_reduce: the tensor must be float16 or bfloat16")
+    pass over the tensor and no host read is added.
+
+    wire_dtype, residual, residual_fresh: as in compressed_reduce_scatter -- a float32 `tensor` whose shards travel as
+    archives of wire_dtype, with error feedback on that first rounding when a residual is given.  The call then returns
+    the sum in wire_dtype.  Its second rounding -- of the float32 sum, before the all-gather -- carries NO feedback: it is
+    the same on every rank and would need a residual per shard of the sum."""
+    codec = codec or GpuFloatCodec()
+    _check_wire("compressed_all_reduce", tensor, codec, raw_local, wire_dtype, residual)
+    out_dtype = wire_dtype if wire_dtype is not None else tensor.dtype
+    if out_dtype not in _WIRE_DTYPES:
+        raise RuntimeError("compressed_all_reduce: the tensor must be float16 or bfloat16 (float32: give wire_dtype)")
     if clip_norm is not None:
         clip_norm = float(clip_norm)
         if not (math.isfinite(clip_norm) and clip_norm > 0.0):
             raise RuntimeError("compressed_all_reduce: clip_norm must be a positive finite float")
         norm = True
-    codec = codec or GpuFloatCodec()
     world = dist.get_world_size()
     factor = _reduce_factor(op, scale, world)
     one_call = callable(getattr(codec, "decompress_reduce_compress", None)) and world <= _MAX_REDUCE_SOURCES
@@ -542,7 +603,7 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
         reduce_compress = codec.decompress_reduce_compress_mixed if mixed else codec.decompress_reduce_compress
         one_call = factor is None or _takes_scale(reduce_compress)
     if one_call:
-        shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec, mixed)
+        shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec, mixed, wire_dtype, residual, residual_fresh)
         me = dist.get_rank()
         shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
         pair = _norm_pair(tensor.device) if norm else None
@@ -556,30 +617,34 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
         }
     else:
         pair = _norm_pair(tensor.device) if norm else None
-        shard, rs = compressed_reduce_scatter(tensor, codec, raw_local, scale=factor)
-        comp, sizes = codec.compress_cast([shard], tensor.dtype)
-    out = torch.empty_like(tensor)
+        if wire_dtype is None:
+            shard, rs = compressed_reduce_scatter(tensor, codec, raw_local, scale=factor)
+        else:
+            shard, rs = compressed_reduce_scatter(tensor, codec, raw_local, scale=factor, wire_dtype=wire_dtype, residual=residual,
+                                                  residual_fresh=residual_fresh)
+        comp, sizes = codec.compress_cast([shard], out_dtype)
+    out = torch.empty(tensor.shape, dtype=out_dtype, device=tensor.device)
     rows = out.view(world, shard.numel())
     if clip_norm is not None:
         # the statistics first: the coefficient is known before the gather, whose decode applies it
         if not pair[2]:  # (the words of the archive: the shard rounded as the cast rounds it)
-            _norm_by_torch(pair, shard.to(tensor.dtype))
+            _norm_by_torch(pair, shard.to(out_dtype))
         both = torch.cat([pair[0], pair[1].to(torch.float64)])
         dist.all_reduce(both)
         # torch.nn.utils.clip_grad_norm_'s formula, in float64 on the device, rounded once to float32
         coef = torch.clamp(clip_norm / (both[0].sqrt() + 1e-6), max=1.0).to(torch.float32)
-        _, ag = _all_gather_archives(comp, sizes, lambda r: [rows[r]], shard.numel() * tensor.element_size(), codec, scale=coef)
+        _, ag = _all_gather_archives(comp, sizes, lambda r: [rows[r]], shard.numel() * out.element_size(), codec, scale=coef)
         stats = {k: rs[k] + ag[k] for k in rs}
         _norm_stats(stats, pair)
         stats["global_sumsq"] = both[0]
         stats["global_nonfinite"] = both[1].to(torch.int32)
         stats["clip_coef"] = coef
         return out, stats
-    _, ag = _all_gather_archives(comp, sizes, lambda r: [rows[r]], shard.numel() * tensor.element_size(), codec)
+    _, ag = _all_gather_archives(comp, sizes, lambda r: [rows[r]], shard.numel() * out.element_size(), codec)
     stats = {k: rs[k] + ag[k] for k in rs}
     if norm:
         if not pair[2]:  # (the words of the archive: the shard rounded as the cast rounds it)
-            _norm_by_torch(pair, shard.to(tensor.dtype))
+            _norm_by_torch(pair, shard.to(out_dtype))
         _norm_stats(stats, pair)
         both = torch.cat([pair[0], pair[1].to(torch.float64)])
         dist.all_reduce(both)

@@ -370,6 +370,51 @@ def compress_data_cast(ts_in, dtype, temp_mem=None, out_compressed=None, out_com
     return comp, sizes, int(used.value)
 
 
+# ------------------------------------------------------ feedback cast-compress
+# (no reference op: dgpu_float_feedback_compress, include/dietgpu_amd.h)
+def _validate_residuals(ts_in, ts_residual):
+    _check(len(ts_residual) == len(ts_in), "one residual per tensor")
+    for t, r in zip(ts_in, ts_residual):
+        _check(r.dtype == torch.float32, "the residuals of a feedback call must be float32")
+        _check(r.numel() == t.numel(), "a residual has its tensor's number of elements")
+        _check(r.is_contiguous() and r.device == t.device, "a residual is contiguous and on its tensor's device")
+
+
+def compress_data_feedback(ts_in, ts_residual, dtype, fresh=False, temp_mem=None, out_compressed=None,
+                           out_compressed_sizes=None, prob_bits=K_DEFAULT_PRECISION):
+    """compress_data_cast with error feedback: tensor i is compressed as `ts_in[i] + ts_residual[i]` (one float32 add)
+    rounded to `dtype`, and ts_residual[i] -- float32, of the tensor's size -- is updated IN PLACE to what that rounding
+    dropped (zero where the rounded word is an infinity or a NaN), for the next step.  `fresh=True`: there is no
+    residual yet -- the buffers are only written and need not be initialised.  ts_in is not modified.
+    -> (comp [B, maxSize] u8, sizes [B] i32, temp bytes used), as compress_data_cast."""
+    _check(len(ts_in) > 0)
+    _check(dtype in (torch.float16, torch.bfloat16), "dtype (of the archives) must be float16 or bfloat16")
+    for t in ts_in:
+        _check(t.dtype == torch.float32, "the inputs of a feedback call must be float32")
+    _validate_residuals(ts_in, ts_residual)
+    _check(ts_in[0].is_cuda, "tensors must be on the GPU")
+    ft = _DTYPE_TO_FT[dtype]
+    dev = ts_in[0].get_device()
+    for t in ts_in:
+        _check(t.is_cuda and t.is_contiguous() and t.get_device() == dev)
+    op = _amd_op(prob_bits, "compress_data_feedback")
+    if op is not None:
+        return op(ts_in, ts_residual, ft, bool(fresh), temp_mem, out_compressed, out_compressed_sizes)
+    _, mx = _total_and_max(ts_in)
+    rows, cols = len(ts_in), _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
+    with torch.cuda.device(dev):
+        comp, sizes = _validate_out(out_compressed, out_compressed_sizes, rows, cols, dev, ts_in[0].device)
+        tp, tb = _temp(temp_mem, dev)
+        row = comp.size(1)
+        out_ptrs = (C.c_void_p * rows)(*[comp.data_ptr() + i * row for i in range(rows)])
+        res_ptrs = _ptr_array(ts_residual)
+        used = C.c_size_t(0)
+        check(lib().dgpu_float_feedback_compress(
+            tp, tb, C.byref(used), ft, prob_bits, rows, _ptr_array(ts_in), _u32_array([t.numel() for t in ts_in]),
+            None if fresh else res_ptrs, res_ptrs, out_ptrs, _ptr(sizes), _stream()))
+    return comp, sizes, int(used.value)
+
+
 # ------------------------------------------------------- rolling-table compress
 # (no reference op: dgpu_float_rolling_compress, include/dietgpu_amd.h)
 def _validate_counts(counts, rows, dev, name):

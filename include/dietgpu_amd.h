@@ -72,7 +72,7 @@ const char* dgpu_version(void);
  * dgpu_float_reduce_compress_temp_bytes, dgpu_float_rolling_compress, dgpu_float_decode_reduce_mixed,
  * dgpu_float_reduce_compress_mixed, dgpu_float_decode_reduce_scaled, dgpu_float_reduce_compress_scaled,
  * dgpu_float_reduce_norm_temp_bytes, dgpu_float_decode_reduce_norm, dgpu_float_reduce_compress_norm and
- * dgpu_float_decode_scaled were added at version 8). */
+ * dgpu_float_decode_scaled were added at version 8, dgpu_float_feedback_compress after them). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -399,6 +399,46 @@ int dgpu_float_cast_compress(
     void* temp_dev, size_t tempBytes, size_t* tempUsed,
     uint32_t floatType /* of the ARCHIVE: DGPU_FLOAT16 or DGPU_BFLOAT16 */, int probBits,
     uint32_t numInBatch, const void* const* in /* float32 */, const uint32_t* inSize /* words */,
+    void* const* out, uint32_t* outSize_dev, void* stream);
+
+/* ---- feedback cast-compress (no upstream equivalent) ------------------------------------
+ * dgpu_float_cast_compress with error feedback: the sender of a compressed exchange of float32 gradients keeps a float32
+ * residual per tensor, the call adds it before the rounding and stores the new rounding error back, so that what one
+ * step's rounding drops reaches the wire in a later step.  For word k of element i, on the float32 bits:
+ *   1. residualIn given: v = x[k] + e[k] -- ONE IEEE float32 add, round to nearest even, denormals kept, not
+ *      contracted.  residualIn == NULL (the ARRAY: no residual yet): v = x[k], NO add -- -0.0f keeps its sign and a
+ *      signalling NaN reaches the rounding as it is (a zero-filled residual is not the same thing: -0 + +0 = +0).
+ *      Where both x[k] and e[k] are NaNs, or the add is invalid (inf - inf), v is a NaN whose sign is unspecified.
+ *   2. q = the rounding of dgpu_float_cast_compress applied to v (nearest even, float16 denormals produced, overflow to
+ *      infinity, every NaN to the canonical quiet NaN with its sign).
+ *   3. residualOut[i][k] = v - widen(q) when q is finite -- exact, so its rounding mode never shows ((-0) - (-0) is
+ *      +0) -- and +0.0f (bits 0) when q is an infinity or a NaN: one overflowing step does not poison the residual for
+ *      good.  Whether to take such a step remains the caller's decision, as elsewhere.
+ *   4. out[i] / outSize_dev[i] are byte for byte what dgpu_float_cast_compress(floatType, probBits) writes for the
+ *      float32 tensor v: an ordinary archive that every decoder of this header reads.
+ *   - In place: residualOut[i] == residualIn[i], exactly, is allowed and is the intended use -- one buffer per tensor.
+ *     Any other overlap among in, residualIn, residualOut and out, within or across members, is invalid
+ *     (DGPU_ERR_INVALID_ARGUMENT).  `in` is never written.
+ *   - Exactly inSize[i] words of residualOut[i] are written: no byte before or behind them is touched, an empty element
+ *     writes nothing.
+ *   - in[i], residualIn[i] and residualOut[i] are 4-byte aligned and congruent to each other modulo 16 (a residual laid
+ *     out like its tensor always is); out[i] 16-byte aligned with room for dgpu_float_max_compressed_size(floatType,
+ *     inSize[i]).  probBits 9 / 10 / 11, numInBatch <= 65535, inSize[i] within the size guard, floatType DGPU_FLOAT16 or
+ *     DGPU_BFLOAT16, residualOut not NULL when numInBatch > 0, no entry of a given array NULL:
+ *     DGPU_ERR_INVALID_ARGUMENT otherwise, with a dgpu_last_error() text, before anything is enqueued.  An empty batch
+ *     returns 0 with *tempUsed = 0.
+ *   - No checksum, for dgpu_float_cast_compress's reason.  Temp memory: within
+ *     dgpu_float_compress_temp_bytes(floatType, numInBatch, max inSize).
+ *   - The host routes are dgpu_float_cast_compress's: stride detection (the residual arrays included), parameter cache
+ *     (the residual pointers are part of the resident block and of its key), work lists, size classes, both dispatch
+ *     forms, no host synchronisation, capturable into a HIP graph after one identical warm call; single-block elements
+ *     run on the 2-block tiles. */
+int dgpu_float_feedback_compress(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed,
+    uint32_t floatType /* of the ARCHIVE: DGPU_FLOAT16 or DGPU_BFLOAT16 */, int probBits,
+    uint32_t numInBatch, const void* const* in /* float32 */, const uint32_t* inSize /* words */,
+    const void* const* residualIn /* float32, [numInBatch]; the ARRAY may be NULL: no residual yet */,
+    void* const* residualOut /* float32, [numInBatch], required */,
     void* const* out, uint32_t* outSize_dev, void* stream);
 
 /* ---- rolling-table compress (no upstream equivalent) ------------------------------------
