@@ -1554,13 +1554,30 @@ int planFloatDecode(Batch& b, StreamLease& streamLease, DeviceBatch* dev, Launch
   return rc;
 }
 
+// The factor of a scaled decode-accumulate: the host float, or device memory the kernel reads (dev, stride 0 / 1).
+struct DecodeFactor {
+  float scale;
+  const float* dev;
+  uint32_t stride;
+};
+
 // Decode-accumulate (k_ans_decode_accum): every archive widened to float32 and stored to (accumulate == 0) or added into
-// (1) its float32 accumulator.  No temp memory, no host synchronisation.
+// (1) its float32 accumulator.  factor (k_ans_decode_accum_scaled): the widened word is multiplied by it first.  No temp
+// memory, no host synchronisation.
 int decodeAccumulateImpl(
     size_t* tempUsed, uint32_t ft, int P, int accumulate, uint32_t B, const void* const* in, const uint32_t* inBytes,
-    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+    void* const* out, const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream,
+    const DecodeFactor* factor = nullptr) {
   DGPU_REQUIRE(validFloatType(ft), kMsgFloatType);
   DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "decode-accumulate: accumulate must be 0 or 1");
+  if (factor) {
+    DGPU_REQUIRE(factor->stride <= 1u, "scaled decode-accumulate: scaleStride must be 0 (one factor) or 1 (one per member)");
+    DGPU_REQUIRE(factor->dev != nullptr || (std::isfinite(factor->scale) && factor->scale != 0.0f),
+                 "scaled decode-accumulate: a host scale must be finite and not zero");
+    DGPU_REQUIRE((uintptr_t)factor->dev % 4u == 0u, "scaled decode-accumulate: scale_dev must be 4-byte aligned");
+    // a host factor of exactly 1 is the plain call (a multiply by 1 would quiet a signalling NaN)
+    if (!factor->dev && factor->scale == 1.0f) factor = nullptr;
+  }
   bool done;
   int rc = checkCall(P, B, ft, tempUsed, /*errBatch*/ nullptr, &done);
   if (done) return rc;
@@ -1576,7 +1593,11 @@ int decodeAccumulateImpl(
   if (rc) return rc;
   DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
   d.accumulate = (uint32_t)accumulate;
-  return launchDecode(d, group, dev.work, DecodeForm::kAccum, P, stream);
+  if (!factor) return launchDecode(d, group, dev.work, DecodeForm::kAccum, P, stream);
+  d.scale = factor->scale;
+  d.scalePtr = factor->dev;
+  d.scaleStride = factor->stride;
+  return launchDecode(d, group, dev.work, DecodeForm::kAccumScaled, P, stream);
 }
 
 // Scaled decompress (k_ans_decode_scaled): the whole bounded float decode whose every word is multiplied by the member's
@@ -2093,6 +2114,18 @@ int dgpu_float_decode_accumulate(
   (void)tempBytes;
   return decodeAccumulateImpl(tempUsed, floatType, probBits, accumulate, numInBatch, in, inBytes, out, outCapacity,
                               outSuccess_dev, outSize_dev, (hipStream_t)stream);
+}
+
+// ---- scaled decode-accumulate (no upstream equivalent) ----------------------------
+int dgpu_float_decode_accumulate_scaled(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, const void* const* in, const uint32_t* inBytes, void* const* out, const uint32_t* outCapacity,
+    float scale, const float* scale_dev, uint32_t scaleStride, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream) {
+  (void)temp_dev;
+  (void)tempBytes;
+  const DecodeFactor factor{scale, scale_dev, scaleStride};
+  return decodeAccumulateImpl(tempUsed, floatType, probBits, accumulate, numInBatch, in, inBytes, out, outCapacity,
+                              outSuccess_dev, outSize_dev, (hipStream_t)stream, &factor);
 }
 
 // ---- scaled decompress (no upstream equivalent) -----------------------------------

@@ -182,6 +182,8 @@ constexpr uint32_t halvesOnly(uint32_t ft) { return ft == kFloat16 ? kFloat16 : 
 //   * kWholeScaled: the whole decode that multiplies every word by the member's factor (DecodeArgs::scalePtr /
 //     scaleStride / scale); float types only, the LDS of the whole form.  There is no scaled form of k_ans_decode_pair:
 //     single-block batches run on 4-block tiles;
+//   * kAccumScaled: kAccum whose widened word is multiplied by the member's factor (as kWholeScaled takes it) before
+//     the store or the add; float types only, the LDS of kAccum;
 //   * kRanged: decodes a block range of every element (a range of one or two blocks takes the 4-block form).
 #define DGPU_DECODE_FORMS(X)                                                                                           \
   X(kAccum, k_ans_decode_accum, floatsOnly, decLdsBytes(P, T, TB))                                                     \
@@ -194,6 +196,7 @@ constexpr uint32_t halvesOnly(uint32_t ft) { return ft == kFloat16 ? kFloat16 : 
   X(kReduceNorm, k_ans_decode_reduce_mixed_norm, floatsOnly, decReduceNormLdsBytes(P, T, TB, false))                   \
   X(kReduceNormStats, k_ans_decode_reduce_mixed_stats_norm, halvesOnly, decReduceNormLdsBytes(P, T, TB, true))         \
   X(kWholeScaled, k_ans_decode_scaled, floatsOnly, decScaledLdsBytes(P, T, TB))                                        \
+  X(kAccumScaled, k_ans_decode_accum_scaled, floatsOnly, decLdsBytes(P, T, TB))                                        \
   X(kRanged, k_ans_decode_range, sameType, decLdsBytes(P, T, TB))
 
 // The decoder of tiles of `tileBlocks` blocks.  A form of the list above takes the 4-block instantiation for tiles of

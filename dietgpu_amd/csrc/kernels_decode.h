@@ -80,8 +80,9 @@ struct DecodeArgs {
   // numInBatch * maxTiles float64, the counts of its non-finite ones (decodeReduceTile, kNorm); k_reduce_norm_finish
   // adds a member's partials in tile order
   double* normPartials = nullptr;
-  // k_ans_decode_scaled only: the factor of member b is scalePtr[b * scaleStride] (device memory, read when the kernel
-  // runs; scaleStride 0: one factor for the call, 1: one per member), or `scale` above when scalePtr is null
+  // k_ans_decode_scaled and k_ans_decode_accum_scaled: the factor of member b is scalePtr[b * scaleStride] (device
+  // memory, read when the kernel runs; scaleStride 0: one factor for the call, 1: one per member), or `scale` above when
+  // scalePtr is null
   const float* scalePtr = nullptr;
   uint32_t scaleStride = 0;
 };
@@ -374,12 +375,33 @@ typedef __attribute__((address_space(3))) float LdsF32w;
 // (__fmul_rn: never contracted)
 __device__ __forceinline__ uint32_t accScale(uint32_t o, float f) { return __builtin_bit_cast(uint32_t, __fmul_rn(__builtin_bit_cast(float, o), f)); }
 
+// kPreScaled (k_ans_decode_accum_scaled): the WIDENED word is multiplied by the member's factor before the add --
+// acc = [acc +] fl32(widened * factor): one IEEE float32 multiply and one IEEE add, each rounded once, never an FMA.
+// The factor is wave-uniform, set by decodeTile, and lives in a register: the plain sinks only (see above).  The pair is
+// written with contraction switched off: __fmul_rn and __fadd_rn are the plain operators in the HIP headers, and a
+// multiply that feeds an add is otherwise fused into one FMA by the translation unit's contraction mode.
+__device__ __forceinline__ float accMulUnfused(float v, float f) {
+#pragma clang fp contract(off)
+  return v * f;
+}
+__device__ __forceinline__ uint32_t accAddUnfused(uint32_t acc, float p) {
+#pragma clang fp contract(off)
+  return __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, acc) + p);
+}
+template <bool kHasFactor>
+struct AccumFactor {};
+template <>
+struct AccumFactor<true> {
+  float preFactor;
+};
+
 // kUnitAware (the norm forms, which serve a factor of 1 as well): the counting sink multiplies by a factor other than 1
 // only, so that a factor of 1 leaves the bits of the unscaled call (a multiply by 1 quiets a signalling NaN).  The
 // plain sinks need nothing: their flag is simply not set (reduceScales).
-template <uint32_t FT, uint32_t kSlots = 0, bool kScaledSink = false, bool kUnitAware = false>
-struct AccumSink : AccumBins<kSlots != 0u>, AccumScale<kScaledSink && kSlots == 0u> {  // kFloat16 / kBFloat16
+template <uint32_t FT, uint32_t kSlots = 0, bool kScaledSink = false, bool kUnitAware = false, bool kPreScaled = false>
+struct AccumSink : AccumBins<kSlots != 0u>, AccumScale<kScaledSink && kSlots == 0u>, AccumFactor<kPreScaled> {  // kFloat16 / kBFloat16
   static_assert(FT == kFloat16 || FT == kBFloat16, "");
+  static_assert(!kPreScaled || (kSlots == 0u && !kScaledSink), "the pre-scaled sink is a plain sink");
   static constexpr bool kStats = kSlots != 0u;
   static constexpr bool kScaled = kScaledSink;
   static constexpr bool kUnit = kUnitAware;
@@ -425,8 +447,11 @@ struct AccumSink : AccumBins<kSlots != 0u>, AccumScale<kScaledSink && kSlots == 
   }
   // h: the 16-bit word of FT in the LOW half
   __device__ __forceinline__ void storeWord(uint32_t row, uint32_t h, const AccumPre& p) const {
-    const float v = accWiden16<FT>(h);
-    uint32_t o = accumulate ? accAdd(p.acc, v) : __builtin_bit_cast(uint32_t, v);
+    float v = accWiden16<FT>(h);
+    if constexpr (kPreScaled) v = accMulUnfused(v, this->preFactor);
+    uint32_t o;
+    if constexpr (kPreScaled) o = accumulate ? accAddUnfused(p.acc, v) : __builtin_bit_cast(uint32_t, v);
+    else o = accumulate ? accAdd(p.acc, v) : __builtin_bit_cast(uint32_t, v);
     if constexpr (kScaled && kStats && kUnit) {
       if (scales()) {
         const float f = factor();
@@ -480,11 +505,20 @@ struct AccumSink : AccumBins<kSlots != 0u>, AccumScale<kScaledSink && kSlots == 
       v[2u * k] = accWiden16<FT>(w[k] & 0xffffu);
       v[2u * k + 1u] = accWiden16<FT>(w[k] >> 16);
     }
+    if constexpr (kPreScaled) {
+#pragma unroll
+      for (uint32_t k = 0; k < 8u; ++k) v[k] = accMulUnfused(v[k], this->preFactor);
+    }
     u32x4w o0, o1;
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
-      o0[k] = accumulate ? accAdd(p.a0[k], v[k]) : __builtin_bit_cast(uint32_t, v[k]);
-      o1[k] = accumulate ? accAdd(p.a1[k], v[4u + k]) : __builtin_bit_cast(uint32_t, v[4u + k]);
+      if constexpr (kPreScaled) {
+        o0[k] = accumulate ? accAddUnfused(p.a0[k], v[k]) : __builtin_bit_cast(uint32_t, v[k]);
+        o1[k] = accumulate ? accAddUnfused(p.a1[k], v[4u + k]) : __builtin_bit_cast(uint32_t, v[4u + k]);
+      } else {
+        o0[k] = accumulate ? accAdd(p.a0[k], v[k]) : __builtin_bit_cast(uint32_t, v[k]);
+        o1[k] = accumulate ? accAdd(p.a1[k], v[4u + k]) : __builtin_bit_cast(uint32_t, v[4u + k]);
+      }
     }
     if constexpr (kScaled && kStats && kUnit) {
       if (scales()) {
@@ -526,9 +560,10 @@ struct AccumSink : AccumBins<kSlots != 0u>, AccumScale<kScaledSink && kSlots == 
   }
 };
 
-template <uint32_t kSlots, bool kScaledSink, bool kUnitAware>
-struct AccumSink<kFloat32, kSlots, kScaledSink, kUnitAware> : AccumScale<kScaledSink> {  // row-wise, as RowSink<kFloat32>: 128-byte pieces already
+template <uint32_t kSlots, bool kScaledSink, bool kUnitAware, bool kPreScaled>
+struct AccumSink<kFloat32, kSlots, kScaledSink, kUnitAware, kPreScaled> : AccumScale<kScaledSink>, AccumFactor<kPreScaled> {  // row-wise, as RowSink<kFloat32>: 128-byte pieces already
   static_assert(kSlots == 0u, "counting sinks: the 16-bit archive types only");
+  static_assert(!kPreScaled || !kScaledSink, "the pre-scaled sink is a plain sink");
   static constexpr bool kStats = false;
   static constexpr bool kScaled = kScaledSink;
   static constexpr bool kUnit = kUnitAware;
@@ -555,7 +590,13 @@ struct AccumSink<kFloat32, kSlots, kScaledSink, kUnitAware> : AccumScale<kScaled
     return p;
   }
   __device__ __forceinline__ void storeWord(uint32_t row, uint32_t w, const AccumPre& p) const {
-    uint32_t o = accumulate ? accAdd(p.acc, __builtin_bit_cast(float, w)) : w;
+    uint32_t o;
+    if constexpr (kPreScaled) {
+      w = __builtin_bit_cast(uint32_t, accMulUnfused(__builtin_bit_cast(float, w), this->preFactor));
+      o = accumulate ? accAddUnfused(p.acc, __builtin_bit_cast(float, w)) : w;
+    } else {
+      o = accumulate ? accAdd(p.acc, __builtin_bit_cast(float, w)) : w;
+    }
     if constexpr (kScaled) {
       if (this->scaleLast != 0u) o = accScale(o, this->scale);
     }
@@ -926,7 +967,7 @@ __device__ __forceinline__ void decodeBlock(
 
 // One workgroup of the tiled decoder: 32 threads per block of the tile (512 or 128), LDS = word rings + 64-bit LUT.
 // The body of k_ans_decode (DecodeForm::kWhole), k_ans_decode_range (kRanged), k_ans_decode_accum (kAccum) and
-// k_ans_decode_scaled (kWholeScaled), below.
+// k_ans_decode_scaled (kWholeScaled) and k_ans_decode_accum_scaled (kAccumScaled), below.
 //
 // kRanged: blocks [firstBlock[b], firstBlock[b] + numBlocks[b]) of element b, clipped to the element's end, and block
 // firstBlock + k goes to out + k * 4096 words: the output buffer holds the range, not the element.
@@ -955,15 +996,22 @@ __device__ __forceinline__ void decodeBlock(
 // and rounded back to FT before it is stored (ScaledSink).  Everything else -- checks, success, outSize, the words behind
 // a short element -- is kWhole's.  The factor (DecodeArgs::scalePtr / scaleStride, or the host's DecodeArgs::scale) is
 // wave-uniform and is requested with the header, so it is there long before the first store.
+//
+// kAccumScaled: kAccum whose widened word is multiplied by the member's float32 factor before it is stored or added:
+// acc = [acc +] fl32(widened * factor), one multiply and one add, never fused (AccumSink, kPreScaled).  The factor is
+// fetched as kWholeScaled fetches it; everything else is kAccum's, the descriptor checks of every tile included.
 // (kReduce: decodeReduceTile, below)
-enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats, kReduceNorm, kReduceNormStats, kWholeScaled };
+enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats, kReduceNorm, kReduceNormStats, kWholeScaled, kAccumScaled };
 template <int P, uint32_t FT, uint32_t kTileBlocks, DecodeForm kForm>
 __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
-  constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccum = kForm == DecodeForm::kAccum, kScaledForm = kForm == DecodeForm::kWholeScaled;
-  static_assert(kForm == DecodeForm::kWhole || kForm == DecodeForm::kRanged || kForm == DecodeForm::kAccum || kScaledForm,
+  constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccumScaled = kForm == DecodeForm::kAccumScaled;
+  constexpr bool kAccum = kForm == DecodeForm::kAccum || kAccumScaled;                 // the accumulating forms
+  constexpr bool kScaledForm = kForm == DecodeForm::kWholeScaled || kAccumScaled;       // the forms with a factor
+  static_assert(kForm == DecodeForm::kWhole || kForm == DecodeForm::kRanged || kAccum || kScaledForm,
                 "decode-reduce has a body of its own: decodeReduceTile");
   static_assert(!(kAccum || kScaledForm) || FT != 0u, "accumulating and scaled decode: float archives only");
-  using Sink = std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32>, std::conditional_t<kScaledForm, ScaledSink<FT ? FT : kFloat32>, RowSink<FT>>>;
+  using Sink = std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32, 0u, false, false, kAccumScaled>,
+                                  std::conditional_t<kScaledForm, ScaledSink<FT ? FT : kFloat32>, RowSink<FT>>>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks);
   // the LUT-build scratch (cdf, pdf: 2 KiB, read while the LUT is stored) sits in the ring area
   static_assert(kTileBlocks * kRingBytes >= 2048u, "");
@@ -1135,7 +1183,8 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   const uint8_t* gwords = ans + ansOverhead(nb) + 2u * (size_t)start;
   Sink sink;
   if constexpr (kAccum) sink.accumulate = a.accumulate;
-  if constexpr (kScaledForm) sink.factor = factor;
+  if constexpr (kAccumScaled) sink.preFactor = factor;
+  else if constexpr (kScaledForm) sink.factor = factor;
   // (a half without a block points at its wave's first block: its prefetches must stay inside the archive -- kAccum:
   // and inside the accumulator)
   uint32_t sinkBlock = haveBlock ? block : (block & ~1u);
@@ -1911,6 +1960,14 @@ template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_scaled(DecodeArgs a) {
   static_assert(FT != 0u, "scaled decode: float archives only");
   decodeTile<P, FT, kTileBlocks, DecodeForm::kWholeScaled>(a);
+}
+
+// Scaled accumulating form: k_ans_decode_accum with the widened word multiplied by the member's factor before the store
+// or the add (DecodeArgs::scalePtr / scaleStride / scale).  Grid, order and LDS as k_ans_decode_accum.
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_accum_scaled(DecodeArgs a) {
+  static_assert(FT != 0u, "accumulating decode: float archives only");
+  decodeTile<P, FT, kTileBlocks, DecodeForm::kAccumScaled>(a);
 }
 
 // Reducing form: grid and order as k_ans_decode_accum, DecodeArgs::numSources archives per accumulator (decodeReduceTile).

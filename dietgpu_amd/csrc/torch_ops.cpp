@@ -525,6 +525,48 @@ int64_t decompress_data_accumulate(
   return (int64_t)used;
 }
 
+// A tensor factor of the scaled decode calls: a float32 tensor on the tensors' GPU with 1 element (stride 0) or one per
+// archive (stride 1).  The kernel reads it; nothing here does.  No tensor: null, the call's host float is used.
+static const float* scaleFactors(const std::optional<at::Tensor>& scaleDev, size_t n, int dev, uint32_t* stride) {
+  *stride = 0;
+  if (!scaleDev) return nullptr;
+  const at::Tensor& s = *scaleDev;
+  TORCH_CHECK(s.device().is_cuda() && s.get_device() == dev && s.is_contiguous() && s.scalar_type() == at::ScalarType::Float,
+              "dietgpu: a tensor scale must be a contiguous float32 tensor on the tensors' GPU");
+  TORCH_CHECK(s.numel() == 1 || s.numel() == (int64_t)n, "dietgpu: a tensor scale holds 1 element or one per archive");
+  *stride = (s.numel() == 1) ? 0u : 1u;
+  return (const float*)s.data_ptr();
+}
+
+// Scaled decode-accumulate (no reference op): decompress_data_accumulate whose every widened word is multiplied by a
+// float32 factor before it is stored or added (dgpu_float_decode_accumulate_scaled).  scale_dev as in
+// decompress_data_scaled; without it: `scale`.
+int64_t decompress_data_accumulate_scaled(
+    const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tAccs, int64_t floatType, bool accumulate, double scale,
+    const std::optional<at::Tensor>& scaleDev, const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outStatus,
+    const std::optional<at::Tensor>& outSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.size() == tAccs.size());
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType >= (int64_t)DGPU_FLOAT16 && floatType <= (int64_t)DGPU_FLOAT32, "dietgpu: float_type must be 1, 2 or 3");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  Temp tmp = tempOf(tempMem, dev);
+  const size_t n = tIns.size();
+  DecodeTensors m = marshalDecode(true, tIns, tAccs, dev, [&](size_t i) {
+    TORCH_CHECK(tAccs[i].scalar_type() == at::ScalarType::Float, "dietgpu: accumulators must be float32");
+  });
+  uint32_t stride = 0;
+  const float* factors = scaleFactors(scaleDev, n, dev, &stride);
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  size_t used = 0;
+  check(dgpu_float_decode_accumulate_scaled(tmp.ptr, tmp.bytes, &used, (uint32_t)floatType, precision(), accumulate ? 1 : 0, (uint32_t)n,
+                                                m.inPtrs.data(), m.inBytes.data(), m.outPtrs.data(), m.outCapacity.data(), (float)scale,
+                                                factors, stride, ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
+        "floatDecompressAccumulateScaled", true);
+  return (int64_t)used;
+}
+
 // Scaled decompress (no reference op): the float decode of archive i into ts_out[i] with every word multiplied by a
 // float32 factor before it is stored (dgpu_float_decode_scaled).  scale_dev: a float32 tensor on the tensors' GPU
 // with 1 element (one factor) or one per archive; the kernel reads it, nothing here does.  Without it: `scale`.
@@ -541,16 +583,8 @@ int64_t decompress_data_scaled(
   DecodeTensors m = marshalDecode(true, tIns, tOuts, dev, [&](size_t i) {
     TORCH_CHECK(tOuts[i].scalar_type() == tOuts[0].scalar_type(), "dietgpu: outputs must share one float dtype");
   });
-  const float* factors = nullptr;
   uint32_t stride = 0;
-  if (scaleDev) {
-    const at::Tensor& s = *scaleDev;
-    TORCH_CHECK(s.device().is_cuda() && s.get_device() == dev && s.is_contiguous() && s.scalar_type() == at::ScalarType::Float,
-                "dietgpu: a tensor scale must be a contiguous float32 tensor on the tensors' GPU");
-    TORCH_CHECK(s.numel() == 1 || s.numel() == (int64_t)n, "dietgpu: a tensor scale holds 1 element or one per archive");
-    factors = (const float*)s.data_ptr();
-    stride = (s.numel() == 1) ? 0u : 1u;
-  }
+  const float* factors = scaleFactors(scaleDev, n, dev, &stride);
   validateStatus(outStatus, outSizes, (int64_t)n, dev);
   size_t used = 0;
   check(dgpu_float_decode_scaled(tmp.ptr, tmp.bytes, &used, floatTypeFromDtype(tOuts[0].scalar_type()), precision(), (uint32_t)n,
@@ -941,6 +975,9 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "decompress_data_accumulate(Tensor[] ts_in, Tensor[] ts_acc, int float_type, bool accumulate=True, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
       &dietgpu_amd::decompress_data_accumulate);
+  m.def(
+      "decompress_data_accumulate_scaled(Tensor[] ts_in, Tensor[] ts_acc, int float_type, bool accumulate, float scale, Tensor? scale_dev=None, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
+      &dietgpu_amd::decompress_data_accumulate_scaled);
   m.def(
       "decompress_data_scaled(Tensor[] ts_in, Tensor[] ts_out, float scale, Tensor? scale_dev=None, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_decompressed_words=None) -> int",
       &dietgpu_amd::decompress_data_scaled);

@@ -175,12 +175,15 @@ class GpuFloatCodec:
         self.ops.decompress_data(True, rows, outs, False, self.temp_mem, status, None)
         return status
 
-    def decompress_accumulate(self, rows, accs, accumulate):
-        """rows widened to float32 and stored to (accumulate false) or added into the float32 tensors `accs` -> status"""
+    def decompress_accumulate(self, rows, accs, accumulate, scale=None):
+        """rows widened to float32 and stored to (accumulate false) or added into the float32 tensors `accs` -> status.
+        `scale` (a number, or a float32 tensor of 1 or len(rows) elements on the device): every widened word is multiplied
+        by it in the decode kernel before the store or the add, one multiply and one add, never an FMA
+        (ops.decompress_data_accumulate's `scale`); a tensor is never read by the host"""
         from . import ops
 
         status = torch.zeros((len(rows),), dtype=torch.uint8, device=accs[0].device)
-        ops.decompress_data_accumulate(rows, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype)
+        ops.decompress_data_accumulate(rows, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype, scale=scale)
         return status
 
     def _reduce(self, name, mixed, rows_per_acc, accs, accumulate, scale, norm):
@@ -253,10 +256,41 @@ def _scaled_decompress(codec, rows, outs, scale):
     return status
 
 
-def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec, scale=None):
+def _decode_into_float32(codec, rows, accs, factor, accumulate, dtype):
+    """The rows (archives of `dtype`) decoded into the float32 tensors `accs`: acc = [acc +] fl32(widen(word) * factor),
+    one float32 multiply and one float32 add (factor None: the exact widening, no multiply) -> status.  A codec whose
+    `decompress_accumulate` has a `scale` parameter does it in ONE call (GpuFloatCodec: in the decode kernel; a tensor
+    factor is never read by the host); without a factor the method gets the three arguments it always got; a
+    `decompress_accumulate` without the parameter decodes into a float32 scratch, which then takes `mul_` by the 0-dim
+    factor and `copy_` / `add_`; a codec without the method decodes with `decompress` into a scratch of `dtype`, which is
+    widened first.  The same bits every way."""
+    method = getattr(codec, "decompress_accumulate", None)
+    if callable(method):
+        if factor is None:
+            return method(rows, accs, accumulate)
+        if _takes_scale(method):
+            return method(rows, accs, accumulate, scale=factor)
+        wide = [torch.empty_like(a) for a in accs]
+        status = method(rows, wide, False)
+    else:
+        narrow = [torch.empty(a.shape, dtype=dtype, device=a.device) for a in accs]
+        status = codec.decompress(rows, narrow)
+        wide = [t.float() for t in narrow]
+    for a, w in zip(accs, wide):
+        if factor is not None:
+            w.mul_(factor)
+        if accumulate:
+            a.add_(w)
+        else:
+            a.copy_(w)
+    return status
+
+
+def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec, scale=None, decode=None):
     """The exchange of compressed_all_gather for rows that are compressed already: `comp` [n, cap] / `sizes` [n] as a
     codec's compress returns them; `outs_of(r)` -> the n tensors rank r's rows are decompressed into.  `scale`: see
-    compressed_all_gather."""
+    compressed_all_gather.  `decode(rows, outs)` -> status: what decodes a rank's rows instead of the codec's
+    `decompress` (compressed_all_reduce's `out`)."""
     world = dist.get_world_size()
     n = comp.shape[0]
     sizes = sizes.to(torch.int32)
@@ -277,7 +311,7 @@ def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec, scale=None):
     for r in range(world):
         rows = [gathered_payload[r][i, : int(all_sizes[r, i])] for i in range(n)]
         outs = outs_of(r)
-        status = _scaled_decompress(codec, rows, outs, scale)
+        status = decode(rows, outs) if decode is not None else _scaled_decompress(codec, rows, outs, scale)
         if not bool(status.all().item()):
             raise RuntimeError(f"decompression of rank {r}'s rows failed")
         gathered.append(outs)
@@ -539,7 +573,7 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
 
 
 def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False, clip_norm=None, wire_dtype=None,
-                          residual=None, residual_fresh=False):
+                          residual=None, residual_fresh=False, out=None, out_scale=None, out_accumulate=False):
     """All-reduce (sum) of a flat fp16 / bf16 tensor, moving compressed bytes both ways and summing in float32.
 
     Three steps: `compressed_reduce_scatter` (this rank's float32 shard of the sum), the codec's `compress_cast` of that
@@ -584,12 +618,47 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
     wire_dtype, residual, residual_fresh: as in compressed_reduce_scatter -- a float32 `tensor` whose shards travel as
     archives of wire_dtype, with error feedback on that first rounding when a residual is given.  The call then returns
     the sum in wire_dtype.  Its second rounding -- of the float32 sum, before the all-gather -- carries NO feedback: it is
-    the same on every rank and would need a residual per shard of the sum."""
+    the same on every rank and would need a residual per shard of the sum.
+
+    out (a flat contiguous float32 tensor of the tensor's length on its device; for 16-bit tensors and for float32
+    tensors with wire_dtype alike): the result is delivered in FLOAT32.  The final all-gather decodes every rank's shard
+    archive straight into out.view(world, -1)[r]; no 16-bit result tensor exists, and the call returns (out, stats).
+    Without a factor the widening is exact: out == (today's result).float().  The factor f is `coef` with clip_norm,
+    `out_scale` with out_scale -- a number, finite and not zero, rounded once to float32, or a 0-dim / 1-element float32
+    tensor on the device (-lr: the update of float32 master weights) -- and fl32(coef * out_scale) with both, one float32
+    multiply of two 0-dim device tensors; nothing is read by the host.  Then out[k] = [out[k] +] fl32(widen(word_k) * f):
+    one float32 multiply and, with out_accumulate=True (gradient accumulation into a float32 buffer), one float32 add,
+    never fused; with a clip that is one rounding fewer than the 16-bit result has, whose bits out.to(dtype) still gives.
+    A codec whose `decompress_accumulate` has a `scale` parameter makes one call per source rank (GpuFloatCodec: in the
+    decode kernel); any other codec is decoded into a scratch and takes the multiply and the add from torch, with the
+    same bits.  `out is tensor` is allowed without out_accumulate -- an in-place float32 all-reduce on a 16-bit wire;
+    every read of `tensor` precedes the gather -- and is an error with it; `out` must not overlap `tensor` otherwise.
+    out_scale or out_accumulate without out is an error.  The statistics keep their meaning: "sumsq", "nonfinite" and
+    "global_*" describe the 16-bit words of the archives, unclipped and without out_scale, as without `out`.  With
+    out=None the call is what it was."""
     codec = codec or GpuFloatCodec()
     _check_wire("compressed_all_reduce", tensor, codec, raw_local, wire_dtype, residual)
     out_dtype = wire_dtype if wire_dtype is not None else tensor.dtype
     if out_dtype not in _WIRE_DTYPES:
         raise RuntimeError("compressed_all_reduce: the tensor must be float16 or bfloat16 (float32: give wire_dtype)")
+    if out is None:
+        if out_scale is not None or out_accumulate:
+            raise RuntimeError("compressed_all_reduce: out_scale and out_accumulate need `out`")
+    else:
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.dim() == 1 and out.is_contiguous()
+                and out.numel() == tensor.numel() and out.device == tensor.device):
+            raise RuntimeError("compressed_all_reduce: out must be a flat contiguous float32 tensor of the tensor's length on its device")
+        if out is tensor and out_accumulate:
+            raise RuntimeError("compressed_all_reduce: out is the tensor itself: out_accumulate is not possible")
+        if isinstance(out_scale, torch.Tensor):
+            if not (out_scale.dtype == torch.float32 and out_scale.numel() == 1 and out_scale.device == tensor.device):
+                raise RuntimeError("compressed_all_reduce: a tensor out_scale must be a 0-dim or 1-element float32 tensor on the tensor's device")
+            out_scale = out_scale.reshape(())
+        elif out_scale is not None:
+            f32 = ctypes.c_float(float(out_scale)).value
+            if not math.isfinite(f32) or f32 == 0.0:
+                raise RuntimeError("compressed_all_reduce: out_scale must be finite and not zero")
+            out_scale = torch.tensor(f32, dtype=torch.float32, device=tensor.device)
     if clip_norm is not None:
         clip_norm = float(clip_norm)
         if not (math.isfinite(clip_norm) and clip_norm > 0.0):
@@ -623,8 +692,21 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
             shard, rs = compressed_reduce_scatter(tensor, codec, raw_local, scale=factor, wire_dtype=wire_dtype, residual=residual,
                                                   residual_fresh=residual_fresh)
         comp, sizes = codec.compress_cast([shard], out_dtype)
-    out = torch.empty(tensor.shape, dtype=out_dtype, device=tensor.device)
-    rows = out.view(world, shard.numel())
+    gathered_bytes = shard.numel() * (torch.finfo(out_dtype).bits // 8)
+    if out is None:
+        out = torch.empty(tensor.shape, dtype=out_dtype, device=tensor.device)
+        rows = out.view(world, shard.numel())
+
+        def all_gather(coef):
+            return _all_gather_archives(comp, sizes, lambda r: [rows[r]], gathered_bytes, codec, scale=coef)
+    else:
+        rows = out.view(world, shard.numel())
+
+        def all_gather(coef):
+            # the factor of the float32 decode: coef, out_scale, or their float32 product (0-dim tensors: nothing is read)
+            f = out_scale if coef is None else (coef if out_scale is None else coef * out_scale)
+            return _all_gather_archives(comp, sizes, lambda r: [rows[r]], gathered_bytes, codec,
+                                        decode=lambda rws, accs: _decode_into_float32(codec, rws, accs, f, out_accumulate, out_dtype))
     if clip_norm is not None:
         # the statistics first: the coefficient is known before the gather, whose decode applies it
         if not pair[2]:  # (the words of the archive: the shard rounded as the cast rounds it)
@@ -633,14 +715,14 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
         dist.all_reduce(both)
         # torch.nn.utils.clip_grad_norm_'s formula, in float64 on the device, rounded once to float32
         coef = torch.clamp(clip_norm / (both[0].sqrt() + 1e-6), max=1.0).to(torch.float32)
-        _, ag = _all_gather_archives(comp, sizes, lambda r: [rows[r]], shard.numel() * out.element_size(), codec, scale=coef)
+        _, ag = all_gather(coef)
         stats = {k: rs[k] + ag[k] for k in rs}
         _norm_stats(stats, pair)
         stats["global_sumsq"] = both[0]
         stats["global_nonfinite"] = both[1].to(torch.int32)
         stats["clip_coef"] = coef
         return out, stats
-    _, ag = _all_gather_archives(comp, sizes, lambda r: [rows[r]], shard.numel() * out.element_size(), codec)
+    _, ag = all_gather(None)
     stats = {k: rs[k] + ag[k] for k in rs}
     if norm:
         if not pair[2]:  # (the words of the archive: the shard rounded as the cast rounds it)

@@ -671,7 +671,7 @@ def decompress_data_range(compress_as_float, ts_in, ts_out, first_block, num_blo
 # ------------------------------------------------------------- decode-accumulate
 # (no reference op: dgpu_float_decode_accumulate, include/dietgpu_amd.h)
 def decompress_data_accumulate(ts_in, ts_acc, accumulate=True, temp_mem=None, out_status=None, out_sizes=None,
-                               prob_bits=K_DEFAULT_PRECISION, dtype=None):
+                               prob_bits=K_DEFAULT_PRECISION, dtype=None, scale=None):
     """Decodes float archive ts_in[i], widens every word to float32 and adds it into ts_acc[i] (accumulate=True: one IEEE
     float32 add per word) or stores it there (accumulate=False: the accumulator is not read -- a 16-bit archive straight
     into float32, and the first source of a sum) -> temp bytes used (0).  ts_acc: float32 CUDA tensors that do not overlap.
@@ -680,11 +680,22 @@ def decompress_data_accumulate(ts_in, ts_acc, accumulate=True, temp_mem=None, ou
     or captures the call into a graph, passes), else the type in the header of ts_in[0], read with one synchronising
     copy (`_header_info`).  out_status[i] is 0, and ts_acc[i] untouched, for an archive of another type, a malformed or
     truncated one, or one that does not fit ts_acc[i]; out_sizes[i] is the size its header states.  There is no
-    `checksum`: a checksum covers the 16-bit words, which never reach memory here, and is ignored."""
+    `checksum`: a checksum covers the 16-bit words, which never reach memory here, and is ignored.
+
+    `scale` (dgpu_float_decode_accumulate_scaled): every widened word is multiplied by a float32 factor before it is
+    stored or added, ts_acc[i][k] = [ts_acc[i][k] +] fl32(widen(word) * s) -- one IEEE float32 multiply and one IEEE add,
+    each rounded once, never an FMA: bit for bit this call into a scratch, `mul_` by a 0-dim float32 tensor and `add_`.
+    A Python number is rounded once to float32 and must be finite and not zero (None, or one whose float32 is 1.0, is the
+    call without it); a float32 CUDA tensor on the tensors' device, contiguous, with 1 element (one factor for the call)
+    or len(ts_in) elements (one per archive) is read by the kernel when it runs and never by the host: it may hold any
+    value (a 1 multiplies), may be the result of work enqueued before this call, and a captured call follows the value it
+    holds at each replay."""
     _check(len(ts_in) > 0)
     _check(len(ts_in) == len(ts_acc))
+    host, dev_scale = _scale_arg(scale, len(ts_in))
     _check(ts_in[0].is_cuda, "tensors must be on the GPU")
     dev = ts_in[0].get_device()
+    _check(dev_scale is None or dev_scale.get_device() == dev, "a tensor scale must be on the tensors' GPU")
     for ti, ta in zip(ts_in, ts_acc):
         _check(ti.is_cuda and ti.get_device() == dev and ti.is_contiguous() and ti.dtype == torch.uint8)
         _check(ta.is_cuda and ta.get_device() == dev and ta.is_contiguous(), "accumulators must be contiguous tensors on the GPU")
@@ -700,10 +711,19 @@ def decompress_data_accumulate(ts_in, ts_acc, accumulate=True, temp_mem=None, ou
         else:
             ft = _header_info(True, ts_in[:1], tp, tb)[1][0]
             _check(ft in _FT_TO_DTYPE, "ts_in[0] is not a float archive")
+        used = C.c_size_t(0)
+        if host is not None:
+            op = _amd_op(prob_bits, "decompress_data_accumulate_scaled")
+            if op is not None:
+                return op(ts_in, ts_acc, ft, bool(accumulate), host, dev_scale, temp_mem, out_status, out_sizes)
+            check(lib().dgpu_float_decode_accumulate_scaled(
+                tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, _ptr_array(ts_in), _in_bytes(ts_in),
+                _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), host, _ptr(dev_scale),
+                0 if dev_scale is None or dev_scale.numel() == 1 else 1, _ptr(out_status), _ptr(out_sizes), _stream()))
+            return int(used.value)
         op = _amd_op(prob_bits, "decompress_data_accumulate")
         if op is not None:
             return op(ts_in, ts_acc, ft, bool(accumulate), temp_mem, out_status, out_sizes)
-        used = C.c_size_t(0)
         check(lib().dgpu_float_decode_accumulate(
             tp, tb, C.byref(used), ft, prob_bits, int(bool(accumulate)), n, _ptr_array(ts_in), _in_bytes(ts_in),
             _ptr_array(ts_acc), _u32_array([t.numel() for t in ts_acc]), _ptr(out_status), _ptr(out_sizes), _stream()))
@@ -728,18 +748,9 @@ def decompress_data_scaled(ts_in, ts_out, scale, temp_mem=None, out_status=None,
     _check(len(ts_in) > 0)
     _check(len(ts_in) == len(ts_out))
     n = len(ts_in)
-    if isinstance(scale, torch.Tensor):
-        _check(scale.dtype == torch.float32, "a tensor scale must be float32")
-        _check(scale.numel() in (1, n), "a tensor scale holds 1 element or one per archive")
-        _check(scale.is_cuda and scale.is_contiguous(), "a tensor scale must be a contiguous tensor on the tensors' GPU")
-        host, dev_scale = 1.0, scale
-    else:
-        try:
-            host, dev_scale = _scale32(scale), None
-        except (TypeError, ValueError):
-            raise RuntimeError("scale must be a number or a float32 tensor") from None
-        if host is None:
-            return decompress_data(True, ts_in, ts_out, False, temp_mem, out_status, out_decompressed_words, prob_bits=prob_bits)
+    host, dev_scale = _scale_arg(scale, n)
+    if host is None:
+        return decompress_data(True, ts_in, ts_out, False, temp_mem, out_status, out_decompressed_words, prob_bits=prob_bits)
     _check(ts_in[0].is_cuda, "tensors must be on the GPU")
     dev = ts_in[0].get_device()
     _check(dev_scale is None or dev_scale.get_device() == dev, "a tensor scale must be on the tensors' GPU")
@@ -772,6 +783,21 @@ def _scale32(scale):
     f = C.c_float(float(scale)).value
     _check(math.isfinite(f) and f != 0.0, "scale must be finite and not zero")
     return None if f == 1.0 else f
+
+
+def _scale_arg(scale, n):
+    """The `scale` of the scaled decode calls over n archives -> (host float, device tensor or None); (None, None): the
+    call without a factor (None, or a number whose float32 is 1.0).  A tensor is float32, contiguous, on the GPU, with 1
+    or n elements, and is not read; a number is rounded once to float32 and must be finite and not zero."""
+    if isinstance(scale, torch.Tensor):
+        _check(scale.dtype == torch.float32, "a tensor scale must be float32")
+        _check(scale.numel() in (1, n), "a tensor scale holds 1 element or one per archive")
+        _check(scale.is_cuda and scale.is_contiguous(), "a tensor scale must be a contiguous tensor on the tensors' GPU")
+        return 1.0, scale
+    try:
+        return _scale32(scale), None
+    except (TypeError, ValueError):
+        raise RuntimeError("scale must be a number or a float32 tensor") from None
 
 
 def _norm_outputs(out_sumsq, out_nonfinite, n, dev=None):

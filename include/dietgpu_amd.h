@@ -72,7 +72,8 @@ const char* dgpu_version(void);
  * dgpu_float_reduce_compress_temp_bytes, dgpu_float_rolling_compress, dgpu_float_decode_reduce_mixed,
  * dgpu_float_reduce_compress_mixed, dgpu_float_decode_reduce_scaled, dgpu_float_reduce_compress_scaled,
  * dgpu_float_reduce_norm_temp_bytes, dgpu_float_decode_reduce_norm, dgpu_float_reduce_compress_norm and
- * dgpu_float_decode_scaled were added at version 8, dgpu_float_feedback_compress after them). */
+ * dgpu_float_decode_scaled were added at version 8, dgpu_float_feedback_compress and
+ * dgpu_float_decode_accumulate_scaled after them). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -308,6 +309,44 @@ int dgpu_float_decode_accumulate(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
     uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
     void* const* out /* float32 */, const uint32_t* outCapacity /* float words */,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
+
+/* ---- scaled decode-accumulate (no upstream equivalent) --------------------------------
+ * dgpu_float_decode_accumulate whose every widened word is multiplied by a float32 factor before it is stored or added:
+ * out = [out +] s * x in float32, with s read by the kernel from device memory.  It is the decode of the final
+ * all-gather of a compressed all-reduce into a float32 gradient buffer with the clip coefficient applied, gradient
+ * accumulation over micro-batches (accumulate == 1), and with s = -lr * coef the SGD update of float32 master weights
+ * straight from the archive.
+ *   - For every decoded word w of member i with factor s_i:  p = fl32(widen(w) * s_i);  out[i][k] = accumulate ?
+ *     fl32(out[i][k] + p) : p.  Widening is exact, as in dgpu_float_decode_accumulate (float32 archives: the identity).
+ *     ONE IEEE float32 multiply and ONE IEEE float32 add, each rounded once to nearest even, denormals kept, never fused
+ *     into an FMA: bit for bit what decode-accumulate into a scratch, a float32 multiply by the factor and a float32 add
+ *     compose to.  With accumulate == 0 the accumulator is not read.
+ *   - The factor: scale_dev != NULL points at DEVICE memory, 4-byte aligned, of 1 float (scaleStride == 0: one factor
+ *     for the call) or numInBatch floats (scaleStride == 1: member i takes scale_dev[i]).  It is read when the kernel
+ *     runs and never by the host, so it may be the result of work enqueued earlier on the stream, and a captured call
+ *     follows the value the memory holds at each replay.  It may hold ANY value -- 0, an infinity, a NaN, 1 -- and the
+ *     arithmetic above is the contract for all of them: a device factor of 1 multiplies (a signalling NaN leaves
+ *     quiet).  scale_dev == NULL: the host float `scale`, which must be finite and not zero.  A host float of exactly
+ *     1.0f IS dgpu_float_decode_accumulate (the call forwards to it): with accumulate == 0 a signalling NaN of a float32
+ *     archive keeps its bits.
+ *   - Everything else is dgpu_float_decode_accumulate's: every header and descriptor check, outSuccess_dev[i] and
+ *     outSize_dev[i]; a member that fails (outSuccess_dev[i] = 0) keeps every bit of its accumulator and does not
+ *     disturb the others; a capacity larger than the element leaves the words behind the element untouched; the
+ *     accumulators are 4-byte aligned and those of one call MUST NOT overlap; there is no useChecksum (a checksum in
+ *     the archive is ignored); one kernel geometry per call, from its largest capacity.
+ *   - floatType must be DGPU_FLOAT16, DGPU_BFLOAT16 or DGPU_FLOAT32, probBits 9, 10 or 11, accumulate 0 or 1,
+ *     scaleStride 0 or 1, scale_dev 4-byte aligned, a host scale finite and not zero, no array null when
+ *     numInBatch > 0, in[i] 16-byte aligned, out[i] 4-byte aligned, outCapacity[i] <= 0xfffff000:
+ *     DGPU_ERR_INVALID_ARGUMENT with a dgpu_last_error() text otherwise, before anything is enqueued.  An empty batch
+ *     returns 0.
+ *   - No temp memory is used (*tempUsed = 0) and nothing synchronises: capturable into a HIP graph under the same
+ *     conditions as the other pointer-array decode calls (the arrays resident from an earlier identical call). */
+int dgpu_float_decode_accumulate_scaled(
+    void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t floatType, int probBits, int accumulate,
+    uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
+    void* const* out /* float32 */, const uint32_t* outCapacity /* float words */,
+    float scale, const float* scale_dev /* nullable: the host float is used */, uint32_t scaleStride /* 0 or 1 */,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
 
 /* ---- scaled decompress (no upstream equivalent) ---------------------------------------

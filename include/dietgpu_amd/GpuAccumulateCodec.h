@@ -22,6 +22,23 @@ inline void floatDecompressAccumulate(
                   "floatDecompressAccumulate");
 }
 
+// Scaled decode-accumulate: floatDecompressAccumulate whose every widened word is multiplied by a float32 factor before it
+// is stored or added, out[i][k] = [out[i][k] +] fl32(widen(word) * s) -- one IEEE multiply and one IEEE add, never fused.
+// `scale_dev`: DEVICE memory holding 1 float (scaleStride 0: one factor for the call) or numInBatch floats (scaleStride
+// 1), read when the kernel runs and never by the host -- it may hold any value; null: the host float `scale`, which must
+// be finite and not zero, and 1.0f is floatDecompressAccumulate.  dgpu_float_decode_accumulate_scaled of ../dietgpu_amd.h.
+inline void floatDecompressAccumulateScaled(
+    StackDeviceMemory& res, const FloatDecompressConfig& config, bool accumulate, uint32_t numInBatch, const void** in,
+    const uint32_t* inBytes, float** out, const uint32_t* outCapacity, float scale, const float* scale_dev, uint32_t scaleStride,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+  (void)res;
+  size_t used = 0;
+  detail::checkRc(dgpu_float_decode_accumulate_scaled(nullptr, 0, &used, (uint32_t)config.floatType, config.ansConfig.probBits,
+                                                      accumulate ? 1 : 0, numInBatch, in, inBytes, (void* const*)out, outCapacity,
+                                                      scale, scale_dev, scaleStride, outSuccess_dev, outSize_dev, stream),
+                  "floatDecompressAccumulateScaled");
+}
+
 // Decode-reduce: numSources archives per accumulator, member-major (source s of member i is in[i * numSources + s], with
 // inBytes of the same shape), summed strictly left to right in ONE launch -- bit for bit what numSources successive
 // floatDecompressAccumulate calls leave, the first with `accumulate`, the rest with true -- and all or nothing per
