@@ -65,6 +65,7 @@ _SIGS = {
     "dgpu_release_stream_state": (i32, [vp]),
     "dgpu_release_all_stream_state": (i32, []),
     "dgpu_debug_stream_state_count": (u32, []),
+    "dgpu_debug_counters_nonzero": (C.c_int64, [vp]),
     "dgpu_prof_enable": (None, [i32]),
     "dgpu_prof_reset": (None, []),
     "dgpu_prof_summary": (i32, [C.c_char_p, sz]),

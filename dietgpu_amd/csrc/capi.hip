@@ -179,7 +179,8 @@ class StreamRegistry {
   // `busy` is taken (try_lock) while the registry mutex is held, so trimLocked() / release() -- which only drop
   // states whose `busy` they can take -- can never delete a state between its lookup and its use.  A state that is
   // busy (another host thread is enqueueing on the same stream) is waited for with the registry mutex released.
-  StreamState* acquire(hipStream_t stream, hipError_t* err) {
+  // `create` false: nullptr (with *err == hipSuccess) when the stream has no state.
+  StreamState* acquire(hipStream_t stream, hipError_t* err, bool create = true) {
     for (;;) {
       {
         std::lock_guard<std::mutex> g(mu_);
@@ -189,6 +190,7 @@ class StreamRegistry {
         auto key = std::make_pair(dev, stream);
         auto it = states_.find(key);
         if (it == states_.end()) {
+          if (!create) return nullptr;
           if (states_.size() >= kMaxStreams) trimLocked();
           StreamState* s = new StreamState();
           s->device = dev;
@@ -1856,6 +1858,24 @@ int dgpu_release_graph_state(void) {
 int dgpu_release_stream_state(void* stream) { return streamRegistry().release((hipStream_t)stream, false); }
 int dgpu_release_all_stream_state(void) { return streamRegistry().release(nullptr, true); }
 uint32_t dgpu_debug_stream_state_count(void) { return (uint32_t)streamRegistry().size(); }
+int64_t dgpu_debug_counters_nonzero(void* stream) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing((hipStream_t)stream, &st) != hipSuccess || st != hipStreamCaptureStatusNone) {
+    (void)hipGetLastError();
+    return -1;  // (a synchronise would invalidate a capture)
+  }
+  hipError_t e = hipSuccess;
+  StreamState* s = streamRegistry().acquire((hipStream_t)stream, &e, false);  // `busy` held: no call frees the counters underneath
+  if (!s) return -1;
+  int64_t n = -1;
+  std::vector<uint32_t> host(kCounterWordsArrive + kCounterWordsAcc + kCounterWordsSpill);
+  if (s->counters && hipStreamSynchronize((hipStream_t)stream) == hipSuccess &&
+      hipMemcpy(host.data(), s->counters, host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess) {
+    n = (int64_t)std::count_if(host.begin(), host.end(), [](uint32_t w) { return w != 0u; });
+  }
+  s->busy.unlock();
+  return n;
+}
 
 void dgpu_prof_enable(int on) {
   ProfState& p = prof();

@@ -758,6 +758,11 @@ int dgpu_release_stream_state(void* stream);
 int dgpu_release_all_stream_state(void);
 /* Test hook: number of (device, stream) states currently kept. */
 uint32_t dgpu_debug_stream_state_count(void);
+/* Test hook: synchronises `stream`, copies the hand-off counters the library keeps for it on the current device to the
+ * host -- 65536 arrival words, 64 x 256 histogram counters, 16384 spill-pool flags, all zero at rest -- and returns how
+ * many of them are not zero; -1 when the stream has no state or no counters yet (asking creates none), or is being
+ * captured. */
+int64_t dgpu_debug_counters_nonzero(void* stream);
 
 /* ---- instrumentation (no upstream equivalent) ------------------------------ */
 /* Per-kernel timing with HIP events recorded on the launch stream; used by
