@@ -27,6 +27,7 @@ from .ops import (  # noqa: F401
     decompress_data_simple,
     decompress_data_slice,
     decompress_data_split_size,
+    decompress_data_update,
     max_any_compressed_output_size,
     max_any_compressed_size,
     max_float_compressed_output_size,

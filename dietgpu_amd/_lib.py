@@ -43,6 +43,7 @@ _SIGS = {
     "dgpu_float_decode_accumulate": (i32, [vp, sz, vp, u32, i32, i32, u32, vp, vp, vp, vp, vp, vp, vp]),
     "dgpu_float_decode_accumulate_scaled": (i32, [vp, sz, vp, u32, i32, i32, u32, vp, vp, vp, vp, C.c_float, vp, u32, vp, vp, vp]),
     "dgpu_float_decode_scaled": (i32, [vp, sz, vp, u32, i32, u32, vp, vp, vp, vp, C.c_float, vp, u32, vp, vp, vp]),
+    "dgpu_float_decode_update": (i32, [u32, i32, i32, u32, vp, vp, vp, vp, C.c_float, vp, u32, C.c_uint64, vp, u32, vp, vp, vp]),
     "dgpu_float_decode_reduce": (i32, [vp, sz, vp, u32, i32, i32, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
     "dgpu_float_cast_compress": (i32, [vp, sz, vp, u32, i32, u32, vp, vp, vp, vp, vp]),
     "dgpu_float_feedback_compress": (i32, [vp, sz, vp, u32, i32, u32, vp, vp, vp, vp, vp, vp, vp]),

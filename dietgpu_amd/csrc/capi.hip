@@ -1633,6 +1633,44 @@ int decodeScaledImpl(
   return launchDecode(d, group, dev.work, DecodeForm::kWholeScaled, P, stream);
 }
 
+// Decode-update (k_ans_decode_update): every 16-bit archive multiplied by the member's float32 factor, added to
+// (accumulate == 1) or stored over (0) its 16-bit tensor of the same type, and rounded stochastically.  scale_dev and
+// seed_dev: device memory, read by the kernel -- never here -- so a captured call follows what they hold at each replay;
+// null: the host values.  No temp memory, no host synchronisation.
+int decodeUpdateImpl(
+    uint32_t ft, int P, int accumulate, uint32_t B, const void* const* in, const uint32_t* inBytes, void* const* out,
+    const uint32_t* outCapacity, float scale, const float* scale_dev, uint32_t scaleStride, uint64_t seed,
+    const uint64_t* seed_dev, uint32_t firstMember, uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+  DGPU_REQUIRE(ft == DGPU_FLOAT16 || ft == DGPU_BFLOAT16, "decode-update: floatType must be DGPU_FLOAT16 or DGPU_BFLOAT16");
+  DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "decode-update: accumulate must be 0 or 1");
+  DGPU_REQUIRE(scaleStride <= 1u, "decode-update: scaleStride must be 0 (one factor) or 1 (one per member)");
+  DGPU_REQUIRE(scale_dev != nullptr || (std::isfinite(scale) && scale != 0.0f), "decode-update: a host scale must be finite and not zero");
+  DGPU_REQUIRE((uintptr_t)scale_dev % 4u == 0u, "decode-update: scale_dev must be 4-byte aligned");
+  DGPU_REQUIRE((uintptr_t)seed_dev % 8u == 0u, "decode-update: seed_dev must be 8-byte aligned");
+  bool done;
+  int rc = checkCall(P, B, ft, /*tempUsed*/ nullptr, /*errBatch*/ nullptr, &done);
+  if (done) return rc;
+  DGPU_REQUIRE(in && inBytes && out && outCapacity, "decode-update: null array with numInBatch > 0");
+  Batch b;
+  rc = floatDecodeBatch(&b, ft, B, 1, in, inBytes, nullptr, ptrSide(out, 2, "decode-update: tensors must be 2-byte aligned"), outCapacity,
+                        "decode-update: outCapacity must not exceed 0xfffff000");
+  if (rc) return rc;
+  StreamLease streamLease(stream);
+  DeviceBatch dev;
+  LaunchGroup group;
+  rc = planFloatDecode(b, streamLease, &dev, &group);
+  if (rc) return rc;
+  DecodeArgs d = decodeArgs(b, dev, ft, outSuccess_dev, outSize_dev);
+  d.accumulate = (uint32_t)accumulate;
+  d.scale = scale;
+  d.scalePtr = scale_dev;
+  d.scaleStride = scaleStride;
+  d.seed = seed;
+  d.seedPtr = seed_dev;
+  d.firstMember = firstMember;
+  return launchDecode(d, group, dev.work, DecodeForm::kUpdate, P, stream);
+}
+
 // The norm outputs of a reduce call (either given: the call measures what it leaves) and the temp region their tile
 // partials are carved from.
 struct ReduceNorm {
@@ -2157,6 +2195,15 @@ int dgpu_float_decode_scaled(
   (void)tempBytes;
   return decodeScaledImpl(tempUsed, floatType, probBits, numInBatch, in, inBytes, out, outCapacity, scale, scale_dev, scaleStride,
                           outSuccess_dev, outSize_dev, (hipStream_t)stream);
+}
+
+// ---- decode-update (no upstream equivalent) ----------------------------------------
+int dgpu_float_decode_update(
+    uint32_t floatType, int probBits, int accumulate, uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
+    void* const* out, const uint32_t* outCapacity, float scale, const float* scale_dev, uint32_t scaleStride, uint64_t seed,
+    const uint64_t* seed_dev, uint32_t firstMember, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream) {
+  return decodeUpdateImpl(floatType, probBits, accumulate, numInBatch, in, inBytes, out, outCapacity, scale, scale_dev, scaleStride,
+                          seed, seed_dev, firstMember, outSuccess_dev, outSize_dev, (hipStream_t)stream);
 }
 
 // ---- the reduce family (no upstream equivalent) -------------------------------------

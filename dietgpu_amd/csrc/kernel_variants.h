@@ -184,6 +184,8 @@ constexpr uint32_t halvesOnly(uint32_t ft) { return ft == kFloat16 ? kFloat16 : 
 //     single-block batches run on 4-block tiles;
 //   * kAccumScaled: kAccum whose widened word is multiplied by the member's factor (as kWholeScaled takes it) before
 //     the store or the add; float types only, the LDS of kAccum;
+//   * kUpdate: kAccumScaled into 16-bit tensors of the archive's type, rounded stochastically (DecodeArgs::seedPtr /
+//     seed / firstMember); float16 and bfloat16 only, the LDS of kAccum;
 //   * kRanged: decodes a block range of every element (a range of one or two blocks takes the 4-block form).
 #define DGPU_DECODE_FORMS(X)                                                                                           \
   X(kAccum, k_ans_decode_accum, floatsOnly, decLdsBytes(P, T, TB))                                                     \
@@ -197,6 +199,7 @@ constexpr uint32_t halvesOnly(uint32_t ft) { return ft == kFloat16 ? kFloat16 : 
   X(kReduceNormStats, k_ans_decode_reduce_mixed_stats_norm, halvesOnly, decReduceNormLdsBytes(P, T, TB, true))         \
   X(kWholeScaled, k_ans_decode_scaled, floatsOnly, decScaledLdsBytes(P, T, TB))                                        \
   X(kAccumScaled, k_ans_decode_accum_scaled, floatsOnly, decLdsBytes(P, T, TB))                                        \
+  X(kUpdate, k_ans_decode_update, halvesOnly, decLdsBytes(P, T, TB))                                                   \
   X(kRanged, k_ans_decode_range, sameType, decLdsBytes(P, T, TB))
 
 // The decoder of tiles of `tileBlocks` blocks.  A form of the list above takes the 4-block instantiation for tiles of

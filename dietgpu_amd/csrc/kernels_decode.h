@@ -85,6 +85,11 @@ struct DecodeArgs {
   // scalePtr is null
   const float* scalePtr = nullptr;
   uint32_t scaleStride = 0;
+  // k_ans_decode_update only: the seed of the stochastic rounding is *seedPtr (device memory, 8-byte aligned, read when
+  // the kernel runs) or `seed` when seedPtr is null; member b draws the random bits of member firstMember + b
+  uint32_t firstMember = 0;
+  uint64_t seed = 0;
+  const uint64_t* seedPtr = nullptr;
 };
 __device__ __forceinline__ uint64_t decodeInBytes(const DecodeArgs& a, uint32_t b) {
   return a.inBytes ? (uint64_t)a.inBytes[b] : (a.uniformInBytes ? (uint64_t)a.uniformInBytes : ~0ull);
@@ -657,6 +662,83 @@ struct ScaledSink<kFloat32> : RowSink<kFloat32> {
 };
 
 // ---------------------------------------------------------------------------
+// Updating sinks (k_ans_decode_update; float16 / bfloat16): RowSink<FT> whose joined word is widened to float32,
+// multiplied by the member's factor, added to the widened word of the 16-bit TENSOR at the same place (accumulate == 1;
+// 0: the tensor is not read) -- ONE IEEE multiply and ONE IEEE add, written unfused as in AccumSink's kPreScaled -- and
+// rounded STOCHASTICALLY back to FT (castRoundStochastic) before it is stored where RowSink stores it.  The random bits
+// of word k of the member come from srBits(key, k >> 1): `key` is the member's (srMemberKey; wave-uniform, set by
+// decodeTile), kLane the index of the lane's word in row 0 of its block.  Staging and the shape of the stores are
+// RowSink's: the wide path leaves ONE 16-byte store per lane and group.  The tensor words a lane adds to are requested
+// where AccumSink requests its accumulator words -- with the non-compressed bytes, two groups ahead on the wide path --
+// as ONE 16-byte load per group (8 words of 2 bytes where AccumSink has 8 of 4), and not at all with accumulate == 0.
+typedef u32x4w u32x4w2 __attribute__((aligned(2)));  // tensors are word-aligned only
+struct UpdateGroupPre {  // one 8-row group of a lane: 8 non-compressed bytes and 8 tensor words
+  uint2 nc;
+  u32x4w t;
+};
+template <uint32_t FT>
+struct UpdateSink : RowSink<FT> {
+  static_assert(FT == kFloat16 || FT == kBFloat16, "");
+  float factor;
+  uint32_t accumulate;
+  uint32_t key;
+  uint32_t kLane;
+  __device__ __forceinline__ void init(uint8_t* outBase, const uint8_t* archive, uint32_t floatSize, size_t first, uint32_t hl) {
+    RowSink<FT>::init(outBase, archive, floatSize, first, hl);
+    kLane = (uint32_t)first + hl;
+  }
+  typedef AccumPre Pre;
+  typedef UpdateGroupPre GroupPre;
+  __device__ __forceinline__ AccumPre prefetch(uint32_t row) const {
+    AccumPre p(0);
+    p.r = this->nc[row * 32u];
+    if (accumulate) p.acc = this->out[row * 32u];
+    return p;
+  }
+  // w: the decoded word, t: the tensor word, both float32 bits -> the float32 bits that are rounded
+  __device__ __forceinline__ uint32_t value(uint32_t w, uint32_t t) const {
+    const float p = accMulUnfused(__builtin_bit_cast(float, w), factor);
+    return accumulate ? accAddUnfused(t, p) : __builtin_bit_cast(uint32_t, p);
+  }
+  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, const AccumPre& p) const {
+    const uint32_t h = RowSink<FT>::joinWord(e0, p.r) >> 16;
+    const uint32_t v = value(__builtin_bit_cast(uint32_t, accWiden16<FT>(h)), __builtin_bit_cast(uint32_t, accWiden16<FT>(p.acc)));
+    const uint32_t k = kLane + row * 32u;
+    const uint32_t bits = srBits(key, k >> 1);
+    const uint32_t r = (k & 1u) ? bits >> 16 : bits & 0xffffu;
+    streamStore<kNtDecStores>(&this->out[row * 32u], (uint16_t)castRoundStochastic<FT>(v, r));
+  }
+  __device__ __forceinline__ UpdateGroupPre prefetchGroup(uint32_t g, uint32_t hl) const {
+    UpdateGroupPre p;
+    p.nc = decLoad8(this->nc - hl + g * 256u + hl * 8u);
+    p.t = u32x4w{0u, 0u, 0u, 0u};
+    if (accumulate) p.t = *(const u32x4w2*)(this->out - hl + g * 256u + hl * 8u);
+    return p;
+  }
+  // two words of FT, the two tensor words under them and the 32 random bits of the pair -> two words of FT
+  __device__ __forceinline__ uint32_t updatePair(uint32_t w, uint32_t t, uint32_t bits) const {
+    if constexpr (FT == kBFloat16) {
+      const uint32_t v0 = value(w << 16, t << 16), v1 = value(w & 0xffff0000u, t & 0xffff0000u);
+      return __builtin_amdgcn_perm(castRoundStochasticHigh<kBFloat16>(v1, bits >> 16), castRoundStochasticHigh<kBFloat16>(v0, bits & 0xffffu),
+                                   0x07060302u);
+    } else {
+      const uint32_t v0 = value(__builtin_bit_cast(uint32_t, accWiden16<FT>(w & 0xffffu)), __builtin_bit_cast(uint32_t, accWiden16<FT>(t & 0xffffu)));
+      const uint32_t v1 = value(__builtin_bit_cast(uint32_t, accWiden16<FT>(w >> 16)), __builtin_bit_cast(uint32_t, accWiden16<FT>(t >> 16)));
+      return __builtin_amdgcn_perm(castRoundStochastic<FT>(v1, bits >> 16), castRoundStochastic<FT>(v0, bits & 0xffffu), 0x05040100u);
+    }
+  }
+  __device__ __forceinline__ void flushGroup(uint32_t xpose, uint32_t g, uint32_t hl, const UpdateGroupPre& p) const {
+    u32x4w o = RowSink<FT>::joinGroup(xpose, hl, p.nc);
+    const uint32_t pair0 = (kLane - hl + g * 256u + hl * 8u) >> 1;  // the lane's 8 words begin at a multiple of 8
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) o[k] = updatePair(o[k], p.t[k], srBits(key, pair0 + k));
+    u32x4w2* dst = (u32x4w2*)(this->out - hl + g * 256u + hl * 8u);
+    if (kNtDecStores) __builtin_nontemporal_store(o, dst);
+    else *dst = o;
+  }
+};
+
+// ---------------------------------------------------------------------------
 // Compressed-word ring: 4 chunks of 256 words (512 bytes) per block.  Chunk k of
 // the block's data lives in slot k & 3.  Words are consumed from the top of the
 // block downwards, at most 32 per row = 256 per 8-row group = one chunk per
@@ -967,7 +1049,7 @@ __device__ __forceinline__ void decodeBlock(
 
 // One workgroup of the tiled decoder: 32 threads per block of the tile (512 or 128), LDS = word rings + 64-bit LUT.
 // The body of k_ans_decode (DecodeForm::kWhole), k_ans_decode_range (kRanged), k_ans_decode_accum (kAccum) and
-// k_ans_decode_scaled (kWholeScaled) and k_ans_decode_accum_scaled (kAccumScaled), below.
+// k_ans_decode_scaled (kWholeScaled), k_ans_decode_accum_scaled (kAccumScaled) and k_ans_decode_update (kUpdate), below.
 //
 // kRanged: blocks [firstBlock[b], firstBlock[b] + numBlocks[b]) of element b, clipped to the element's end, and block
 // firstBlock + k goes to out + k * 4096 words: the output buffer holds the range, not the element.
@@ -1000,18 +1082,27 @@ __device__ __forceinline__ void decodeBlock(
 // kAccumScaled: kAccum whose widened word is multiplied by the member's float32 factor before it is stored or added:
 // acc = [acc +] fl32(widened * factor), one multiply and one add, never fused (AccumSink, kPreScaled).  The factor is
 // fetched as kWholeScaled fetches it; everything else is kAccum's, the descriptor checks of every tile included.
+//
+// kUpdate: the factor of kAccumScaled, the 16-bit output of kWholeScaled: out = sround_FT([widen(out) +] fl32(widened *
+// factor)) (UpdateSink; float16 and bfloat16 only).  Checks, success and outSize are kAccum's, the descriptor checks of
+// every tile included: a failing member keeps every bit of its tensor.  The seed (DecodeArgs::seedPtr, or the host's
+// DecodeArgs::seed) is requested with the factor, in the round trip of the header; the member's key follows from it in
+// scalar registers, once per tile.
 // (kReduce: decodeReduceTile, below)
-enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats, kReduceNorm, kReduceNormStats, kWholeScaled, kAccumScaled };
+enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats, kReduceNorm, kReduceNormStats, kWholeScaled, kAccumScaled, kUpdate };
 template <int P, uint32_t FT, uint32_t kTileBlocks, DecodeForm kForm>
 __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccumScaled = kForm == DecodeForm::kAccumScaled;
-  constexpr bool kAccum = kForm == DecodeForm::kAccum || kAccumScaled;                 // the accumulating forms
-  constexpr bool kScaledForm = kForm == DecodeForm::kWholeScaled || kAccumScaled;       // the forms with a factor
+  constexpr bool kUpdate = kForm == DecodeForm::kUpdate;
+  constexpr bool kAccum = kForm == DecodeForm::kAccum || kAccumScaled || kUpdate;      // the accumulating forms
+  constexpr bool kScaledForm = kForm == DecodeForm::kWholeScaled || kAccumScaled || kUpdate;  // the forms with a factor
   static_assert(kForm == DecodeForm::kWhole || kForm == DecodeForm::kRanged || kAccum || kScaledForm,
                 "decode-reduce has a body of its own: decodeReduceTile");
   static_assert(!(kAccum || kScaledForm) || FT != 0u, "accumulating and scaled decode: float archives only");
-  using Sink = std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32, 0u, false, false, kAccumScaled>,
-                                  std::conditional_t<kScaledForm, ScaledSink<FT ? FT : kFloat32>, RowSink<FT>>>;
+  static_assert(!kUpdate || FT == kFloat16 || FT == kBFloat16, "decode-update: 16-bit float archives only");
+  using Sink = std::conditional_t<kUpdate, UpdateSink<kUpdate ? FT : kBFloat16>,
+                                  std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32, 0u, false, false, kAccumScaled>,
+                                                     std::conditional_t<kScaledForm, ScaledSink<FT ? FT : kFloat32>, RowSink<FT>>>>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks);
   // the LUT-build scratch (cdf, pdf: 2 KiB, read while the LUT is stored) sits in the ring area
   static_assert(kTileBlocks * kRingBytes >= 2048u, "");
@@ -1098,6 +1189,8 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   const AnsHeader header = *(const AnsHeader*)ans;
   float factor = 1.0f;  // kScaledForm: the member's factor, in the round trip of the header
   if constexpr (kScaledForm) factor = a.scalePtr ? a.scalePtr[(size_t)b * a.scaleStride] : a.scale;
+  uint64_t seed = 0;    // kUpdate: the call's seed, in the same round trip
+  if constexpr (kUpdate) seed = a.seedPtr ? *a.seedPtr : a.seed;
   uint2 pdfRaw = make_uint2(0u, 0u);
   if (wave == 0) pdfRaw = *(const uint2*)(pdfEarly ? ans + sizeof(AnsHeader) + 8u * lane : ans);  // pdf[4 lane .. 4 lane + 3]
   uint2 bwMine = *(const uint2*)(blockEarly ? ans + ansBlockWordsOffset(nbSpec) + 8u * block : ans);
@@ -1185,6 +1278,7 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   if constexpr (kAccum) sink.accumulate = a.accumulate;
   if constexpr (kAccumScaled) sink.preFactor = factor;
   else if constexpr (kScaledForm) sink.factor = factor;
+  if constexpr (kUpdate) sink.key = srMemberKey(seed, a.firstMember + b);
   // (a half without a block points at its wave's first block: its prefetches must stay inside the archive -- kAccum:
   // and inside the accumulator)
   uint32_t sinkBlock = haveBlock ? block : (block & ~1u);
@@ -1968,6 +2062,14 @@ template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_accum_scaled(DecodeArgs a) {
   static_assert(FT != 0u, "accumulating decode: float archives only");
   decodeTile<P, FT, kTileBlocks, DecodeForm::kAccumScaled>(a);
+}
+
+// Updating form: k_ans_decode_accum_scaled whose outputs are 16-bit tensors of the archive's type, rounded stochastically
+// (DecodeArgs::seedPtr / seed / firstMember).  Grid, order and LDS as k_ans_decode_accum.  float16 and bfloat16 only.
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_update(DecodeArgs a) {
+  static_assert(FT == kFloat16 || FT == kBFloat16, "decode-update: 16-bit float archives only");
+  decodeTile<P, FT, kTileBlocks, DecodeForm::kUpdate>(a);
 }
 
 // Reducing form: grid and order as k_ans_decode_accum, DecodeArgs::numSources archives per accumulator (decodeReduceTile).

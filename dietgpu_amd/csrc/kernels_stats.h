@@ -497,6 +497,52 @@ __device__ __forceinline__ uint32_t castRound(uint32_t x) {
   }
 }
 
+// float32 -> 16-bit float, STOCHASTIC rounding, for the decode-update (k_ans_decode_update): the only place the rule is
+// written (include/dietgpu_amd.h states it; tests/sr_ref.py restates it from there).  `x` are the float32 bits, `r16` a
+// 16-bit random number: the result is x truncated toward zero to AT, or the next word away from zero with probability
+// remainder / unit -- exact to 2^-16 (bfloat16: the 16 dropped bits meet 16 random ones) or 2^-13 (float16: the 13
+// dropped bits meet the top 13).  A word AT represents has no remainder and never moves; an infinity stays one; a finite
+// value beyond AT's largest may carry into infinity; r16 == 0 truncates.  NaN: the canonical quiet NaN, sign kept.
+//   * bfloat16: (x + r16) >> 16 on the bits (the carry walks into the exponent as in castRoundHigh).
+//   * float16: u = |x| in units of 2^-13 of a float16 last place -- the bits re-biased for a float16 normal, the
+//     significand shifted down (floor) for a float16 denormal -- then (u + (r16 >> 3)) >> 13, capped at infinity.
+// The random bits are a pure function of (seed, member, word index): srMemberKey is wave-uniform, srBits(key, k >> 1)
+// serves words k (low half) and k + 1 (high half, k even), so a lane's 8 consecutive words take four mixes.
+__device__ __forceinline__ uint32_t srMix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+__device__ __forceinline__ uint32_t srMemberKey(uint64_t seed, uint32_t member) {
+  const uint32_t base = srMix32(srMix32((uint32_t)seed + 0x9E3779B9u) ^ (uint32_t)(seed >> 32));
+  return srMix32(base + member * 0x85EBCA6Bu);
+}
+__device__ __forceinline__ uint32_t srBits(uint32_t key, uint32_t pairIndex) { return srMix32(key ^ pairIndex); }
+// (bfloat16 only: the result in the HIGH half, as castRoundHigh)
+template <uint32_t AT>
+__device__ __forceinline__ uint32_t castRoundStochasticHigh(uint32_t x, uint32_t r16) {
+  static_assert(AT == kBFloat16, "");
+  const bool nan = (x & 0x7fffffffu) > 0x7f800000u;
+  return nan ? ((x & 0x80000000u) | 0x7fc00000u) : x + r16;
+}
+template <uint32_t AT>
+__device__ __forceinline__ uint32_t castRoundStochastic(uint32_t x, uint32_t r16) {
+  if (AT == kBFloat16) {
+    return castRoundStochasticHigh<kBFloat16>(x, r16) >> 16;
+  } else {
+    const uint32_t a = x & 0x7fffffffu, sign = (x >> 16) & 0x8000u;
+    const uint32_t e = a >> 23;
+    const uint32_t m = (a & 0x7fffffu) | (e ? 0x800000u : 0u);
+    const uint32_t down = 113u - (e > 1u ? e : 1u);  // (only looked at for e < 113; m < 2^24: a shift of 31 leaves 0)
+    const uint32_t u = a >= 0x38800000u ? a - 0x38000000u : m >> (down < 31u ? down : 31u);
+    const uint32_t h = (u + (r16 >> 3)) >> 13;
+    return a > 0x7f800000u ? (sign | 0x7e00u) : (sign | (h < 0x7c00u ? h : 0x7c00u));
+  }
+}
+
 // Histogram kernel: 16-byte loads with a byte-wise head/tail so any start
 // alignment works (the reference test uses stride size+11,
 // ANSStatisticsTest.cu:52-57).  grid = (xBlocks, B), 256 threads.

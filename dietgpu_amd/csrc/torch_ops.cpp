@@ -594,6 +594,43 @@ int64_t decompress_data_scaled(
   return (int64_t)used;
 }
 
+// Decode-update (no reference op): archive i multiplied by a float32 factor, added to (accumulate) or stored over the
+// 16-bit tensor ts_out[i] of the archive's type and rounded stochastically (dgpu_float_decode_update).  scale_dev as in
+// decompress_data_scaled.  seed: the 64 seed bits as an int64; seed_dev: a 1-element int64 tensor on the tensors' GPU
+// whose bits are the seed -- the kernel reads it, nothing here does.  -> 0 (the call uses no temp memory).
+int64_t decompress_data_update(
+    const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tOuts, double scale, const std::optional<at::Tensor>& scaleDev,
+    int64_t seed, const std::optional<at::Tensor>& seedDev, int64_t firstMember, bool accumulate,
+    const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.size() == tOuts.size());
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(firstMember >= 0 && firstMember <= (int64_t)std::numeric_limits<uint32_t>::max(), "dietgpu: first_member must be in [0, 2^32)");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  const size_t n = tIns.size();
+  DecodeTensors m = marshalDecode(true, tIns, tOuts, dev, [&](size_t i) {
+    TORCH_CHECK(tOuts[i].scalar_type() == tOuts[0].scalar_type(), "dietgpu: outputs must share one float dtype");
+  });
+  TORCH_CHECK(tOuts[0].scalar_type() == at::ScalarType::Half || tOuts[0].scalar_type() == at::ScalarType::BFloat16,
+              "dietgpu: decode-update takes float16 or bfloat16 tensors");
+  uint32_t stride = 0;
+  const float* factors = scaleFactors(scaleDev, n, dev, &stride);
+  const uint64_t* seedPtr = nullptr;
+  if (seedDev) {
+    const at::Tensor& s = *seedDev;
+    TORCH_CHECK(s.device().is_cuda() && s.get_device() == dev && s.is_contiguous() && s.scalar_type() == at::ScalarType::Long && s.numel() == 1,
+                "dietgpu: a tensor seed must be a 1-element int64 tensor on the tensors' GPU");
+    seedPtr = (const uint64_t*)s.data_ptr();
+  }
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  check(dgpu_float_decode_update(floatTypeFromDtype(tOuts[0].scalar_type()), precision(), accumulate ? 1 : 0, (uint32_t)n, m.inPtrs.data(),
+                                 m.inBytes.data(), m.outPtrs.data(), m.outCapacity.data(), (float)scale, factors, stride, (uint64_t)seed,
+                                 seedPtr, (uint32_t)firstMember, ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
+        "floatDecompressUpdate", true);
+  return 0;
+}
+
 // Cast-compress (no reference op): float32 tensor i rounded to float_type (1 = float16, 2 = bfloat16) in registers and
 // compressed into an ordinary archive of that type (dgpu_float_cast_compress).  Output conventions of compress_data.
 std::tuple<at::Tensor, at::Tensor, int64_t> compress_data_cast(
@@ -981,6 +1018,9 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "decompress_data_scaled(Tensor[] ts_in, Tensor[] ts_out, float scale, Tensor? scale_dev=None, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_decompressed_words=None) -> int",
       &dietgpu_amd::decompress_data_scaled);
+  m.def(
+      "decompress_data_update(Tensor[] ts_in, Tensor[] ts_out, float scale, Tensor? scale_dev, int seed, Tensor? seed_dev, int first_member, bool accumulate, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
+      &dietgpu_amd::decompress_data_update);
   m.def(
       "decompress_data_reduce(Tensor[] ts_in, int num_sources, Tensor[] ts_acc, int float_type, bool accumulate=False, Tensor? temp_mem=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
       &dietgpu_amd::decompress_data_reduce);

@@ -186,6 +186,17 @@ class GpuFloatCodec:
         ops.decompress_data_accumulate(rows, accs, accumulate, self.temp_mem, status, None, dtype=self.dtype, scale=scale)
         return status
 
+    def decompress_update(self, rows, outs, accumulate, scale=None, seed=0, first_member=0):
+        """rows multiplied by `scale`, added to (accumulate) or stored over the 16-bit tensors `outs` of the rows' dtype
+        and rounded stochastically, in the decode kernel (ops.decompress_data_update) -> status.  `seed`: an int in
+        [0, 2^64) or a 1-element int64 tensor on the device, never read by the host; row i draws the random bits of member
+        first_member + i"""
+        from . import ops
+
+        status = torch.zeros((len(rows),), dtype=torch.uint8, device=outs[0].device)
+        ops.decompress_data_update(rows, outs, seed, scale, accumulate, first_member, status, None)
+        return status
+
     def _reduce(self, name, mixed, rows_per_acc, accs, accumulate, scale, norm):
         """The reduce call `name` of ops -> (status, what it returned).  The call's float type: with `mixed`, what a raw
         row says it is; without one, what the last compress call held."""
@@ -286,10 +297,29 @@ def _decode_into_float32(codec, rows, accs, factor, accumulate, dtype):
     return status
 
 
+def _decode_update(codec, rows, outs, factor, accumulate, seed, first_member):
+    """The rows (archives of the outs' 16-bit dtype) applied to `outs` with stochastic rounding: out = sround([widen(out)
+    +] fl32(widen(word) * factor)), row i with the random bits of member first_member + i (dgpu_float_decode_update;
+    factor None: 1, which multiplies) -> status.  A codec with `decompress_update` does it in ONE call (GpuFloatCodec: in
+    the decode kernel); any other codec decodes into a float32 scratch (_decode_into_float32), which takes the add of the
+    widened tensor and the rounding from torch (rounding.update_).  The same bits either way."""
+    method = getattr(codec, "decompress_update", None)
+    if callable(method):
+        return method(rows, outs, accumulate, scale=factor, seed=seed, first_member=first_member)
+    from . import rounding
+
+    one = torch.ones((), dtype=torch.float32, device=outs[0].device)
+    wide = [torch.empty(o.shape, dtype=torch.float32, device=o.device) for o in outs]
+    status = _decode_into_float32(codec, rows, wide, one if factor is None else factor, False, outs[0].dtype)
+    for i, (o, w) in enumerate(zip(outs, wide)):
+        rounding.update_(o, w, seed, first_member + i, accumulate)
+    return status
+
+
 def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec, scale=None, decode=None):
     """The exchange of compressed_all_gather for rows that are compressed already: `comp` [n, cap] / `sizes` [n] as a
     codec's compress returns them; `outs_of(r)` -> the n tensors rank r's rows are decompressed into.  `scale`: see
-    compressed_all_gather.  `decode(rows, outs)` -> status: what decodes a rank's rows instead of the codec's
+    compressed_all_gather.  `decode(r, rows, outs)` -> status: what decodes source rank r's rows instead of the codec's
     `decompress` (compressed_all_reduce's `out`)."""
     world = dist.get_world_size()
     n = comp.shape[0]
@@ -311,7 +341,7 @@ def _all_gather_archives(comp, sizes, outs_of, raw_bytes, codec, scale=None, dec
     for r in range(world):
         rows = [gathered_payload[r][i, : int(all_sizes[r, i])] for i in range(n)]
         outs = outs_of(r)
-        status = decode(rows, outs) if decode is not None else _scaled_decompress(codec, rows, outs, scale)
+        status = decode(r, rows, outs) if decode is not None else _scaled_decompress(codec, rows, outs, scale)
         if not bool(status.all().item()):
             raise RuntimeError(f"decompression of rank {r}'s rows failed")
         gathered.append(outs)
@@ -573,7 +603,7 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
 
 
 def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False, clip_norm=None, wire_dtype=None,
-                          residual=None, residual_fresh=False, out=None, out_scale=None, out_accumulate=False):
+                          residual=None, residual_fresh=False, out=None, out_scale=None, out_accumulate=False, out_seed=None):
     """All-reduce (sum) of a flat fp16 / bf16 tensor, moving compressed bytes both ways and summing in float32.
 
     Three steps: `compressed_reduce_scatter` (this rank's float32 shard of the sum), the codec's `compress_cast` of that
@@ -635,7 +665,19 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
     every read of `tensor` precedes the gather -- and is an error with it; `out` must not overlap `tensor` otherwise.
     out_scale or out_accumulate without out is an error.  The statistics keep their meaning: "sumsq", "nonfinite" and
     "global_*" describe the 16-bit words of the archives, unclipped and without out_scale, as without `out`.  With
-    out=None the call is what it was."""
+    out=None the call is what it was.
+
+    out_seed (an int in [0, 2^64), or a 1-element int64 tensor on the device, never read by the host): `out` is a flat
+    contiguous tensor of the wire's 16-BIT dtype -- parameters without a float32 master copy -- and the final gather
+    decodes source rank r's shard into out.view(world, -1)[r] as out[k] = sround([widen(out[k]) +] fl32(widen(word_k) *
+    f)): one float32 multiply, one float32 add (out_accumulate=True), and the STOCHASTIC rounding of
+    dgpu_float_decode_update with the random bits of member r and word index k within the shard.  f is as above (1
+    without clip_norm and out_scale); out_scale = -lr with out_accumulate is the SGD step.  THE SEED MUST BE THE SAME ON
+    EVERY RANK: the random bits are a pure function of (seed, source rank, word index), so equal seeds give every rank
+    the same parameter bits, and different seeds let the replicas drift apart.  A codec with `decompress_update` makes one
+    call per source rank (GpuFloatCodec: in the decode kernel); any other codec is decoded into a float32 scratch and
+    takes the add and the rounding from torch (dietgpu_amd.rounding), with the same bits.  out_seed with a float32 `out`
+    is an error, and so is a 16-bit `out` without out_seed; `out is tensor` follows the rules above."""
     codec = codec or GpuFloatCodec()
     _check_wire("compressed_all_reduce", tensor, codec, raw_local, wire_dtype, residual)
     out_dtype = wire_dtype if wire_dtype is not None else tensor.dtype
@@ -644,9 +686,24 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
     if out is None:
         if out_scale is not None or out_accumulate:
             raise RuntimeError("compressed_all_reduce: out_scale and out_accumulate need `out`")
+        if out_seed is not None:
+            raise RuntimeError("compressed_all_reduce: out_seed needs `out`")
     else:
-        if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.dim() == 1 and out.is_contiguous()
-                and out.numel() == tensor.numel() and out.device == tensor.device):
+        if isinstance(out, torch.Tensor) and out.dtype in _WIRE_DTYPES and out_seed is None:
+            raise RuntimeError("compressed_all_reduce: out must be a flat contiguous float32 tensor of the tensor's length on its device "
+                               "(a 16-bit out is rounded stochastically and needs out_seed)")
+        if out_seed is not None:
+            if not (isinstance(out, torch.Tensor) and out.dtype == out_dtype and out.dim() == 1 and out.is_contiguous()
+                    and out.numel() == tensor.numel() and out.device == tensor.device):
+                raise RuntimeError("compressed_all_reduce: with out_seed, out must be a flat contiguous tensor of the wire's 16-bit dtype, "
+                                   "of the tensor's length on its device")
+            if isinstance(out_seed, torch.Tensor):
+                if not (out_seed.dtype == torch.int64 and out_seed.numel() == 1 and out_seed.device == tensor.device):
+                    raise RuntimeError("compressed_all_reduce: a tensor out_seed must be a 1-element int64 tensor on the tensor's device")
+            elif not (isinstance(out_seed, int) and not isinstance(out_seed, bool) and 0 <= out_seed < (1 << 64)):
+                raise RuntimeError("compressed_all_reduce: out_seed must be an int in [0, 2^64) or a 1-element int64 tensor")
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.dim() == 1 and out.is_contiguous()
+                  and out.numel() == tensor.numel() and out.device == tensor.device):
             raise RuntimeError("compressed_all_reduce: out must be a flat contiguous float32 tensor of the tensor's length on its device")
         if out is tensor and out_accumulate:
             raise RuntimeError("compressed_all_reduce: out is the tensor itself: out_accumulate is not possible")
@@ -705,8 +762,11 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
         def all_gather(coef):
             # the factor of the float32 decode: coef, out_scale, or their float32 product (0-dim tensors: nothing is read)
             f = out_scale if coef is None else (coef if out_scale is None else coef * out_scale)
+            if out_seed is not None:
+                return _all_gather_archives(comp, sizes, lambda r: [rows[r]], gathered_bytes, codec,
+                                            decode=lambda r, rws, outs: _decode_update(codec, rws, outs, f, out_accumulate, out_seed, r))
             return _all_gather_archives(comp, sizes, lambda r: [rows[r]], gathered_bytes, codec,
-                                        decode=lambda rws, accs: _decode_into_float32(codec, rws, accs, f, out_accumulate, out_dtype))
+                                        decode=lambda r, rws, accs: _decode_into_float32(codec, rws, accs, f, out_accumulate, out_dtype))
     if clip_norm is not None:
         # the statistics first: the coefficient is known before the gather, whose decode applies it
         if not pair[2]:  # (the words of the archive: the shard rounded as the cast rounds it)

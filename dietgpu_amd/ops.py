@@ -770,6 +770,62 @@ def decompress_data_scaled(ts_in, ts_out, scale, temp_mem=None, out_status=None,
     return int(used.value)
 
 
+# ------------------------------------------------------------------ decode-update
+# (no reference op: dgpu_float_decode_update, include/dietgpu_amd.h)
+def _seed_arg(seed):
+    """The `seed` of decode-update -> (the 64 seed bits as a signed int, device tensor or None).  An int in [0, 2^64), or a
+    1-element int64 CUDA tensor whose bits are the seed and which is not read."""
+    if isinstance(seed, torch.Tensor):
+        _check(seed.dtype == torch.int64 and seed.numel() == 1, "a tensor seed must be a 1-element int64 tensor")
+        _check(seed.is_cuda and seed.is_contiguous(), "a tensor seed must be a contiguous tensor on the tensors' GPU")
+        return 0, seed
+    _check(isinstance(seed, int) and not isinstance(seed, bool), "seed must be an int or a 1-element int64 tensor")
+    _check(0 <= seed < (1 << 64), "seed must be in [0, 2^64)")
+    return (seed - (1 << 64) if seed >= (1 << 63) else seed), None
+
+
+def decompress_data_update(ts_in, ts_out, seed, scale=None, accumulate=True, first_member=0, out_status=None, out_sizes=None,
+                           prob_bits=K_DEFAULT_PRECISION):
+    """Decodes 16-bit float archive ts_in[i], multiplies every word by a float32 factor, adds it to the 16-bit tensor
+    ts_out[i] of the archive's type (accumulate=True) or stores it there (False: the tensor is not read), and rounds the
+    result STOCHASTICALLY to that type: ts_out[i][k] = sround_T([widen(ts_out[i][k]) +] fl32(widen(word) * s)) -- one
+    IEEE float32 multiply and one IEEE add, never an FMA; the result is the neighbour of the sum toward zero or the next
+    one away from zero, the latter with probability remainder / unit (`dietgpu_amd.rounding` restates the rule in torch)
+    -> 0 (no temp memory is used).  With s = -lr * coef it is the SGD update of bfloat16 parameters without a float32
+    master copy.  ts_out: float16 or bfloat16 CUDA tensors of one dtype that do not overlap.
+
+    The random bits are a pure function of (seed, first_member + i, k): the same archives with the same seed give the
+    same bits on every replica.  `seed`: an int in [0, 2^64), or a 1-element int64 CUDA tensor whose bits are the seed,
+    read by the kernel when it runs -- a captured call advances the rounding by `seed.add_(1)`.  `scale`: as in
+    decompress_data_scaled; None is 1.0.  out_status[i] is 0, and ts_out[i] keeps every bit, for an archive of another
+    type, a malformed or truncated one, or one that does not fit; out_sizes[i] is the size its header states."""
+    _check(len(ts_in) > 0)
+    _check(len(ts_in) == len(ts_out))
+    n = len(ts_in)
+    host, dev_scale = _scale_arg(scale, n)
+    if host is None:
+        host = 1.0
+    host_seed, dev_seed = _seed_arg(seed)
+    _check(isinstance(first_member, int) and 0 <= first_member < (1 << 32), "first_member must be an int in [0, 2^32)")
+    _check(ts_in[0].is_cuda, "tensors must be on the GPU")
+    dev = ts_in[0].get_device()
+    _check(dev_scale is None or dev_scale.get_device() == dev, "a tensor scale must be on the tensors' GPU")
+    _check(dev_seed is None or dev_seed.get_device() == dev, "a tensor seed must be on the tensors' GPU")
+    _check(ts_out[0].dtype in (torch.float16, torch.bfloat16), "decode-update takes float16 or bfloat16 tensors")
+    op = _amd_op(prob_bits, "decompress_data_update")
+    if op is not None:
+        # (the op makes the per-tensor checks below itself, and raises RuntimeError like them)
+        return op(ts_in, ts_out, host, dev_scale, host_seed, dev_seed, first_member, bool(accumulate), out_status, out_sizes)
+    caps = _decode_capacities(True, ts_in, ts_out, dev, same_dtype=True)
+    _validate_status(out_status, out_sizes, n, dev)
+    with torch.cuda.device(dev):
+        check(lib().dgpu_float_decode_update(
+            _float_type(ts_out[0]), prob_bits, int(bool(accumulate)), n, _ptr_array(ts_in), _in_bytes(ts_in), _ptr_array(ts_out),
+            _u32_array(caps), host, _ptr(dev_scale), 0 if dev_scale is None or dev_scale.numel() == 1 else 1,
+            host_seed & ((1 << 64) - 1), _ptr(dev_seed), first_member, _ptr(out_status), _ptr(out_sizes), _stream()))
+    return 0
+
+
 # ------------------------------------------------------------------ decode-reduce
 # (no reference op: dgpu_float_decode_reduce, include/dietgpu_amd.h)
 MAX_REDUCE_SOURCES = 64

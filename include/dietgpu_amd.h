@@ -73,7 +73,7 @@ const char* dgpu_version(void);
  * dgpu_float_reduce_compress_mixed, dgpu_float_decode_reduce_scaled, dgpu_float_reduce_compress_scaled,
  * dgpu_float_reduce_norm_temp_bytes, dgpu_float_decode_reduce_norm, dgpu_float_reduce_compress_norm and
  * dgpu_float_decode_scaled were added at version 8, dgpu_float_feedback_compress and
- * dgpu_float_decode_accumulate_scaled after them). */
+ * dgpu_float_decode_accumulate_scaled after them, dgpu_float_decode_update after those). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -381,6 +381,62 @@ int dgpu_float_decode_scaled(
     uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
     void* const* out, const uint32_t* outCapacity /* float words */,
     float scale, const float* scale_dev /* nullable: the host float is used */, uint32_t scaleStride /* 0 or 1 */,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
+
+/* ---- decode-update (no upstream equivalent) -------------------------------------------
+ * Decodes 16-bit float archives, multiplies every word by a float32 factor, adds it to a 16-bit tensor OF THE ARCHIVE'S
+ * TYPE and rounds the sum STOCHASTICALLY back to that type: with s = -lr * coef the SGD update of bfloat16 / float16
+ * parameters that have no float32 master copy, straight from the final all-gather of a compressed all-reduce.  One
+ * kernel: 2 bytes read and 2 written per word beside the archive.
+ *   For decoded word w_k (index k within member i), factor s_i and tensor word t_k = out[i][k]:
+ *   1. p = fl32(widen(w_k) * s_i).  Widening is exact; ONE IEEE float32 multiply, as in
+ *      dgpu_float_decode_accumulate_scaled.
+ *   2. v = accumulate ? fl32(widen(t_k) + p) : p.  ONE IEEE float32 add, never fused with the multiply.  With
+ *      accumulate == 0 the tensor is not read.
+ *   3. out[i][k] = sround_T(bits(v), r16(S, firstMember + i, k)), with S = seed_dev ? *seed_dev : seed.
+ *   - sround_T(x, r) works on the float32 bits x with a 16-bit number r.  Let a = x & 0x7fffffff and
+ *     sign = (x >> 16) & 0x8000.  A NaN (a > 0x7f800000) becomes the canonical quiet NaN of T (sign | 0x7fc0 for
+ *     bfloat16, sign | 0x7e00 for float16); the sign of a NaN that the arithmetic produced is unspecified.
+ *     bfloat16: (x + r) >> 16.
+ *     float16: u = a - 0x38000000 when a >= 0x38800000; otherwise u = floor(|v| * 2^37), that is m >> (113 - max(e, 1))
+ *     with e = a >> 23, m = (a & 0x7fffff) | (e ? 0x800000 : 0), and 0 once the shift reaches 32.
+ *     h = min((u + (r >> 3)) >> 13, 0x7c00); the result is sign | h.
+ *   - So: the result is the neighbour of v toward zero or the next one away from zero, "away" with probability
+ *     remainder / unit -- exact to 2^-16 for bfloat16 and to 2^-13 for float16; for float16-denormal results the
+ *     truncation of u adds less than 2^-13 of a unit.  A value that T represents never moves; infinities stay
+ *     infinities; a finite v beyond T's largest value can round to infinity; r = 0 is truncation.
+ *   - r16(S, j, k), with mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (mod 2^32):
+ *     base = mix32(mix32(lo32(S) + 0x9E3779B9) ^ hi32(S));  key_j = mix32(base + j * 0x85EBCA6B);
+ *     bits = mix32(key_j ^ (k >> 1));  r16 = the low half of bits for even k, the high half for odd k.
+ *     The random bits are a pure function of (seed, member, word index): every replica that decodes the same archives
+ *     with the same seed holds the same parameter bits, whatever the kernel geometry, the dispatch order, the
+ *     dgpu_debug_set_* knobs or the alignment of out[i]; firstMember lets a batch split over several calls draw the
+ *     bits of the whole batch.
+ *   - The factor is dgpu_float_decode_scaled's: scale_dev != NULL points at DEVICE memory, 4-byte aligned, of 1 float
+ *     (scaleStride == 0) or numInBatch floats (scaleStride == 1), read when the kernel runs and never by the host; it
+ *     may hold ANY value.  scale_dev == NULL: the host float `scale`, which must be finite and not zero.
+ *   - seed_dev != NULL points at DEVICE memory, 8-byte aligned, of one uint64_t that the kernel reads when it runs: a
+ *     captured call advances the rounding by advancing that word.  seed_dev == NULL: the host `seed`.
+ *   - Every archive check of dgpu_float_decode_scaled applies; outSuccess_dev[i] and outSize_dev[i] behave as there.  A
+ *     member that fails (outSuccess_dev[i] = 0: another float type, a malformed or truncated archive, one that does not
+ *     fit) keeps EVERY bit of its tensor and does not disturb the others.  Words behind the element stay untouched and
+ *     no byte outside [out[i], out[i] + size) is written: tensors laid side by side in one buffer, with odd sizes, are
+ *     a legal call.  out[i] is 2-byte aligned; the tensors of one call must not overlap each other or the archives.
+ *   - floatType (of the archives AND of the tensors) must be DGPU_FLOAT16 or DGPU_BFLOAT16 -- DGPU_FLOAT32 is rejected --
+ *     probBits 9, 10 or 11, accumulate 0 or 1, scaleStride 0 or 1, scale_dev 4-byte aligned, seed_dev 8-byte aligned, a
+ *     host scale finite and not zero, no array null when numInBatch > 0, in[i] 16-byte aligned, out[i] 2-byte aligned,
+ *     outCapacity[i] <= 0xfffff000: DGPU_ERR_INVALID_ARGUMENT with a dgpu_last_error() text otherwise, before anything
+ *     is enqueued.  An empty batch returns 0.  There is no checksum (one in the archive is ignored).
+ *   - One kernel geometry per call, from its largest capacity (single-block members run on the 4-block tiles).
+ *   - No temp memory is used -- the call has no temp-memory parameters -- and nothing synchronises: capturable into a
+ *     HIP graph under the same conditions as the other pointer-array decode calls (the arrays resident from an earlier
+ *     identical call). */
+int dgpu_float_decode_update(
+    uint32_t floatType /* of the archives AND of the tensors: DGPU_FLOAT16 or DGPU_BFLOAT16 */, int probBits,
+    int accumulate, uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
+    void* const* out /* 16-bit words of floatType */, const uint32_t* outCapacity /* words */,
+    float scale, const float* scale_dev /* nullable */, uint32_t scaleStride /* 0 or 1 */,
+    uint64_t seed, const uint64_t* seed_dev /* nullable */, uint32_t firstMember,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
 
 /* ---- decode-reduce (no upstream equivalent) ------------------------------------------
