@@ -15,6 +15,7 @@ from .ops import (  # noqa: F401
     compress_data_rolling,
     compress_data_simple,
     compress_data_split_size,
+    compress_data_stochastic,
     block_cover,
     decompress_data,
     decompress_data_accumulate,

@@ -47,6 +47,7 @@ _SIGS = {
     "dgpu_float_decode_reduce": (i32, [vp, sz, vp, u32, i32, i32, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
     "dgpu_float_cast_compress": (i32, [vp, sz, vp, u32, i32, u32, vp, vp, vp, vp, vp]),
     "dgpu_float_feedback_compress": (i32, [vp, sz, vp, u32, i32, u32, vp, vp, vp, vp, vp, vp, vp]),
+    "dgpu_float_stochastic_compress": (i32, [u32, i32, u32, vp, vp, C.c_uint64, vp, u32, vp, vp, vp]),
     "dgpu_float_rolling_compress": (i32, [vp, sz, vp, u32, u32, i32, u32, vp, vp, vp, vp, vp, vp, vp]),
     "dgpu_float_reduce_compress_temp_bytes": (sz, [u32, u32, u32]),
     "dgpu_float_reduce_compress": (i32, [vp, sz, vp, u32, i32, i32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1066,6 +1066,13 @@ struct RollingCounts {
   const uint32_t* countsIn = nullptr;
   uint32_t* countsOut = nullptr;
 };
+// dgpu_float_stochastic_compress: what the histogram and the encoder form a member's random bits from.  Kernel arguments,
+// not part of the parameter block: calls that differ only in seed share the block and its cache entry.
+struct StochasticSeed {
+  uint64_t seed = 0;
+  const uint64_t* seed_dev = nullptr;
+  uint32_t firstMember = 0;
+};
 struct EncodeShared {
   uint32_t* checksumTemp = nullptr;  // [B] the batch's checksums (computed by the first class's call)
   uint4* table = nullptr;            // [B][256] encoder tables, indexed by the element's own index
@@ -1081,7 +1088,8 @@ int encodeCommon(
     uint32_t* histAcc_dev = nullptr /* the histogram in the stream's zero-at-rest counters instead of hist_dev (reduce-compress):
                                        the normalisation reads them and puts them back to zero */,
     const RollingCounts& rolling = RollingCounts{},
-    const DeviceBatch* residual = nullptr /* feedback source: its resIn / resOut */) {
+    const DeviceBatch* residual = nullptr /* feedback source: its resIn / resOut */,
+    const StochasticSeed& sr = StochasticSeed{} /* stochastic source: handed to both launches */) {
   // (kCountingSource is the planner's: from here on the source is what the kernels are instantiated for)
   sourceType &= ~kCountingSource;
   // (rolling.countsIn arrives as hist_dev -- encodeBatch passes it as the call's histogram; here it only says that the
@@ -1240,6 +1248,9 @@ int encodeCommon(
     n.histParts = histList ? 1u : grid.x;
     fuse.norm = n;
     fuse.residual = residual ? residual->resIn : BatchView{};
+    fuse.seed = sr.seed;
+    fuse.seedPtr = sr.seed_dev;
+    fuse.firstMember = sr.firstMember;
     // bins with 32 lane slots unless a workgroup sees too little data to pay for zeroing / folding them
     const bool smallBins = histList ? listedHistPartBytes <= 64u * 1024u : (uint64_t)maxSize * wordBytes / grid.x <= 64u * 1024u;
     rc = launchVariant(histogramVariant(sourceType, smallBins, histogramLoadsNonTemporal(floatType)), grid, stream, in, histTemp, 1u, fuse);
@@ -1281,6 +1292,9 @@ int encodeCommon(
     e.countsOut = rolling.countsOut;
     e.resIn = residual ? residual->resIn : BatchView{};
     e.resOut = residual ? residual->resOut : BatchView{};
+    e.seed = sr.seed;
+    e.seedPtr = sr.seed_dev;
+    e.firstMember = sr.firstMember;
     int rc = launchVariant(enc, dim3(grid), stream, e);
     if (rc) return rc;
   }
@@ -1292,15 +1306,17 @@ int encodeCommon(
 int encodeBatch(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b,
     const uint32_t* histogram_dev /*may be null*/, uint32_t* outSize_dev, hipStream_t stream,
-    uint32_t outCapacity = 0xffffffffu /* as encodeCommon's */, const RollingCounts& rolling = RollingCounts{}) {
+    uint32_t outCapacity = 0xffffffffu /* as encodeCommon's */, const RollingCounts& rolling = RollingCounts{},
+    const StochasticSeed& sr = StochasticSeed{}) {
   // a counting call is planned without single-block kernels, one with last call's counts as one with a caller's histogram
   if (rolling.countsOut) ft |= kCountingSource;
   if (rolling.countsIn) histogram_dev = rolling.countsIn;
   StreamLease streamLease(stream);
   TempArena arena(temp_dev, tempBytes, streamLease);
   DeviceBatch d;
-  // (a feedback call is planned as the cast call it extends: same geometry, same lists, same cached plan)
-  const uint32_t planType = ft & ~kFeedbackSource;
+  // (a feedback call, and a stochastic one, is planned as the cast call it extends: same geometry, same lists, same
+  // cached plan)
+  const uint32_t planType = ft & ~(kFeedbackSource | kStochasticSource);
   std::vector<LaunchGroup> groups{encodeRectangle(b.maxSize, planType)};
   int rc = resolveBatch(b, false, streamLease, &d, [&] { planEncodeCall(planPolicy(), b.sizes, planType, b.maxSize, histogram_dev != nullptr, &groups, &b.work); });
   if (rc) return rc;
@@ -1309,7 +1325,7 @@ int encodeBatch(
   EncodeShared shared;
   for (const LaunchGroup& g : groups) {
     rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, g, d.work, shared, histogram_dev, outSize_dev, outCapacity, nullptr, rolling,
-                      encIsFeedback(ft) ? &d : nullptr);
+                      encIsFeedback(ft) ? &d : nullptr, sr);
     if (rc) break;
   }
   if (tempUsed) *tempUsed = arena.requested();
@@ -1327,17 +1343,20 @@ int ansEncodeImpl(
 }
 
 // (cast: the batch holds float32 words and ft is the archive's 16-bit type; feedback: a cast call whose batch carries
-// residual pointers)
+// residual pointers; stochastic: a cast call that rounds with the random bits of *stochastic)
 int floatCompressImpl(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b, uint32_t* outSize_dev,
-    hipStream_t stream, bool cast = false, const RollingCounts& rolling = RollingCounts{}, bool feedback = false) {
+    hipStream_t stream, bool cast = false, const RollingCounts& rolling = RollingCounts{}, bool feedback = false,
+    const StochasticSeed* stochastic = nullptr) {
   bool done;
   int rc = checkCall(P, b.n, ft, tempUsed, /*errBatch*/ nullptr, &done,
                      "tensor larger than 1717538816 words: the maximum compressed size of its exponent plane exceeds INT32_MAX (GpuANSEncode.cu:22)",
                      b.maxSize);
   if (done) return rc;
-  const uint32_t source = feedback ? (ft | kCastSource | kFeedbackSource) : (cast ? (ft | kCastSource) : ft);
-  return encodeBatch(temp_dev, tempBytes, tempUsed, source, P, useChecksum, b, nullptr, outSize_dev, stream, 0xffffffffu, rolling);
+  const uint32_t source = stochastic ? (ft | kCastSource | kStochasticSource)
+                                     : (feedback ? (ft | kCastSource | kFeedbackSource) : (cast ? (ft | kCastSource) : ft));
+  return encodeBatch(temp_dev, tempBytes, tempUsed, source, P, useChecksum, b, nullptr, outSize_dev, stream, 0xffffffffu, rolling,
+                     stochastic ? *stochastic : StochasticSeed{});
 }
 
 // Order of k_ans_decode's workgroups (kernels_decode.h: decodeTileOf).  Measured on MI355X, cold round trip
@@ -2478,6 +2497,28 @@ int dgpu_float_feedback_compress(
   return floatCompressImpl(temp_dev, tempBytes, tempUsed, floatType, probBits, 0, b, outSize_dev, (hipStream_t)stream, true, RollingCounts{}, true);
 }
 
+// ---- stochastic cast-compress (no upstream equivalent) ---------------------------------
+// Cast-compress whose every rounding is stochastic (kernels_encode.h, ChunkSourceStochastic): the cast call with a source
+// flag and three values handed to its two launches.  Temporaries come from the stream's slab.
+int dgpu_float_stochastic_compress(
+    uint32_t floatType, int probBits, uint32_t numInBatch, const void* const* in, const uint32_t* inSize, uint64_t seed,
+    const uint64_t* seed_dev, uint32_t firstMember, void* const* out, uint32_t* outSize_dev, void* stream) {
+  DGPU_REQUIRE(floatType == kFloat16 || floatType == kBFloat16, "stochastic compress: floatType of the archive must be float16 or bfloat16");
+  DGPU_REQUIRE(validProbBits(probBits), "probBits must be 9, 10 or 11");
+  DGPU_REQUIRE(numInBatch <= 65535u, "numInBatch must be <= 65535");
+  DGPU_REQUIRE((uintptr_t)seed_dev % 8u == 0u, "stochastic compress: seed_dev must be 8-byte aligned");
+  DGPU_REQUIRE(numInBatch == 0 || (in && inSize && out), "stochastic compress: null array with numInBatch > 0");
+  for (uint32_t i = 0; i < numInBatch; ++i) {
+    DGPU_REQUIRE(encodableSize(inSize[i]),
+                 "tensor larger than 1717538816 words: the maximum compressed size of its exponent plane exceeds INT32_MAX (GpuANSEncode.cu:22)");
+  }
+  Batch b;
+  int rc = pointerBatch(&b, numInBatch, ptrSide(in, 4, "float32 input must be 4-byte aligned"), ptrSide(out, 16, kMsgCompOut), inSize);
+  if (rc) return rc;
+  const StochasticSeed sr{seed, seed_dev, firstMember};
+  return floatCompressImpl(nullptr, 0, nullptr, floatType, probBits, 0, b, outSize_dev, (hipStream_t)stream, true, RollingCounts{}, false, &sr);
+}
+
 // ---- rolling-table compress (no upstream equivalent) ------------------------------------
 // The table of this call from the counts of the last one (countsIn_dev: no histogram pass), the counts of this call for
 // the next one (countsOut_dev: the counting encoder).  float16 / bfloat16 archives only: the float32 encoder has no
@@ -2558,6 +2599,9 @@ int dgpu_ans_histogram_batch_stride(
   noFuse.acc = nullptr;
   noFuse.norm = NormalizeArgs{};
   noFuse.residual = BatchView{};
+  noFuse.seed = 0;
+  noFuse.seedPtr = nullptr;
+  noFuse.firstMember = 0;
   const HistogramVariant hist = histogramVariant(0u, false, true);
   hipLaunchKernelGGL(hist.fn, grid, dim3(hist.threads), hist.ldsBytes, (hipStream_t)stream, in, histogram_dev, 0u, noFuse);
   DGPU_HIP(hipGetLastError());

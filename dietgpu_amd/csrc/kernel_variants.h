@@ -77,8 +77,9 @@ constexpr bool encodeSpills(uint32_t ft) { return ft != 0; }
 // 8-block tiles persistent -- without the wide stage, and as every histogram form.  There is no cast form of the
 // single-block kernels (k_ans_encode_pair, k_stats_single): single-block members of a cast call run on 2-block tiles.
 // Feedback sources (kFeedbackSource as well: the residual added before the rounding, the rounding error stored) exist
-// in exactly the cast source's forms.
-inline EncodeVariant encoderVariantCast(int P, uint32_t archiveType, uint32_t tileBlocks, bool hwDispatch, bool feedback = false) {
+// in exactly the cast source's forms, and so do stochastic sources (kStochasticSource: every rounding stochastic).
+// `extra`: 0, kFeedbackSource or kStochasticSource.
+inline EncodeVariant encoderVariantCast(int P, uint32_t archiveType, uint32_t tileBlocks, bool hwDispatch, uint32_t extra = 0u) {
   auto of = [&](auto p, auto f) -> EncodeVariant {
     constexpr int kP = decltype(p)::value;
     constexpr uint32_t kFT = decltype(f)::value | kCastSource;
@@ -86,7 +87,7 @@ inline EncodeVariant encoderVariantCast(int P, uint32_t archiveType, uint32_t ti
       constexpr uint32_t kTB = decltype(tb)::value;
       constexpr bool kPersistent = decltype(persistent)::value;
       return {k_ans_encode<kP, kFT, true, kTB, kPersistent, false>, encThreads(kTB), encLdsBytes(kP, true, kFT, kTB),
-              encIsFeedback(kFT) ? "k_ans_encode_feedback" : "k_ans_encode_cast"};
+              encIsStochastic(kFT) ? "k_ans_encode_stochastic" : (encIsFeedback(kFT) ? "k_ans_encode_feedback" : "k_ans_encode_cast")};
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
@@ -95,7 +96,8 @@ inline EncodeVariant encoderVariantCast(int P, uint32_t archiveType, uint32_t ti
     return tiled(UintC<kBlocksPerTile>{}, yes);
   };
   return withProbBits(P, [&](auto p) {
-    if (feedback) return archiveType == kFloat16 ? of(p, UintC<kFloat16 | kFeedbackSource>{}) : of(p, UintC<kBFloat16 | kFeedbackSource>{});
+    if (extra == kFeedbackSource) return archiveType == kFloat16 ? of(p, UintC<kFloat16 | kFeedbackSource>{}) : of(p, UintC<kBFloat16 | kFeedbackSource>{});
+    if (extra == kStochasticSource) return archiveType == kFloat16 ? of(p, UintC<kFloat16 | kStochasticSource>{}) : of(p, UintC<kBFloat16 | kStochasticSource>{});
     return archiveType == kFloat16 ? of(p, UintC<kFloat16>{}) : of(p, UintC<kBFloat16>{});
   });
 }
@@ -129,7 +131,7 @@ inline EncodeVariant encoderVariantCounting(int P, uint32_t ft, uint32_t tileBlo
 //     gain there);
 //   * wide: the wide stage (kSpillStageWordsWide) exists for persistent 8-block bf16 / fp32 tiles only.
 inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, bool hwDispatch, bool wide) {
-  if (encIsCast(ft)) return encoderVariantCast(P, encArchiveType(ft), tileBlocks, hwDispatch, encIsFeedback(ft));
+  if (encIsCast(ft)) return encoderVariantCast(P, encArchiveType(ft), tileBlocks, hwDispatch, ft & (kFeedbackSource | kStochasticSource));
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> EncodeVariant {
     constexpr int kP = decltype(p)::value;
     constexpr uint32_t kFT = decltype(f)::value;
@@ -234,7 +236,8 @@ inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, Dec
 }
 
 // The histogram pass: bins with kHistSlotsSmall or kHistSlotsLarge lane slots, non-temporal or ordinary input loads.
-// (ft with kCastSource: the cast form, which bins the exponent byte of the rounded word)
+// (ft with kCastSource: the cast form, which bins the exponent byte of the rounded word; with kFeedbackSource or
+// kStochasticSource as well: that source's rounding)
 inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTemporal) {
   auto pick = [&](auto f) -> HistogramVariant {
     constexpr uint32_t kFT = decltype(f)::value;
@@ -245,7 +248,8 @@ inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTe
         return {k_histogram<kS, kNt>, 256u, 0u, "k_histogram"};
       } else {
         return {k_float_histogram<kFT, kS, kNt>, 256u, 0u,
-                encIsFeedback(kFT) ? "k_float_histogram_feedback" : (encIsCast(kFT) ? "k_float_histogram_cast" : "k_float_histogram")};
+                encIsStochastic(kFT) ? "k_float_histogram_stochastic"
+                                     : (encIsFeedback(kFT) ? "k_float_histogram_feedback" : (encIsCast(kFT) ? "k_float_histogram_cast" : "k_float_histogram"))};
       }
     };
     constexpr UintC<kHistSlotsSmall> small{};
@@ -255,6 +259,9 @@ inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTe
   };
   if (encIsFeedback(ft)) {
     return encArchiveType(ft) == kFloat16 ? pick(UintC<kFloat16 | kCastSource | kFeedbackSource>{}) : pick(UintC<kBFloat16 | kCastSource | kFeedbackSource>{});
+  }
+  if (encIsStochastic(ft)) {
+    return encArchiveType(ft) == kFloat16 ? pick(UintC<kFloat16 | kCastSource | kStochasticSource>{}) : pick(UintC<kBFloat16 | kCastSource | kStochasticSource>{});
   }
   if (encIsCast(ft)) return encArchiveType(ft) == kFloat16 ? pick(UintC<kFloat16 | kCastSource>{}) : pick(UintC<kBFloat16 | kCastSource>{});
   return withFloatType(ft, pick);

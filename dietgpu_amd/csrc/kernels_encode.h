@@ -161,6 +161,11 @@ struct EncodeArgs {
                              // exponent-byte counts are added with relaxed agent-scope atomics
   BatchView resIn, resOut;   // feedback source only: the float32 residual that is added (all zero: none yet) and the one
                              // that is stored; resOut.ptr(b) may equal resIn.ptr(b)
+  // stochastic source only: member b rounds with the random bits of (seedPtr ? *seedPtr : seed, firstMember + b); the
+  // word at seedPtr (device memory) is read when the kernel runs
+  uint64_t seed;
+  const uint64_t* seedPtr;
+  uint32_t firstMember;
 };
 
 struct TileShared {
@@ -704,6 +709,102 @@ struct ChunkSource<kFloat16 | kCastSource | kFeedbackSource> : ChunkSourceFeedba
 template <>
 struct ChunkSource<kBFloat16 | kCastSource | kFeedbackSource> : ChunkSourceFeedback<kBFloat16> {};
 
+// two float32 words and the 32 random bits of their pair (srBits: the low half is the even word's) -> one dword of two
+// 16-bit words, rounded stochastically (x0's in the low half)
+template <uint32_t AT>
+__device__ __forceinline__ uint32_t castRoundStochasticPair(uint32_t x0, uint32_t x1, uint32_t bits) {
+  if (AT == kBFloat16) {
+    return __builtin_amdgcn_perm(castRoundStochasticHigh<kBFloat16>(x1, bits >> 16), castRoundStochasticHigh<kBFloat16>(x0, bits & 0xffffu), 0x07060302u);
+  }
+  return __builtin_amdgcn_perm(castRoundStochastic<AT>(x1, bits >> 16), castRoundStochastic<AT>(x0, bits & 0xffffu), 0x05040100u);
+}
+// the 16-bit random number of word k of the member with `key` (k: the word's index within the ELEMENT)
+__device__ __forceinline__ uint32_t srWordBits(uint32_t key, uint32_t k) {
+  const uint32_t bits = srBits(key, k >> 1);
+  return (k & 1u) ? bits >> 16 : bits & 0xffffu;
+}
+
+// Stochastic source: ChunkSourceCast's chunk shape -- 8 rows, two 16-byte loads, one 8-byte non-compressed store per
+// lane -- with every rounding stochastic (castRoundStochastic; dgpu_float_stochastic_compress).  The random number of a
+// word goes by the word's index k within its ELEMENT, whatever block, tile, workgroup or path reaches it: the histogram
+// (k_float_histogram, which rounds the same word in another kernel) must arrive at the same symbol.  A lane's 8
+// consecutive words begin at a multiple of 8: four srBits(key, k >> 1), as in UpdateSink.  `key` (srMemberKey) is
+// wave-uniform and set per tile by k_ans_encode.  Tail forms: words at or beyond n are zero before they are rounded and
+// zero, which both types represent, never moves.
+template <uint32_t AT>
+struct ChunkSourceStochastic {
+  static constexpr uint32_t kRows = 8;
+  struct Raw { uint4 v[2]; };
+  const uint32_t* in;  // this half's block (4096 float32 words)
+  uint8_t* nc;         // this half's block of the non-comp plane
+  // The pair index of word i of the block is (block * 4096 + i) >> 1 = block * 2048 | i >> 1: its two parts share no
+  // bit, so the member's key and the block's part are ONE word, keyBlock = key ^ block * 2048, and
+  // srBits(key, pair) = srMix32(keyBlock ^ i >> 1) -- one register across the row loop instead of two.
+  uint32_t keyBlock;
+  __device__ __forceinline__ void init(const uint8_t* elemIn, uint8_t* archive, uint32_t, uint32_t block) {
+    in = (const uint32_t*)elemIn + (size_t)block * kBlockSize;
+    nc = archive + 16u + (size_t)block * kBlockSize;
+    keyBlock = block * (kBlockSize / 2u);  // (k_ans_encode adds the key: setKey)
+  }
+  __device__ __forceinline__ void setKey(uint32_t key) { keyBlock ^= key; }
+  __device__ __forceinline__ Raw load(uint32_t c, uint32_t hl) const {
+    const uint4* p = (const uint4*)(in + c * 256u + hl * 8u);
+    Raw r;
+    r.v[0] = streamLoad<kNtEncLoads>(&p[0]);
+    r.v[1] = streamLoad<kNtEncLoads>(&p[1]);
+    return r;
+  }
+  static constexpr uint32_t kCompRegs = 2;
+  __device__ __forceinline__ void consume(const Raw& r, uint32_t c, uint32_t hl, uint8_t* ring) const {
+    uint32_t comp[2];
+    splitStore(r, c, hl, comp);
+    *(uint2*)(ring + hl * 8u) = make_uint2(comp[0], comp[1]);
+  }
+  __device__ __forceinline__ Raw loadTail(uint32_t c, uint32_t hl, uint32_t n) const {
+    const uint32_t first = c * 256u + hl * 8u;
+    Raw r;
+    loadSliceBounded<2>((const uint8_t*)in, first * 4u, n * 4u, r.v);
+    return r;
+  }
+  __device__ __forceinline__ void consumeTail(const Raw& r, uint32_t c, uint32_t hl, uint8_t* ring, uint32_t n) const {
+    const uint32_t first = c * 256u + hl * 8u;
+    const uint32_t valid = n > first ? (n - first < 8u ? n - first : 8u) : 0u;
+    auto keep = [&](uint32_t x, uint32_t j) -> uint32_t { return valid > j ? x : 0u; };
+    Raw m;
+    m.v[0] = make_uint4(keep(r.v[0].x, 0), keep(r.v[0].y, 1), keep(r.v[0].z, 2), keep(r.v[0].w, 3));
+    m.v[1] = make_uint4(keep(r.v[1].x, 4), keep(r.v[1].y, 5), keep(r.v[1].z, 6), keep(r.v[1].w, 7));
+    uint32_t comp[2];
+    splitStore(m, c, hl, comp, valid != 0u);
+    *(uint2*)(ring + hl * 8u) = make_uint2(comp[0], comp[1]);
+  }
+  __device__ __forceinline__ void splitStore(const Raw& r, uint32_t c, uint32_t hl, uint32_t (&comp)[kCompRegs], bool store = true) const {
+    const uint32_t pair0 = c * 128u + hl * 4u;  // (a multiple of 4 below 2048)
+    const uint32_t x[4] = {castRoundStochasticPair<AT>(r.v[0].x, r.v[0].y, srBits(keyBlock, pair0)), castRoundStochasticPair<AT>(r.v[0].z, r.v[0].w, srBits(keyBlock, pair0 | 1u)),
+                           castRoundStochasticPair<AT>(r.v[1].x, r.v[1].y, srBits(keyBlock, pair0 | 2u)), castRoundStochasticPair<AT>(r.v[1].z, r.v[1].w, srBits(keyBlock, pair0 | 3u))};
+    uint32_t rest[2];
+    splitPacked16<AT, 4>(x, comp, rest);
+    if (store) *(uint2*)(nc + c * 256u + hl * 8u) = make_uint2(rest[0], rest[1]);
+  }
+  // scalar path: the rounded 16-bit word of word i of the block
+  __device__ __forceinline__ uint32_t wordAt(uint32_t i) const { return castRoundStochastic<AT>(in[i], srWordBits(keyBlock, i)); }
+  __device__ __forceinline__ uint32_t splitAt(uint32_t i, uint32_t w, bool valid) const {
+    uint32_t c, r;
+    if (AT == kFloat16) {
+      c = w >> 8;
+      r = w & 0xffu;
+    } else {
+      c = (w >> 7) & 0xffu;
+      r = ((w << 1) & 0xfeu) | (w >> 15);
+    }
+    if (valid) nc[i] = (uint8_t)r;
+    return c;
+  }
+};
+template <>
+struct ChunkSource<kFloat16 | kCastSource | kStochasticSource> : ChunkSourceStochastic<kFloat16> {};
+template <>
+struct ChunkSource<kBFloat16 | kCastSource | kStochasticSource> : ChunkSourceStochastic<kBFloat16> {};
+
 // ---------------------------------------------------------------------------
 // The emitting lanes of a full-block row store their word under the row's ballot as execution mask -- two scalar
 // instructions instead of the v_cndmask that would park the idle lanes' store on a scratch slot -- and, for raw
@@ -1177,11 +1278,15 @@ __device__ __forceinline__ uint32_t lookBackTwoLevel(const uint64_t* desc, uint6
 // for persistent spilling tiles of float16 / bfloat16 archives (plain and cast sources), without the wide stage.
 // (the feedback source keeps 16 registers of loads in flight per lane where the cast source keeps 8: it is allowed the
 // registers of 4 waves per SIMD, the residency at which the row loop still loses nothing -- DESIGN.md section 8.1)
-__host__ __device__ constexpr int encMinWavesPerSimd(uint32_t ft) { return encIsFeedback(ft) ? 4 : 6; }
+// (the stochastic source: the four mixes of a chunk and the key on top of the cast source's 76 to 80 registers -- at 6 waves
+// the hardware-dispatched 4-block form spills 12 bytes per lane; every form is allowed the registers of 5)
+__host__ __device__ constexpr int encMinWavesPerSimd(uint32_t ft) { return encIsFeedback(ft) ? 4 : (encIsStochastic(ft) ? 5 : 6); }
 template <int P, uint32_t FT, bool kSpill, uint32_t kTB, bool kPersistent, bool kWide = false, bool kCount = false>
 __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu(encMinWavesPerSimd(FT), 8))) void k_ans_encode(EncodeArgs a) {
   static_assert(kTB >= 2u, "single-block elements are k_ans_encode_pair's");
   static_assert(!encIsFeedback(FT) || (encIsCast(FT) && kSpill && !kWide && !kCount), "the feedback source extends the cast source; no counting form");
+  static_assert(!encIsStochastic(FT) || (encIsCast(FT) && !encIsFeedback(FT) && kSpill && !kWide && !kCount),
+                "the stochastic source is a cast source; no counting and no feedback form");
   static_assert(!kCount || (kSpill && kPersistent && !kWide && (encArchiveType(FT) == kFloat16 || encArchiveType(FT) == kBFloat16)),
                 "the counting form exists for persistent 16-bit float tiles");
   constexpr uint32_t kCountSlots = kCount ? encCountSlots(kTB) : 0u;
@@ -1348,6 +1453,8 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
         const bool haveResidual = a.resIn.ptrs != nullptr || a.resIn.base != 0ull;  // (uniform)
         src.initResidual(haveResidual ? a.resIn.ptr(b) : nullptr, a.resOut.ptr(b), haveBlock ? block : (waveHalf ? firstBlockOfWave : 0u));
       }
+      // (the member's key, once per tile: consecutive tiles of a persistent workgroup belong to different elements)
+      if constexpr (encIsStochastic(FT)) src.setKey(srMemberKey(a.seedPtr ? *a.seedPtr : a.seed, a.firstMember + b));
 
       uint32_t state;
       uint32_t words;        // words left in the LDS stage
@@ -1534,12 +1641,18 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
 // Feedback form (kFeedbackSource as well): the word that is rounded is x + e, with e from fuse.residual -- the encoder's
 // single add (feedbackSum), or the table would not cover the symbols the encoder codes.  The residual is congruent to
 // the element modulo 16, so both streams take their vectors from the same boundary.  The pass only reads.
+// Stochastic form (kStochasticSource as well): the bin is the exponent byte of castRoundStochastic(x, r16) with the
+// random number of the word's index k within the ELEMENT, as the encoder's ChunkSourceStochastic takes it.  The vectors
+// begin at the first 16-byte boundary, `head` words into the element: vector v holds words head + 4 v .. head + 4 v + 3,
+// which start at an odd k when head is odd -- k follows the element, not the address.
 template <uint32_t FT, uint32_t S, bool kNt = true>
 __global__ __launch_bounds__(256) void k_float_histogram(BatchView in, uint32_t* __restrict__ hist, uint32_t partial, HistFuse fuse) {
   __shared__ uint32_t bins[kNumSymbols * S];
   const uint32_t tid = threadIdx.x;
   constexpr bool kCast = encIsCast(FT);
   constexpr bool kFeedback = encIsFeedback(FT);
+  constexpr bool kStochastic = encIsStochastic(FT);
+  static_assert(!kStochastic || (kCast && !kFeedback), "the stochastic source is a cast source without feedback");
   constexpr uint32_t AT = encArchiveType(FT);
   const HistWork w = histWorkOf(fuse, in, AT == kFloat32 ? 4u : 2u);
   const uint32_t b = w.b;
@@ -1574,8 +1687,24 @@ __global__ __launch_bounds__(256) void k_float_histogram(BatchView in, uint32_t*
   };
 
   constexpr uint32_t kShift16 = AT == kFloat16 ? 8u : 7u;  // exponent byte of a 16-bit word
-  auto addVec = [&](const uint4& x, [[maybe_unused]] const uint4& e) {
-    if (kFeedback) {
+  // stochastic form: the member's key (uniform)
+  [[maybe_unused]] uint32_t key = 0;
+  if constexpr (kStochastic) key = srMemberKey(fuse.seedPtr ? *fuse.seedPtr : fuse.seed, fuse.firstMember + b);
+  auto addVec = [&](const uint4& x, [[maybe_unused]] const uint4& e, [[maybe_unused]] uint32_t v) {
+    if (kStochastic) {
+      // words k0 .. k0 + 3 of the element: two pairs when k0 is even, the halves of three when it is odd (head: uniform)
+      const uint32_t xw[4] = {x.x, x.y, x.z, x.w};
+      const uint32_t k0 = head + v * 4u, pair0 = k0 >> 1;
+      const uint32_t b0 = srBits(key, pair0), b1 = srBits(key, pair0 + 1u);
+      uint32_t r[4];
+      if ((head & 1u) == 0u) {
+        r[0] = b0 & 0xffffu, r[1] = b0 >> 16, r[2] = b1 & 0xffffu, r[3] = b1 >> 16;
+      } else {
+        r[0] = b0 >> 16, r[1] = b1 & 0xffffu, r[2] = b1 >> 16, r[3] = srBits(key, pair0 + 2u) & 0xffffu;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) histAdd<S>(myBins, (castRoundStochastic<kCast ? AT : kBFloat16>(xw[j], r[j]) >> kShift16) & 0xffu);
+    } else if (kFeedback) {
       const uint32_t xw[4] = {x.x, x.y, x.z, x.w}, ew[4] = {e.x, e.y, e.z, e.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -1612,19 +1741,21 @@ __global__ __launch_bounds__(256) void k_float_histogram(BatchView in, uint32_t*
   for (; v + 768u < vEnd; v += 1024u) {
     const uint4 x0 = streamLoad<kNt>(&pv[v]), x1 = streamLoad<kNt>(&pv[v + 256u]), x2 = streamLoad<kNt>(&pv[v + 512u]), x3 = streamLoad<kNt>(&pv[v + 768u]);
     const uint4 e0 = loadRes(v), e1 = loadRes(v + 256u), e2 = loadRes(v + 512u), e3 = loadRes(v + 768u);
-    addVec(x0, e0);
-    addVec(x1, e1);
-    addVec(x2, e2);
-    addVec(x3, e3);
+    addVec(x0, e0, v);
+    addVec(x1, e1, v + 256u);
+    addVec(x2, e2, v + 512u);
+    addVec(x3, e3, v + 768u);
   }
-  for (; v < vEnd; v += 256u) addVec(streamLoad<kNt>(&pv[v]), loadRes(v));
+  for (; v < vEnd; v += 256u) addVec(streamLoad<kNt>(&pv[v]), loadRes(v), v);
 
   // head and tail, word by word (the whole element when the input is not even word-aligned)
   const uint32_t loose = n - numVec * kWordsPerVec;
   for (uint32_t j = w.part * 256u + tid; j < loose; j += stride) {
     const uint32_t i = j < head ? j : numVec * kWordsPerVec + j;
     uint32_t c;
-    if (kFeedback) {
+    if (kStochastic) {
+      c = (castRoundStochastic<kCast ? AT : kBFloat16>(((const uint32_t*)inBytes)[i], srWordBits(key, i)) >> kShift16) & 0xffu;
+    } else if (kFeedback) {
       const uint32_t e = resBytes ? ((const uint32_t*)resBytes)[i] : 0u;
       c = (castRound<kCast ? AT : kBFloat16>(feedbackSum(((const uint32_t*)inBytes)[i], e, resBytes != nullptr)) >> kShift16) & 0xffu;
     } else if (kCast) c = (castRound<kCast ? AT : kBFloat16>(((const uint32_t*)inBytes)[i]) >> kShift16) & 0xffu;

@@ -403,6 +403,10 @@ struct HistFuse {
   const uint32_t* workMap;
   uint32_t partBytes;
   BatchView residual;  // feedback form of k_float_histogram only: the float32 residual added before the rounding (all zero: none)
+  // stochastic form of k_float_histogram only: as EncodeArgs::seed / seedPtr / firstMember
+  uint64_t seed;
+  const uint64_t* seedPtr;
+  uint32_t firstMember;
 };
 
 // Which (element, part of how many) a histogram workgroup counts, and where its partial histogram goes.

@@ -32,7 +32,13 @@ constexpr uint32_t kCountingSource = 0x200u;
 // the cast source it extends; there is no counting form.
 constexpr uint32_t kFeedbackSource = 0x400u;
 DGPU_HD constexpr bool encIsFeedback(uint32_t ft) { return (ft & kFeedbackSource) != 0u; }
-DGPU_HD constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~(kCastSource | kCountingSource | kFeedbackSource); }
+// kStochasticSource (with kCastSource): a cast source that rounds stochastically, with random bits that are a pure
+// function of (seed, member, word index within the element) -- the histogram and the encoder round the same word in
+// different kernels and must agree (kernels_encode.h, ChunkSourceStochastic).  Planned and launched as the cast source;
+// there is no counting and no feedback form.
+constexpr uint32_t kStochasticSource = 0x800u;
+DGPU_HD constexpr bool encIsStochastic(uint32_t ft) { return (ft & kStochasticSource) != 0u; }
+DGPU_HD constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~(kCastSource | kCountingSource | kFeedbackSource | kStochasticSource); }
 // whether single-block elements of such a call have kernels of their own (k_ans_encode_pair, k_stats_single)
 DGPU_HD constexpr bool encHasSingleBlockKernels(uint32_t ft) { return (ft & (kCastSource | kCountingSource)) == 0u && ft != kFloat32; }
 

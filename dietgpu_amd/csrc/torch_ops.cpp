@@ -712,6 +712,49 @@ std::tuple<at::Tensor, at::Tensor, int64_t> compress_data_feedback(
   return {std::move(comp), std::move(sizes), (int64_t)used};
 }
 
+// Stochastic cast-compress (no reference op): compress_data_cast whose every rounding is stochastic, with the random bits of
+// (seed, first_member + i, word index) (dgpu_float_stochastic_compress).  seed / seed_dev as in decompress_data_update.  No
+// temp memory is passed: -> (comp, sizes).
+std::tuple<at::Tensor, at::Tensor> compress_data_stochastic(
+    const std::vector<at::Tensor>& tIns, int64_t floatType, int64_t seed, const std::optional<at::Tensor>& seedDev, int64_t firstMember,
+    const std::optional<at::Tensor>& outCompressed, const std::optional<at::Tensor>& outCompressedSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(floatType == (int64_t)DGPU_FLOAT16 || floatType == (int64_t)DGPU_BFLOAT16, "dietgpu: float_type must be 1 (float16) or 2 (bfloat16)");
+  TORCH_CHECK(firstMember >= 0 && firstMember <= (int64_t)std::numeric_limits<uint32_t>::max(), "dietgpu: first_member must be in [0, 2^32)");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  const size_t n = tIns.size();
+  int64_t maxWords = 0;
+  for (auto& t : tIns) {
+    TORCH_CHECK(t.device().is_cuda() && t.is_contiguous() && t.get_device() == dev);
+    TORCH_CHECK(t.scalar_type() == at::ScalarType::Float, "dietgpu: the inputs of a stochastic cast call must be float32");
+    maxWords = std::max<int64_t>(maxWords, t.numel());
+  }
+  const uint64_t* seedPtr = nullptr;
+  if (seedDev) {
+    const at::Tensor& s = *seedDev;
+    TORCH_CHECK(s.device().is_cuda() && s.get_device() == dev && s.is_contiguous() && s.scalar_type() == at::ScalarType::Long && s.numel() == 1,
+                "dietgpu: a tensor seed must be a 1-element int64 tensor on the tensors' GPU");
+    seedPtr = (const uint64_t*)s.data_ptr();
+  }
+  at::Tensor comp, sizes;
+  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxFloatSize((uint32_t)floatType, (uint64_t)maxWords), dev,
+                  tIns[0].device(), comp, sizes);
+  std::vector<const void*> inPtrs(n);
+  std::vector<uint32_t> inSize(n);
+  std::vector<void*> compPtrs(n);
+  for (size_t i = 0; i < n; ++i) {
+    inPtrs[i] = tIns[i].data_ptr();
+    inSize[i] = (uint32_t)tIns[i].numel();
+    compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
+  }
+  check(dgpu_float_stochastic_compress((uint32_t)floatType, precision(), (uint32_t)n, inPtrs.data(), inSize.data(), (uint64_t)seed, seedPtr,
+                                       (uint32_t)firstMember, compPtrs.data(), (uint32_t*)sizes.data_ptr(), streamOf(dev)),
+        "floatCompressStochastic", true);
+  return {std::move(comp), std::move(sizes)};
+}
+
 // Rolling-table compress (no reference op): compress_data / compress_data_cast with the tables made from the counts the
 // last call left (counts_in) and this call's counts taken by the encoder (counts_out): dgpu_float_rolling_compress.
 // float_type (1 = float16, 2 = bfloat16) is that of the archives; source_float32: ts_in are float32 and are rounded.
@@ -1030,6 +1073,9 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "compress_data_feedback(Tensor[] ts_in, Tensor[] ts_residual, int float_type, bool fresh=False, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::compress_data_feedback);
+  m.def(
+      "compress_data_stochastic(Tensor[] ts_in, int float_type, int seed, Tensor? seed_dev=None, int first_member=0, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor)",
+      &dietgpu_amd::compress_data_stochastic);
   m.def(
       "compress_data_rolling(Tensor[] ts_in, Tensor? counts_in, Tensor? counts_out, int float_type, bool source_float32=False, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::compress_data_rolling);

@@ -163,6 +163,16 @@ class GpuFloatCodec:
         comp, sizes, _ = ops.compress_data_feedback(tensors, residuals, dtype, fresh, self.temp_mem)
         return comp, sizes
 
+    def compress_cast_stochastic(self, tensors, dtype, seed, first_member=0):
+        """compress_cast with STOCHASTIC rounding (ops.compress_data_stochastic): tensor i is rounded with the random bits
+        of member first_member + i under `seed` -- an int in [0, 2^64) or a 1-element int64 tensor on the device, never
+        read by the host.  Unbiased, and without the residual of compress_cast_feedback.  It does not use the rolling
+        tables (there is no counting form of the stochastic encoder)."""
+        from . import ops
+
+        self.dtype = dtype
+        return ops.compress_data_stochastic(tensors, dtype, seed, first_member)
+
     def decompress(self, rows, outs, scale=None):
         """`scale` (a number, or a float32 tensor of 1 or len(rows) elements on the device): every word is multiplied by
         it in the decode kernel (ops.decompress_data_scaled); a tensor is never read by the host"""
@@ -381,14 +391,50 @@ def _check_wire(what, tensor, codec, raw_local, wire_dtype, residual):
         raise RuntimeError(f"{what}: a residual needs a codec with compress_cast_feedback(tensors, residuals, dtype, fresh)")
 
 
-def _exchange_shard_rows(tensor, codec, raw_local=False, wire_dtype=None, residual=None, residual_fresh=False):
+def _check_wire_seed(what, tensor, wire_dtype, wire_seed, residual, norm, clip_norm=None, needs_wire_dtype=True):
+    """The arguments of a stochastically rounded wire (wire_seed), before anything is exchanged."""
+    if wire_seed is None:
+        return
+    if isinstance(wire_seed, torch.Tensor):
+        if not (wire_seed.dtype == torch.int64 and wire_seed.numel() == 1 and wire_seed.device == tensor.device):
+            raise RuntimeError(f"{what}: a tensor wire_seed must be a 1-element int64 tensor on the tensor's device")
+    elif not (isinstance(wire_seed, int) and not isinstance(wire_seed, bool) and 0 <= wire_seed < (1 << 64)):
+        raise RuntimeError(f"{what}: wire_seed must be an int in [0, 2^64) or a 1-element int64 tensor")
+    if needs_wire_dtype and wire_dtype is None:
+        raise RuntimeError(f"{what}: wire_seed needs wire_dtype -- without it nothing is rounded here")
+    if residual is not None:
+        raise RuntimeError(f"{what}: wire_seed cannot be combined with a residual -- error feedback and stochastic rounding are "
+                           "alternatives")
+    if norm or clip_norm is not None:
+        raise RuntimeError(f"{what}: wire_seed cannot be combined with norm=True or clip_norm -- the statistics must describe the "
+                           "archive's words, which on the stochastic path only a second pass could give")
+
+
+def _compress_stochastic(codec, tensors, dtype, seed, first_member):
+    """float32 tensors -> archives of `dtype`, tensor i rounded stochastically with the random bits of member
+    first_member + i under `seed` (dgpu_float_stochastic_compress) -> (comp, sizes).  A codec with
+    `compress_cast_stochastic` does it in ONE call (GpuFloatCodec: in the compressor's two kernels); any other codec gets
+    the rounding from torch (rounding.stochastic_round_) into a 16-bit scratch and compresses that.  The same bits."""
+    method = getattr(codec, "compress_cast_stochastic", None)
+    if callable(method):
+        return method(tensors, dtype, seed, first_member=first_member)
+    from . import rounding
+
+    scratch = [torch.empty(t.shape, dtype=dtype, device=t.device) for t in tensors]
+    for i, (q, t) in enumerate(zip(scratch, tensors)):
+        rounding.stochastic_round_(q, t, seed, (first_member + i) & 0xFFFFFFFF)
+    return codec.compress(scratch)
+
+
+def _exchange_shard_rows(tensor, codec, raw_local=False, wire_dtype=None, residual=None, residual_fresh=False, wire_seed=None):
     """The exchange half of compressed_reduce_scatter: shard j of this rank's flat tensor, compressed, goes to rank j ->
     (words per shard, recv [source rank, width] uint8, all_sizes [source rank, destination rank] int32, width).
     raw_local: the rank's own shard is not compressed (the codec gets the other world - 1, none at all in a world of one);
     its row of the exchange has size 0 and carries nothing.
     wire_dtype (float16 / bfloat16, for a float32 tensor): the shards are rounded to it by the compressor -- the codec's
     compress_cast, or, with `residual` (a flat float32 tensor of the tensor's length, updated in place), its
-    compress_cast_feedback on the shards and the matching views of the residual."""
+    compress_cast_feedback on the shards and the matching views of the residual, or, with `wire_seed`, stochastically
+    (_compress_stochastic): the shard of this rank for destination j is member rank * world + j."""
     world = dist.get_world_size()
     if tensor.dim() != 1 or tensor.numel() % world != 0:
         raise RuntimeError("compressed_reduce_scatter: the tensor must be flat, its length a multiple of the world size")
@@ -408,6 +454,8 @@ def _exchange_shard_rows(tensor, codec, raw_local=False, wire_dtype=None, residu
             comp[me].zero_()  # (travels to this rank itself; nothing reads it)
     elif wire_dtype is not None and residual is not None:
         comp, sizes = codec.compress_cast_feedback(shards, list(residual.view(world, shard_words).unbind(0)), wire_dtype, bool(residual_fresh))
+    elif wire_dtype is not None and wire_seed is not None:
+        comp, sizes = _compress_stochastic(codec, shards, wire_dtype, wire_seed, dist.get_rank() * world)
     elif wire_dtype is not None:
         comp, sizes = codec.compress_cast(shards, wire_dtype)
     else:
@@ -505,7 +553,7 @@ def _scale_shard(shard, factor):
 
 
 def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False, wire_dtype=None, residual=None,
-                              residual_fresh=False):
+                              residual_fresh=False, wire_seed=None):
     """Reduce-scatter (sum) of a flat float tensor, moving compressed bytes and summing in float32.
 
     `tensor`: this rank's flat fp16 / bf16 / fp32 tensor; its length is a multiple of the world size and the same on
@@ -547,9 +595,20 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
     rounding has error feedback: the codec's compress_cast_feedback(shards, residual's shard views, wire_dtype, fresh) adds
     the residual before it rounds and stores the new rounding error back, in place.  residual_fresh=True: the first step,
     the residual is only written.  raw_local=True with wire_dtype, and a residual with a codec that has no
-    compress_cast_feedback, raise RuntimeError."""
+    compress_cast_feedback, raise RuntimeError.
+
+    wire_seed (with wire_dtype; an int in [0, 2^64), or a 1-element int64 tensor on the device, never read by the host):
+    the rounding to wire_dtype is STOCHASTIC -- unbiased, where round to nearest drops a component below half a unit at
+    every step, and without a residual's 4 bytes per element.  The shard of source rank r for destination j is rounded
+    with the random bits of member r * world + j (dgpu_float_stochastic_compress), so the ranks draw independent bits and
+    their errors average out in the sum.  THE SEED MUST BE THE SAME ON EVERY RANK for the result to be a pure function of
+    the inputs and the seed.  A codec with compress_cast_stochastic(tensors, dtype, seed, first_member) rounds in the
+    compressor (GpuFloatCodec: in its two kernels); any other codec gets dietgpu_amd.rounding.stochastic_round_ into a
+    16-bit scratch and its `compress`, with the same bits.  wire_seed without wire_dtype (nothing is rounded here), with
+    a residual (feedback and stochastic rounding are alternatives) or with norm=True raises RuntimeError."""
     codec = codec or GpuFloatCodec()
     _check_wire("compressed_reduce_scatter", tensor, codec, raw_local, wire_dtype, residual)
+    _check_wire_seed("compressed_reduce_scatter", tensor, wire_dtype, wire_seed, residual, norm)
     world = dist.get_world_size()
     me = dist.get_rank()
     factor = _reduce_factor(op, scale, world)
@@ -571,7 +630,7 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
                 _norm_by_torch(pair, shard)
             _norm_stats(stats, pair)
         return shard, stats
-    shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec, False, wire_dtype, residual, residual_fresh)
+    shard_words, recv, all_sizes, width = _exchange_shard_rows(tensor, codec, False, wire_dtype, residual, residual_fresh, wire_seed)
     shard = torch.empty((shard_words,), dtype=torch.float32, device=tensor.device)
     has_reduce = callable(getattr(codec, "decompress_reduce", None))
     if not (has_reduce and world <= _MAX_REDUCE_SOURCES) and not callable(getattr(codec, "decompress_accumulate", None)):
@@ -603,7 +662,8 @@ def compressed_reduce_scatter(tensor, codec=None, raw_local=False, op="sum", sca
 
 
 def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=None, norm=False, clip_norm=None, wire_dtype=None,
-                          residual=None, residual_fresh=False, out=None, out_scale=None, out_accumulate=False, out_seed=None):
+                          residual=None, residual_fresh=False, out=None, out_scale=None, out_accumulate=False, out_seed=None,
+                          wire_seed=None):
     """All-reduce (sum) of a flat fp16 / bf16 tensor, moving compressed bytes both ways and summing in float32.
 
     Three steps: `compressed_reduce_scatter` (this rank's float32 shard of the sum), the codec's `compress_cast` of that
@@ -648,7 +708,7 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
     wire_dtype, residual, residual_fresh: as in compressed_reduce_scatter -- a float32 `tensor` whose shards travel as
     archives of wire_dtype, with error feedback on that first rounding when a residual is given.  The call then returns
     the sum in wire_dtype.  Its second rounding -- of the float32 sum, before the all-gather -- carries NO feedback: it is
-    the same on every rank and would need a residual per shard of the sum.
+    the same on every rank and would need a residual per shard of the sum (wire_seed, below, covers it).
 
     out (a flat contiguous float32 tensor of the tensor's length on its device; for 16-bit tensors and for float32
     tensors with wire_dtype alike): the result is delivered in FLOAT32.  The final all-gather decodes every rank's shard
@@ -677,9 +737,23 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
     the same parameter bits, and different seeds let the replicas drift apart.  A codec with `decompress_update` makes one
     call per source rank (GpuFloatCodec: in the decode kernel); any other codec is decoded into a float32 scratch and
     takes the add and the rounding from torch (dietgpu_amd.rounding), with the same bits.  out_seed with a float32 `out`
-    is an error, and so is a 16-bit `out` without out_seed; `out is tensor` follows the rules above."""
+    is an error, and so is a 16-bit `out` without out_seed; `out is tensor` follows the rules above.
+
+    wire_seed (an int in [0, 2^64), or a 1-element int64 tensor on the device, never read by the host; THE SAME ON EVERY
+    RANK): every rounding on the sending side is STOCHASTIC instead of to nearest.  The first -- of a float32 tensor's
+    shards to wire_dtype -- as in compressed_reduce_scatter, member r * world + j for source rank r and destination j.
+    The second -- of the float32 sum of shard `me` before the all-gather, the one that carries no feedback -- with the
+    random bits of member world * world + me; for a 16-bit tensor without wire_dtype it is the only rounding.  The call
+    takes the three-step path: the reduce-scatter, the codec's compress_cast_stochastic of the shard (any other codec:
+    dietgpu_amd.rounding.stochastic_round_ into a 16-bit scratch and its `compress`, the same bits), the gather; the fused
+    reduce-compress call rounds to nearest and is not used.  The result is a pure function of the inputs and the seed,
+    bit-identical on every rank.  raw_local (for 16-bit tensors), op, scale, out and out_seed compose as without it.
+    wire_seed with a residual, norm=True or clip_norm raises RuntimeError: feedback and stochastic rounding are
+    alternatives, and the statistics must describe the archive's words, which on this path only a second pass could
+    give.  Without wire_seed every codec call is what it was."""
     codec = codec or GpuFloatCodec()
     _check_wire("compressed_all_reduce", tensor, codec, raw_local, wire_dtype, residual)
+    _check_wire_seed("compressed_all_reduce", tensor, wire_dtype, wire_seed, residual, norm, clip_norm, needs_wire_dtype=False)
     out_dtype = wire_dtype if wire_dtype is not None else tensor.dtype
     if out_dtype not in _WIRE_DTYPES:
         raise RuntimeError("compressed_all_reduce: the tensor must be float16 or bfloat16 (float32: give wire_dtype)")
@@ -725,6 +799,8 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
     factor = _reduce_factor(op, scale, world)
     one_call = callable(getattr(codec, "decompress_reduce_compress", None)) and world <= _MAX_REDUCE_SOURCES
     mixed = one_call and raw_local and callable(getattr(codec, "decompress_reduce_compress_mixed", None))
+    if wire_seed is not None:
+        one_call = False  # (the fused reduce-compress kernel rounds to nearest)
     if one_call:
         reduce_compress = codec.decompress_reduce_compress_mixed if mixed else codec.decompress_reduce_compress
         one_call = factor is None or _takes_scale(reduce_compress)
@@ -745,10 +821,15 @@ def compressed_all_reduce(tensor, codec=None, raw_local=False, op="sum", scale=N
         pair = _norm_pair(tensor.device) if norm else None
         if wire_dtype is None:
             shard, rs = compressed_reduce_scatter(tensor, codec, raw_local, scale=factor)
+        elif wire_seed is not None:
+            shard, rs = compressed_reduce_scatter(tensor, codec, raw_local, scale=factor, wire_dtype=wire_dtype, wire_seed=wire_seed)
         else:
             shard, rs = compressed_reduce_scatter(tensor, codec, raw_local, scale=factor, wire_dtype=wire_dtype, residual=residual,
                                                   residual_fresh=residual_fresh)
-        comp, sizes = codec.compress_cast([shard], out_dtype)
+        if wire_seed is not None:
+            comp, sizes = _compress_stochastic(codec, [shard], out_dtype, wire_seed, world * world + dist.get_rank())
+        else:
+            comp, sizes = codec.compress_cast([shard], out_dtype)
     gathered_bytes = shard.numel() * (torch.finfo(out_dtype).bits // 8)
     if out is None:
         out = torch.empty(tensor.shape, dtype=out_dtype, device=tensor.device)

@@ -415,6 +415,50 @@ def compress_data_feedback(ts_in, ts_residual, dtype, fresh=False, temp_mem=None
     return comp, sizes, int(used.value)
 
 
+# ---------------------------------------------------- stochastic cast-compress
+# (no reference op: dgpu_float_stochastic_compress, include/dietgpu_amd.h)
+def compress_data_stochastic(ts_in, dtype, seed, first_member=0, out_compressed=None, out_compressed_sizes=None,
+                             prob_bits=K_DEFAULT_PRECISION):
+    """compress_data_cast whose every rounding is STOCHASTIC: word k of float32 tensor i becomes its neighbour in `dtype`
+    toward zero or the next one away from zero, the latter with probability remainder / unit -- unbiased, where round to
+    nearest drops every component below half a unit the same way at every step and on every rank, and without the
+    float32 residual of compress_data_feedback.  The archive is byte for byte what `compress_data(True, ...)` writes for
+    `rounding.stochastic_round_` of the tensor with the random bits of (seed, first_member + i, k): an ordinary archive
+    -> (comp [B, maxSize] u8, sizes [B] i32).  ts_in is not modified; no temp memory is passed (the call's temporaries
+    are the stream's own); no checksum.
+
+    The random bits are a pure function of (seed, first_member + i, k): the same tensors with the same seed give the
+    same archives whatever the kernel geometry.  `seed`: an int in [0, 2^64), or a 1-element int64 CUDA tensor whose bits
+    are the seed, read by the kernels when they run and never by the host -- a captured call advances the rounding by
+    `seed.add_(1)` between replays (never while the call runs: both of its kernels read the word)."""
+    _check(len(ts_in) > 0)
+    _check(dtype in (torch.float16, torch.bfloat16), "dtype (of the archives) must be float16 or bfloat16")
+    host_seed, dev_seed = _seed_arg(seed)
+    _check(isinstance(first_member, int) and not isinstance(first_member, bool) and 0 <= first_member < (1 << 32),
+           "first_member must be an int in [0, 2^32)")
+    for t in ts_in:
+        _check(t.dtype == torch.float32, "the inputs of a stochastic cast call must be float32")
+    _check(ts_in[0].is_cuda, "tensors must be on the GPU")
+    ft = _DTYPE_TO_FT[dtype]
+    dev = ts_in[0].get_device()
+    _check(dev_seed is None or dev_seed.get_device() == dev, "a tensor seed must be on the tensors' GPU")
+    for t in ts_in:
+        _check(t.is_cuda and t.is_contiguous() and t.get_device() == dev)
+    op = _amd_op(prob_bits, "compress_data_stochastic")
+    if op is not None:
+        return op(ts_in, ft, host_seed, dev_seed, first_member, out_compressed, out_compressed_sizes)
+    _, mx = _total_and_max(ts_in)
+    rows, cols = len(ts_in), _guarded(int(lib().dgpu_float_max_compressed_size(ft, mx)), mx)
+    with torch.cuda.device(dev):
+        comp, sizes = _validate_out(out_compressed, out_compressed_sizes, rows, cols, dev, ts_in[0].device)
+        row = comp.size(1)
+        out_ptrs = (C.c_void_p * rows)(*[comp.data_ptr() + i * row for i in range(rows)])
+        check(lib().dgpu_float_stochastic_compress(
+            ft, prob_bits, rows, _ptr_array(ts_in), _u32_array([t.numel() for t in ts_in]), host_seed & ((1 << 64) - 1),
+            _ptr(dev_seed), first_member, out_ptrs, _ptr(sizes), _stream()))
+    return comp, sizes
+
+
 # ------------------------------------------------------- rolling-table compress
 # (no reference op: dgpu_float_rolling_compress, include/dietgpu_amd.h)
 def _validate_counts(counts, rows, dev, name):

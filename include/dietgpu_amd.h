@@ -73,7 +73,8 @@ const char* dgpu_version(void);
  * dgpu_float_reduce_compress_mixed, dgpu_float_decode_reduce_scaled, dgpu_float_reduce_compress_scaled,
  * dgpu_float_reduce_norm_temp_bytes, dgpu_float_decode_reduce_norm, dgpu_float_reduce_compress_norm and
  * dgpu_float_decode_scaled were added at version 8, dgpu_float_feedback_compress and
- * dgpu_float_decode_accumulate_scaled after them, dgpu_float_decode_update after those). */
+ * dgpu_float_decode_accumulate_scaled after them, dgpu_float_decode_update after those,
+ * dgpu_float_stochastic_compress after dgpu_float_decode_update). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -534,6 +535,42 @@ int dgpu_float_feedback_compress(
     uint32_t numInBatch, const void* const* in /* float32 */, const uint32_t* inSize /* words */,
     const void* const* residualIn /* float32, [numInBatch]; the ARRAY may be NULL: no residual yet */,
     void* const* residualOut /* float32, [numInBatch], required */,
+    void* const* out, uint32_t* outSize_dev, void* stream);
+
+/* ---- stochastic cast-compress (no upstream equivalent) ----------------------------------
+ * dgpu_float_cast_compress whose every rounding is STOCHASTIC: the sender of a compressed exchange of float32 gradients
+ * puts an UNBIASED 16-bit word on the wire without keeping a residual -- what round-to-nearest drops every step, and
+ * drops the same way on every rank, is here kept in expectation.  The histogram pass and the encoder round every word in
+ * registers and arrive at the same word, because the random bits are a pure function of (seed, member, word index).
+ *   - out[i] / outSize_dev[i] are byte for byte what dgpu_float_compress(useChecksum = 0) writes for the 16-bit tensor
+ *     q[k] = sround_T(bits(x[k]), r16(S, firstMember + i, k)), k the word's index within element i, with sround_T and
+ *     r16 exactly as stated under dgpu_float_decode_update, S = seed_dev ? *seed_dev : seed and firstMember + i taken
+ *     modulo 2^32.  The same (S, member, k) draws the same bits in both calls.
+ *   - So, as there: a value that T represents never moves; an infinity stays an infinity; a NaN becomes the canonical
+ *     quiet NaN with its sign; a finite value beyond T's largest can round to infinity.  The archive is an ordinary
+ *     one that every decoder of this header reads.  The result does not depend on the kernel geometry, the dispatch
+ *     form, the dgpu_debug_set_* knobs or the alignment of in[i]; firstMember lets a batch split over several calls
+ *     draw the bits of the whole batch.  `in` is never written.
+ *   - seed_dev != NULL points at DEVICE memory, 8-byte aligned, of one uint64_t.  The kernels read it when they run and
+ *     the host never reads it.  BOTH kernels of the call read it, so it must not be written between them: a writer
+ *     enqueued earlier on the same stream is fine, one on another stream must be ordered before or after the whole
+ *     call.  A captured call follows the word at each replay.  seed_dev == NULL: the host `seed`.
+ *   - floatType is the type of the ARCHIVE: DGPU_FLOAT16 or DGPU_BFLOAT16 -- DGPU_FLOAT32 is rejected; in[i] 4-byte
+ *     aligned, out[i] 16-byte aligned with room for dgpu_float_max_compressed_size(floatType, inSize[i]), probBits
+ *     9 / 10 / 11, numInBatch <= 65535, inSize[i] (words) within the size guard of dgpu_float_compress, no array null
+ *     when numInBatch > 0, seed_dev 8-byte aligned: DGPU_ERR_INVALID_ARGUMENT with a dgpu_last_error() text otherwise,
+ *     before anything is enqueued.  An empty batch returns 0.  There is no checksum, for dgpu_float_cast_compress's
+ *     reason.
+ *   - The call has no temp-memory parameters: its temporaries (partial histograms, tables, descriptors, claim words,
+ *     spill slots) come from the stream's library-owned slab (dgpu_release_stream_state).  Nothing synchronises.
+ *   - The host routes are dgpu_float_cast_compress's, and the call is planned as that call: stride detection,
+ *     parameter cache (the seed, seed_dev and firstMember are kernel arguments, not part of the resident block: calls
+ *     that differ only in them share it), work lists, size classes, both dispatch forms; capturable into a HIP graph
+ *     after one identical warm call; single-block elements run on the 2-block tiles. */
+int dgpu_float_stochastic_compress(
+    uint32_t floatType /* of the ARCHIVE: DGPU_FLOAT16 or DGPU_BFLOAT16 */, int probBits,
+    uint32_t numInBatch, const void* const* in /* float32 */, const uint32_t* inSize /* words */,
+    uint64_t seed, const uint64_t* seed_dev /* nullable */, uint32_t firstMember,
     void* const* out, uint32_t* outSize_dev, void* stream);
 
 /* ---- rolling-table compress (no upstream equivalent) ------------------------------------

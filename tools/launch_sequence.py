@@ -12,7 +12,8 @@ dispatch left to the policy, forced persistent and forced to the hardware; ordin
 classes (1 large + many small) and one ragged batch; a caller-supplied histogram; ranged decodes on 16-block and 4-block
 tiles and of nothing but empty requests; decode-accumulate as a rectangle and from a list; cast-compress as a rectangle,
 ragged and split into classes that hold single-block members; the reduce family (REDUCE_SHAPES, reduce_family below) on
-the ctypes route and on the torch route.  The digest is over the lines (kernel name with its
+the ctypes route and on the torch route; stochastic cast-compress on both routes, last (stochastic_compress below: the
+lines of the calls before it do not move).  The digest is over the lines (kernel name with its
 template arguments, grid, workgroup size, LDS bytes) in launch order and, with --temp, the temp bytes every call of the
 list reported (tempUsed), in call order."""
 import argparse
@@ -147,6 +148,7 @@ def main(temp_out):
         used("decompress", dg.decompress_data(True, rows_of(comp, sizes), outs, False, prob_bits=10))
         assert all(torch.equal(o.view(torch.int16), t.to(torch.bfloat16).view(torch.int16)) for o, t in zip(outs, ts)), "cast-compress mismatch"
     reduce_family(dg, torch, tensors, rows_of, used)
+    stochastic_compress(dg, torch, tensors, rows_of)
     if temp_out:
         with open(temp_out, "w") as f:
             f.write("\n".join(temp_lines) + "\n")
@@ -222,6 +224,29 @@ def reduce_family(dg, torch, tensors, rows_of, used):
         ts, rows = sources(torch.bfloat16, REDUCE_SHAPES["4block"], 11)
         for compress in (False, True):
             reduce_calls(route, torch.bfloat16, "4block", ts, rows, 11, compress)
+    dg.ops.prefer_torch_ops(False)
+
+
+def stochastic_compress(dg, torch, tensors, rows_of):
+    """Stochastic cast-compress on both routes, after everything else (the lines of the calls above do not move, and the
+    call reports no temp bytes): the shapes of the cast-compress calls, bf16 and fp16, a host seed and a device seed.  The
+    archives decode to the words dietgpu_amd.rounding gives."""
+    from dietgpu_amd import rounding
+
+    dev = torch.device("cuda:0")
+    held = torch.tensor([11], dtype=torch.int64, device=dev)
+    for route in (False, True):
+        dg.ops.prefer_torch_ops(route)
+        for dtype in (torch.bfloat16, torch.float16):
+            for words in ([100000] * 16, [64 * 1024 + 15000 * i for i in range(64)], [2 * 1024 * 1024] + [1000 + 37 * i for i in range(300)]):
+                ts = tensors(torch.float32, words)
+                for seed in (11, held):
+                    comp, sizes = dg.compress_data_stochastic(ts, dtype, seed, 5, prob_bits=10)
+                outs = [torch.empty([n], dtype=dtype, device=dev) for n in words]
+                dg.decompress_data(True, rows_of(comp, sizes), outs, False, prob_bits=10)
+                for i in (0, len(ts) - 1):
+                    want = rounding.stochastic_round_(torch.empty_like(outs[i]), ts[i], 11, 5 + i)
+                    assert torch.equal(outs[i].view(torch.int16), want.view(torch.int16)), "stochastic cast-compress mismatch"
     dg.ops.prefer_torch_ops(False)
 
 
