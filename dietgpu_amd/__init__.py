@@ -11,6 +11,7 @@ from ._lib import DietGpuError, EXPORTED_SYMBOLS, lib  # noqa: F401
 from .ops import (  # noqa: F401
     compress_data,
     compress_data_cast,
+    compress_data_delta,
     compress_data_feedback,
     compress_data_rolling,
     compress_data_simple,
@@ -19,6 +20,7 @@ from .ops import (  # noqa: F401
     block_cover,
     decompress_data,
     decompress_data_accumulate,
+    decompress_data_delta,
     decompress_data_range,
     decompress_data_scaled,
     decompress_data_reduce,

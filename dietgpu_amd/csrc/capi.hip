@@ -728,7 +728,7 @@ uint32_t maxCompressedSizeHost(uint32_t bytes) {
 bool encodableSize(uint32_t symbols) { return symbols <= kMaxEncodableBytes; }
 
 // One call's batch as its entry point describes it: HOST arrays of device pointers and sizes (packed and uploaded as
-// [in ptrs][out ptrs][sizes][inBytes][work][residual ptrs], the block the parameter cache hashes) or, when `strided`, two
+// [in ptrs][out ptrs][sizes][inBytes][work][residual ptrs][base ptrs], the block the parameter cache hashes) or, when `strided`, two
 // stride views.
 struct Batch {
   uint32_t n = 0;  // elements
@@ -742,6 +742,8 @@ struct Batch {
   uint32_t maxSize = 0;           // the largest size / capacity
   // dgpu_float_feedback_compress: the residual that is added (empty: none yet) and the one that is stored, per element
   std::vector<uint64_t> resInPtrs, resOutPtrs;
+  // dgpu_ans_delta_encode / dgpu_ans_delta_decode: the base of every element (empty: no such side)
+  std::vector<uint64_t> basePtrs;
 };
 
 // One side of a batch as an entry point receives it: a HOST array of device pointers, or (ptrs == nullptr) a base and
@@ -830,13 +832,15 @@ struct DeviceBatch {
   const uint32_t* inBytes = nullptr;
   const uint32_t* work = nullptr;
   BatchView resIn{}, resOut{};  // feedback calls (all zero: no such side)
+  BatchView base{};             // delta calls (all zero: no such side)
   ParamLease lease;
 };
 
 int uploadParams(const Batch& b, bool sizesOnOut, StreamLease& stream, DeviceBatch* d) {
   const size_t outAt = b.inPtrs.size() * 8, sizesAt = outAt + b.outPtrs.size() * 8, inBytesAt = sizesAt + alignUp(b.sizes.size() * 4, 8),
                workAt = inBytesAt + alignUp(b.inBytes.size() * 4, 8), resInAt = workAt + alignUp(b.work.size() * 4, 8),
-               resOutAt = resInAt + b.resInPtrs.size() * 8, bytes = resOutAt + b.resOutPtrs.size() * 8;
+               resOutAt = resInAt + b.resInPtrs.size() * 8, baseAt = resOutAt + b.resOutPtrs.size() * 8,
+               bytes = baseAt + b.basePtrs.size() * 8;
   if (bytes == 0) return DGPU_OK;
   static thread_local std::vector<uint8_t> block;
   block.assign(bytes, 0);
@@ -848,6 +852,7 @@ int uploadParams(const Batch& b, bool sizesOnOut, StreamLease& stream, DeviceBat
   if (!b.work.empty()) memcpy(h + workAt, b.work.data(), b.work.size() * 4);
   if (!b.resInPtrs.empty()) memcpy(h + resInAt, b.resInPtrs.data(), b.resInPtrs.size() * 8);
   if (!b.resOutPtrs.empty()) memcpy(h + resOutAt, b.resOutPtrs.data(), b.resOutPtrs.size() * 8);
+  if (!b.basePtrs.empty()) memcpy(h + baseAt, b.basePtrs.data(), b.basePtrs.size() * 8);
   ParamCache::Entry* entry = nullptr;
   bool miss = false;
   const bool capturing = stream.capturing();
@@ -864,6 +869,7 @@ int uploadParams(const Batch& b, bool sizesOnOut, StreamLease& stream, DeviceBat
   d->work = (const uint32_t*)at(workAt, !b.work.empty());
   if (!b.resInPtrs.empty()) d->resIn = viewPointers((const uint64_t*)at(resInAt, true), nullptr, 0);
   if (!b.resOutPtrs.empty()) d->resOut = viewPointers((const uint64_t*)at(resOutAt, true), nullptr, 0);
+  if (!b.basePtrs.empty()) d->base = viewPointers((const uint64_t*)at(baseAt, true), nullptr, 0);
   return DGPU_OK;
 }
 
@@ -892,7 +898,14 @@ bool asStrideViews(const Batch& b, bool sizesOnOut, BatchView* in, BatchView* ou
   *out = viewStride((const void*)(uintptr_t)b.outPtrs[0], outStride, sizesOnOut ? u : 0u);
   return true;
 }
-// ... and the residual sides of a feedback call, which must be progressions too
+// ... and the residual sides of a feedback call and the base side of a delta call, which must be progressions too
+bool baseStrideView(const Batch& b, BatchView* base) {
+  uint64_t stride = 0;
+  if (b.basePtrs.empty()) return true;
+  if (!progression(b.basePtrs, &stride)) return false;
+  *base = viewStride((const void*)(uintptr_t)b.basePtrs[0], stride, 0u);
+  return true;
+}
 bool residualStrideViews(const Batch& b, BatchView* resIn, BatchView* resOut) {
   uint64_t inStride = 0, outStride = 0;
   if (!b.resInPtrs.empty() && !progression(b.resInPtrs, &inStride)) return false;
@@ -913,8 +926,8 @@ int resolveBatch(Batch& b, bool sizesOnOut, StreamLease& stream, DeviceBatch* d,
     d->out = b.out;
     return DGPU_OK;
   }
-  if (asStrideViews(b, sizesOnOut, &d->in, &d->out) && residualStrideViews(b, &d->resIn, &d->resOut)) return DGPU_OK;
-  d->resIn = d->resOut = BatchView{};
+  if (asStrideViews(b, sizesOnOut, &d->in, &d->out) && residualStrideViews(b, &d->resIn, &d->resOut) && baseStrideView(b, &d->base)) return DGPU_OK;
+  d->resIn = d->resOut = d->base = BatchView{};
   planWork();
   return uploadParams(b, sizesOnOut, stream, d);
 }
@@ -1088,7 +1101,7 @@ int encodeCommon(
     uint32_t* histAcc_dev = nullptr /* the histogram in the stream's zero-at-rest counters instead of hist_dev (reduce-compress):
                                        the normalisation reads them and puts them back to zero */,
     const RollingCounts& rolling = RollingCounts{},
-    const DeviceBatch* residual = nullptr /* feedback source: its resIn / resOut */,
+    const DeviceBatch* residual = nullptr /* feedback source: its resIn / resOut; delta source: its base */,
     const StochasticSeed& sr = StochasticSeed{} /* stochastic source: handed to both launches */) {
   // (kCountingSource is the planner's: from here on the source is what the kernels are instantiated for)
   sourceType &= ~kCountingSource;
@@ -1251,6 +1264,7 @@ int encodeCommon(
     fuse.seed = sr.seed;
     fuse.seedPtr = sr.seed_dev;
     fuse.firstMember = sr.firstMember;
+    fuse.base = residual ? residual->base : BatchView{};
     // bins with 32 lane slots unless a workgroup sees too little data to pay for zeroing / folding them
     const bool smallBins = histList ? listedHistPartBytes <= 64u * 1024u : (uint64_t)maxSize * wordBytes / grid.x <= 64u * 1024u;
     rc = launchVariant(histogramVariant(sourceType, smallBins, histogramLoadsNonTemporal(floatType)), grid, stream, in, histTemp, 1u, fuse);
@@ -1295,6 +1309,7 @@ int encodeCommon(
     e.seed = sr.seed;
     e.seedPtr = sr.seed_dev;
     e.firstMember = sr.firstMember;
+    e.base = residual ? residual->base : BatchView{};
     int rc = launchVariant(enc, dim3(grid), stream, e);
     if (rc) return rc;
   }
@@ -1315,7 +1330,7 @@ int encodeBatch(
   TempArena arena(temp_dev, tempBytes, streamLease);
   DeviceBatch d;
   // (a feedback call, and a stochastic one, is planned as the cast call it extends: same geometry, same lists, same
-  // cached plan)
+  // cached plan; a delta call keeps its flag: the raw-byte plan without single-block kernels)
   const uint32_t planType = ft & ~(kFeedbackSource | kStochasticSource);
   std::vector<LaunchGroup> groups{encodeRectangle(b.maxSize, planType)};
   int rc = resolveBatch(b, false, streamLease, &d, [&] { planEncodeCall(planPolicy(), b.sizes, planType, b.maxSize, histogram_dev != nullptr, &groups, &b.work); });
@@ -1325,7 +1340,7 @@ int encodeBatch(
   EncodeShared shared;
   for (const LaunchGroup& g : groups) {
     rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, g, d.work, shared, histogram_dev, outSize_dev, outCapacity, nullptr, rolling,
-                      encIsFeedback(ft) ? &d : nullptr, sr);
+                      (encIsFeedback(ft) || encIsDelta(ft)) ? &d : nullptr, sr);
     if (rc) break;
   }
   if (tempUsed) *tempUsed = arena.requested();
@@ -2519,6 +2534,55 @@ int dgpu_float_stochastic_compress(
   return floatCompressImpl(nullptr, 0, nullptr, floatType, probBits, 0, b, outSize_dev, (hipStream_t)stream, true, RollingCounts{}, false, &sr);
 }
 
+// ---- XOR-delta archives (no upstream equivalent) ----------------------------------------
+// Raw-byte ANS archives of in ^ base and their decode into out = decoded ^ base (kernels_encode.h,
+// ChunkSource<kDeltaSource>; kernels_stats.h, k_histogram's delta form; kernels_decode.h, DeltaSink): the raw pointer
+// calls with a source flag / a decode form and one more pointer array in the batch.  Temporaries come from the stream's slab.
+int dgpu_ans_delta_encode(
+    int probBits, uint32_t numInBatch, const void* const* in, const void* const* base, const uint32_t* inSize, void* const* out,
+    uint32_t* outSize_dev, void* stream) {
+  DGPU_REQUIRE(validProbBits(probBits), "probBits must be 9, 10 or 11");
+  DGPU_REQUIRE(numInBatch <= 65535u, "numInBatch must be <= 65535");
+  DGPU_REQUIRE(numInBatch == 0 || (in && base && inSize && out), "delta encode: null array with numInBatch > 0");
+  for (uint32_t i = 0; i < numInBatch; ++i) {
+    DGPU_REQUIRE(encodableSize(inSize[i]), "input larger than 1717538816 bytes: its maximum compressed size exceeds INT32_MAX (GpuANSEncode.cu:22)");
+  }
+  Batch b;
+  int rc = pointerBatch(&b, numInBatch, ptrSide(in, DGPU_ANS_REQUIRED_ALIGNMENT, kMsgAnsIn), ptrSide(out, 16, kMsgCompOut), inSize);
+  if (!rc) rc = sideAddresses(ptrSide(base, DGPU_ANS_REQUIRED_ALIGNMENT, "delta encode: base must be 4-byte aligned"), numInBatch, &b.basePtrs);
+  if (rc) return rc;
+  if (numInBatch == 0) return DGPU_OK;
+  return encodeBatch(nullptr, 0, nullptr, kDeltaSource, probBits, 0, b, nullptr, outSize_dev, (hipStream_t)stream);
+}
+
+int dgpu_ans_delta_decode(
+    int probBits, uint32_t numInBatch, const void* const* in, const uint32_t* inBytes, const void* const* base, void* const* out,
+    const uint32_t* outCapacity, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream) {
+  bool done;
+  int rc = checkCall(probBits, numInBatch, 0u, /*tempUsed*/ nullptr, /*errBatch*/ nullptr, &done);
+  if (done) return rc;
+  DGPU_REQUIRE(in && inBytes && base && out && outCapacity, "delta decode: null array with numInBatch > 0");
+  for (uint32_t i = 0; i < numInBatch; ++i) {
+    // in place (the same address) or apart: a lane reads the base byte it later overwrites, and no other
+    const uint64_t o = (uint64_t)(uintptr_t)out[i], s = (uint64_t)(uintptr_t)base[i], n = outCapacity[i];
+    DGPU_REQUIRE(o == s || o + n <= s || s + n <= o, "delta decode: out[i] must equal base[i] or not overlap it");
+  }
+  Batch b;
+  rc = pointerBatch(&b, numInBatch, ptrSide(in, 16, kMsgCompIn), ptrSide(out), outCapacity, inBytes);
+  if (!rc) rc = sideAddresses(ptrSide(base), numInBatch, &b.basePtrs);
+  if (rc) return rc;
+  // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
+  DGPU_REQUIRE(b.maxSize <= 0xfffff000u, "delta decode: outCapacity must not exceed 0xfffff000");
+  StreamLease streamLease((hipStream_t)stream);
+  DeviceBatch dev;
+  LaunchGroup group;
+  rc = planFloatDecode(b, streamLease, &dev, &group);  // (one geometry per call, 16- or 4-block tiles, as the other sink forms)
+  if (rc) return rc;
+  DecodeArgs d = decodeArgs(b, dev, 0u, outSuccess_dev, outSize_dev);
+  d.base = dev.base;
+  return launchDecode(d, group, dev.work, DecodeForm::kDelta, probBits, (hipStream_t)stream);
+}
+
 // ---- rolling-table compress (no upstream equivalent) ------------------------------------
 // The table of this call from the counts of the last one (countsIn_dev: no histogram pass), the counts of this call for
 // the next one (countsOut_dev: the counting encoder).  float16 / bfloat16 archives only: the float32 encoder has no
@@ -2602,6 +2666,7 @@ int dgpu_ans_histogram_batch_stride(
   noFuse.seed = 0;
   noFuse.seedPtr = nullptr;
   noFuse.firstMember = 0;
+  noFuse.base = BatchView{};
   const HistogramVariant hist = histogramVariant(0u, false, true);
   hipLaunchKernelGGL(hist.fn, grid, dim3(hist.threads), hist.ldsBytes, (hipStream_t)stream, in, histogram_dev, 0u, noFuse);
   DGPU_HIP(hipGetLastError());

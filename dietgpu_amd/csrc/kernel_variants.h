@@ -124,6 +124,25 @@ inline EncodeVariant encoderVariantCounting(int P, uint32_t ft, uint32_t tileBlo
   });
 }
 
+// The delta source (kDeltaSource: raw bytes XOR-ed with a base, ChunkSource<kDeltaSource>) exists as the raw-byte
+// encoder's tiles of 2, 4 and 8 blocks in both dispatch forms.  There is no delta form of the single-block kernels:
+// single-block members of a delta call run on 2-block tiles.
+inline EncodeVariant encoderVariantDelta(int P, uint32_t tileBlocks, bool hwDispatch) {
+  return withProbBits(P, [&](auto p) -> EncodeVariant {
+    constexpr int kP = decltype(p)::value;
+    auto tiled = [](auto tb, auto persistent) -> EncodeVariant {
+      constexpr uint32_t kTB = decltype(tb)::value;
+      constexpr bool kPersistent = decltype(persistent)::value;
+      return {k_ans_encode<kP, kDeltaSource, false, kTB, kPersistent, false>, encThreads(kTB), encLdsBytes(kP, false, kDeltaSource, kTB), "k_ans_encode_delta"};
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (tileBlocks <= kBlocksPerTinyTile) return hwDispatch ? tiled(UintC<kBlocksPerTinyTile>{}, no) : tiled(UintC<kBlocksPerTinyTile>{}, yes);
+    if (tileBlocks == kBlocksPerSmallTile) return hwDispatch ? tiled(UintC<kBlocksPerSmallTile>{}, no) : tiled(UintC<kBlocksPerSmallTile>{}, yes);
+    return hwDispatch ? tiled(UintC<kBlocksPerTile>{}, no) : tiled(UintC<kBlocksPerTile>{}, yes);
+  });
+}
+
 // The encoder of tiles of `tileBlocks` blocks; ft: the archive's float type, with kCastSource for a cast source.
 //   * single-block tiles go to k_ans_encode_pair: two ELEMENTS per wavefront, always one workgroup per pair;
 //   * hwDispatch: one workgroup per tile, dispatched by the hardware in ticket order, instead of persistent workgroups
@@ -132,6 +151,7 @@ inline EncodeVariant encoderVariantCounting(int P, uint32_t ft, uint32_t tileBlo
 //   * wide: the wide stage (kSpillStageWordsWide) exists for persistent 8-block bf16 / fp32 tiles only.
 inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, bool hwDispatch, bool wide) {
   if (encIsCast(ft)) return encoderVariantCast(P, encArchiveType(ft), tileBlocks, hwDispatch, ft & (kFeedbackSource | kStochasticSource));
+  if (encIsDelta(ft)) return encoderVariantDelta(P, tileBlocks, hwDispatch);
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> EncodeVariant {
     constexpr int kP = decltype(p)::value;
     constexpr uint32_t kFT = decltype(f)::value;
@@ -167,6 +187,7 @@ inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, boo
 constexpr uint32_t sameType(uint32_t ft) { return ft; }
 constexpr uint32_t floatsOnly(uint32_t ft) { return ft ? ft : kFloat32; }                         // raw bytes: the float32 form
 constexpr uint32_t halvesOnly(uint32_t ft) { return ft == kFloat16 ? kFloat16 : kBFloat16; }  // anything but fp16: the bf16 form
+constexpr uint32_t rawOnly(uint32_t) { return 0u; }                                            // raw bytes whatever the call says
 
 // Every decode form but the whole decode, once: X(form, kernel template, archive-type substitution, LDS bytes of the
 // instantiation <P, T, TB>).  The kernel's name is its profiling name.  Each exists for 16- and 4-block tiles; a new
@@ -188,6 +209,8 @@ constexpr uint32_t halvesOnly(uint32_t ft) { return ft == kFloat16 ? kFloat16 : 
 //     the store or the add; float types only, the LDS of kAccum;
 //   * kUpdate: kAccumScaled into 16-bit tensors of the archive's type, rounded stochastically (DecodeArgs::seedPtr /
 //     seed / firstMember); float16 and bfloat16 only, the LDS of kAccum;
+//   * kDelta: the whole bounded decode of raw bytes XOR-ed with DecodeArgs::base into the output, which may BE the base
+//     (DeltaSink); raw bytes only, with store buffers also on 16-block tiles (decXposeBytes, delta);
 //   * kRanged: decodes a block range of every element (a range of one or two blocks takes the 4-block form).
 #define DGPU_DECODE_FORMS(X)                                                                                           \
   X(kAccum, k_ans_decode_accum, floatsOnly, decLdsBytes(P, T, TB))                                                     \
@@ -202,6 +225,7 @@ constexpr uint32_t halvesOnly(uint32_t ft) { return ft == kFloat16 ? kFloat16 : 
   X(kWholeScaled, k_ans_decode_scaled, floatsOnly, decScaledLdsBytes(P, T, TB))                                        \
   X(kAccumScaled, k_ans_decode_accum_scaled, floatsOnly, decLdsBytes(P, T, TB))                                        \
   X(kUpdate, k_ans_decode_update, halvesOnly, decLdsBytes(P, T, TB))                                                   \
+  X(kDelta, k_ans_decode_delta, rawOnly, decLdsBytes(P, T, TB, true))                                                  \
   X(kRanged, k_ans_decode_range, sameType, decLdsBytes(P, T, TB))
 
 // The decoder of tiles of `tileBlocks` blocks.  A form of the list above takes the 4-block instantiation for tiles of
@@ -237,7 +261,7 @@ inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, Dec
 
 // The histogram pass: bins with kHistSlotsSmall or kHistSlotsLarge lane slots, non-temporal or ordinary input loads.
 // (ft with kCastSource: the cast form, which bins the exponent byte of the rounded word; with kFeedbackSource or
-// kStochasticSource as well: that source's rounding)
+// kStochasticSource as well: that source's rounding; kDeltaSource: the delta form of the raw-byte pass)
 inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTemporal) {
   auto pick = [&](auto f) -> HistogramVariant {
     constexpr uint32_t kFT = decltype(f)::value;
@@ -246,6 +270,8 @@ inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTe
       constexpr bool kNt = decltype(nt)::value;
       if constexpr (kFT == 0) {
         return {k_histogram<kS, kNt>, 256u, 0u, "k_histogram"};
+      } else if constexpr (kFT == kDeltaSource) {
+        return {k_histogram<kS, kNt, true>, 256u, 0u, "k_histogram_delta"};
       } else {
         return {k_float_histogram<kFT, kS, kNt>, 256u, 0u,
                 encIsStochastic(kFT) ? "k_float_histogram_stochastic"
@@ -257,6 +283,7 @@ inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTe
     if (nonTemporal) return smallBins ? of(small, std::true_type{}) : of(large, std::true_type{});
     return smallBins ? of(small, std::false_type{}) : of(large, std::false_type{});
   };
+  if (encIsDelta(ft)) return pick(UintC<kDeltaSource>{});
   if (encIsFeedback(ft)) {
     return encArchiveType(ft) == kFloat16 ? pick(UintC<kFloat16 | kCastSource | kFeedbackSource>{}) : pick(UintC<kBFloat16 | kCastSource | kFeedbackSource>{});
   }

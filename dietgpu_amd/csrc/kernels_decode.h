@@ -90,6 +90,8 @@ struct DecodeArgs {
   uint32_t firstMember = 0;
   uint64_t seed = 0;
   const uint64_t* seedPtr = nullptr;
+  // k_ans_decode_delta only: the bytes member b's decoded bytes are XOR-ed with, base.ptr(b); may equal out.ptr(b)
+  BatchView base = BatchView{};
 };
 __device__ __forceinline__ uint64_t decodeInBytes(const DecodeArgs& a, uint32_t b) {
   return a.inBytes ? (uint64_t)a.inBytes[b] : (a.uniformInBytes ? (uint64_t)a.uniformInBytes : ~0ull);
@@ -739,6 +741,39 @@ struct UpdateSink : RowSink<FT> {
 };
 
 // ---------------------------------------------------------------------------
+// Delta sink (k_ans_decode_delta; raw bytes): RowSink<0> whose every decoded byte is XOR-ed with the byte of a BASE at
+// the same offset before it is stored: out[k] = symbol[k] ^ base[k].  Staging and the shape of the stores are
+// RowSink<0>'s.  The base bytes travel where RowSink's non-compressed bytes travel (Pre / GroupPre):
+//   * wide path: prefetchGroup is ONE 8-byte load per lane and group, at the offset the lane's flushGroup stores its 8
+//     bytes to, requested two groups ahead (decodeBlock) -- or, for the top two groups, before the LUT build
+//     (decodePrefetch, DecodePreOf::nc); flushGroup XORs the two packed dwords and stores 8 bytes;
+//   * narrow path (the rows above the whole groups of a partial block; blocks without a whole group): prefetch is one
+//     base byte per lane and row, at the offset store() writes, one group ahead.
+// IN PLACE (out == base, the main use: the base becomes the new tensor) rests on ONE invariant of this sink: every byte
+// that is stored was formed from the base byte that the SAME lane loaded from the SAME offset earlier in its own program
+// order, and every offset is stored at most once per call.  prefetchGroup(g) covers exactly flushGroup(g)'s bytes,
+// prefetch(row) exactly store(row)'s; the rows of the narrow and the groups of the wide phase of a block are disjoint;
+// a block belongs to one half-wave of one workgroup.  Loads by lanes that never store -- an idle upper half that shadows
+// its lower half's block in the same instructions, a clamped group index at the bottom of the loop -- may see either
+// value: what they return is dropped.  The store depends on the load through its data, so no fence is needed.
+struct DeltaSink : RowSink<0> {
+  const uint8_t* base;  // the lane's byte of row 0 of its block, as `out`
+  __device__ __forceinline__ void initBase(const uint8_t* baseBytes, size_t first, uint32_t hl) { base = baseBytes + first + hl; }
+  typedef uint32_t Pre;
+  typedef uint2 GroupPre;
+  __device__ __forceinline__ uint32_t prefetch(uint32_t row) const { return base[row * 32u]; }
+  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, uint32_t r) const { out[row * 32u] = (uint8_t)((e0 >> 24) ^ r); }
+  __device__ __forceinline__ uint2 prefetchGroup(uint32_t g, uint32_t hl) const { return decLoad8(base - hl + g * 256u + hl * 8u); }
+  __device__ __forceinline__ void flushGroup(uint32_t xpose, uint32_t g, uint32_t hl, uint2 d) const {
+    typedef uint32_t u32x2l __attribute__((ext_vector_type(2)));
+    const u32x4w v = *(const LdsU4w*)(uintptr_t)(xpose + hl * 16u);
+    const uint32_t o0 = __builtin_amdgcn_perm(v.y, v.x, 0x07050301u) ^ d.x;  // {x.b1, x.b3, y.b1, y.b3}
+    const uint32_t o1 = __builtin_amdgcn_perm(v.w, v.z, 0x07050301u) ^ d.y;
+    *(u32x2l*)(out - hl + g * 256u + hl * 8u) = u32x2l{o0, o1};
+  }
+};
+
+// ---------------------------------------------------------------------------
 // Compressed-word ring: 4 chunks of 256 words (512 bytes) per block.  Chunk k of
 // the block's data lives in slot k & 3.  Words are consumed from the top of the
 // block downwards, at most 32 per row = 256 per 8-row group = one chunk per
@@ -760,9 +795,14 @@ __host__ __device__ constexpr uint32_t decThreads(uint32_t tileBlocks) { return 
 // workgroup per CU (40 KiB instead of 48: 8 waves per SIMD) is worth more to their row loop than the 8-byte
 // stores (256 x 1 MiB Zipf bytes decode 152.5 -> 145 us).  16-bit floats are HBM-bound with the wide stores, and
 // their narrow 2-byte non-temporal stores inflate the write traffic by 1.35 (docs/HISTORY.md section 4.2).
-__host__ __device__ constexpr uint32_t decXposeBytes(int P, uint32_t ft, uint32_t tileBlocks) {
+// `delta` (k_ans_decode_delta, DeltaSink): raw bytes WITH the buffers on 16-block tiles too.  The narrow path would add
+// a one-byte LOAD of the base per lane and row -- 128 loads per lane and block in 32-byte pieces, beside as many
+// one-byte stores -- to a form whose base is as many bytes as its output: it moves the memory traffic of the 16-bit
+// float decode (one more input stream of the output's size), which is the case the buffers were measured for.  48 KiB,
+// three workgroups per CU, ONE 8-byte load and ONE 8-byte store per lane and group.
+__host__ __device__ constexpr uint32_t decXposeBytes(int P, uint32_t ft, uint32_t tileBlocks, bool delta = false) {
   (void)P;
-  if (ft == 0 && tileBlocks >= 16u) return 0u;
+  if (ft == 0 && tileBlocks >= 16u && !delta) return 0u;
   return ft == kFloat32 ? 0u : 512u;
 }
 // COMPACT LUT entries, 4 bytes {sym:8 | x - cdf:12 | pdf:12} instead of 8 (two more VALU per row to unpack):
@@ -777,9 +817,11 @@ __host__ __device__ constexpr bool decCompactLut(int P, uint32_t tileBlocks) { r
 __host__ __device__ constexpr uint32_t decLutBytes(int P, uint32_t tileBlocks) {
   return decCompactLut(P, tileBlocks) ? (4u << P) : (8u << P);
 }
-__host__ __device__ constexpr uint32_t decLdsBytes(int P, uint32_t ft, uint32_t tileBlocks) {
-  return decLutBytes(P, tileBlocks) + tileBlocks * kRingBytes + tileBlocks * decXposeBytes(P, ft, tileBlocks);
+__host__ __device__ constexpr uint32_t decLdsBytes(int P, uint32_t ft, uint32_t tileBlocks, bool delta = false) {
+  return decLutBytes(P, tileBlocks) + tileBlocks * kRingBytes + tileBlocks * decXposeBytes(P, ft, tileBlocks, delta);
 }
+static_assert(decLdsBytes(10, 0u, 16u) == 40u * 1024u && decLdsBytes(10, 0u, 16u, true) == 48u * 1024u && 3u * decLdsBytes(11, 0u, 16u, true) <= 160u * 1024u,
+              "raw bytes on 16-block tiles: four workgroups per CU without store buffers, three with them (delta)");
 
 // kIdleUpper (full path only): the upper half of the wave has no block (the element's block count is odd, or
 // it has a single block): its lanes run the same straight-line code on don't-care data and only their
@@ -1088,28 +1130,38 @@ __device__ __forceinline__ void decodeBlock(
 // every tile included: a failing member keeps every bit of its tensor.  The seed (DecodeArgs::seedPtr, or the host's
 // DecodeArgs::seed) is requested with the factor, in the round trip of the header; the member's key follows from it in
 // scalar registers, once per tile.
+//
+// kDelta: the whole bounded decode of RAW bytes whose every byte is XOR-ed with the byte of DecodeArgs::base at the same
+// offset (DeltaSink): out = decoded ^ base, and out may BE base.  Checks, success and outSize are the whole decode's with
+// kAccum's addition: every tile checks all the element's block descriptors and no tile of a failing element stores -- in
+// place, a failing member keeps every bit of its base.  The base is read below the size the header states only, which
+// the capacity bounds.  Store buffers on every tile size (decXposeBytes, delta).
 // (kReduce: decodeReduceTile, below)
-enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats, kReduceNorm, kReduceNormStats, kWholeScaled, kAccumScaled, kUpdate };
+enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats, kReduceNorm, kReduceNormStats, kWholeScaled, kAccumScaled, kUpdate, kDelta };
 template <int P, uint32_t FT, uint32_t kTileBlocks, DecodeForm kForm>
 __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccumScaled = kForm == DecodeForm::kAccumScaled;
   constexpr bool kUpdate = kForm == DecodeForm::kUpdate;
   constexpr bool kAccum = kForm == DecodeForm::kAccum || kAccumScaled || kUpdate;      // the accumulating forms
   constexpr bool kScaledForm = kForm == DecodeForm::kWholeScaled || kAccumScaled || kUpdate;  // the forms with a factor
-  static_assert(kForm == DecodeForm::kWhole || kForm == DecodeForm::kRanged || kAccum || kScaledForm,
+  constexpr bool kDelta = kForm == DecodeForm::kDelta;
+  constexpr bool kAllVouch = kAccum || kDelta;  // every tile checks all the element's descriptors: a failing member stores nothing
+  static_assert(kForm == DecodeForm::kWhole || kForm == DecodeForm::kRanged || kAccum || kScaledForm || kDelta,
                 "decode-reduce has a body of its own: decodeReduceTile");
+  static_assert(!kDelta || FT == 0u, "delta decode: raw bytes only");
   static_assert(!(kAccum || kScaledForm) || FT != 0u, "accumulating and scaled decode: float archives only");
   static_assert(!kUpdate || FT == kFloat16 || FT == kBFloat16, "decode-update: 16-bit float archives only");
   using Sink = std::conditional_t<kUpdate, UpdateSink<kUpdate ? FT : kBFloat16>,
                                   std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32, 0u, false, false, kAccumScaled>,
-                                                     std::conditional_t<kScaledForm, ScaledSink<FT ? FT : kFloat32>, RowSink<FT>>>>;
+                                                     std::conditional_t<kScaledForm, ScaledSink<FT ? FT : kFloat32>,
+                                                                        std::conditional_t<kDelta, DeltaSink, RowSink<FT>>>>>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks);
   // the LUT-build scratch (cdf, pdf: 2 KiB, read while the LUT is stored) sits in the ring area
   static_assert(kTileBlocks * kRingBytes >= 2048u, "");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   // rings: 16 x 2 KiB at LDS offset 0 (2 KiB aligned), then the LUT, then the transposition buffers
   uint2* sLut = (uint2*)(smem + kTileBlocks * kRingBytes);
-  constexpr uint32_t kXpose = decXposeBytes(P, FT, kTileBlocks);
+  constexpr uint32_t kXpose = decXposeBytes(P, FT, kTileBlocks, kDelta);
 
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
@@ -1242,7 +1294,7 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   // tile 0 vouches for the whole element (kRanged: the whole range; it alone writes outSuccess); its loads are
   // issued here and checked after the LUT build
   bool allBlocksOk = true;
-  if constexpr (kAccum) {
+  if constexpr (kAllVouch) {
     // every tile vouches for the whole element (see above); the loads do not wait for each other
     for (uint32_t i = tid; i < endBlock; i += kDecThreads) allBlocksOk = blockOk(i, blockWords[i]) & allBlocksOk;
   } else if (tile == 0) {
@@ -1284,6 +1336,7 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   uint32_t sinkBlock = haveBlock ? block : (block & ~1u);
   if constexpr (kRanged) sinkBlock = haveBlock ? block : tileFirst + (hw & ~1u);
   sink.init(a.out.ptr(b), archive, floatSize, (size_t)sinkBlock * kBlockSize, hl);
+  if constexpr (kDelta) sink.initBase(a.base.ptr(b), (size_t)sinkBlock * kBlockSize, hl);
   if constexpr (kRanged) sink.out -= (size_t)rFirst * kBlockSize;  // the planes are the element's, the output is the range's
   // LDS address of the dynamic segment (0: this kernel has no static LDS); the
   // rings must be 2 KiB aligned for the and-or addressing in decodeBlock
@@ -1296,7 +1349,7 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   const bool noRing = wFirst <= kRingBytes / 2u && wSecond <= kRingBytes / 2u;
   // (the wide stores cover whole 8-row groups of words that exist; they take any word-aligned output element)
   // (kAccum: accumulators are float-aligned, the host checks it)
-  const bool wide = decXposeBytes(P, FT, kTileBlocks) != 0 && (kAccum || (((uintptr_t)a.out.ptr(b)) & (decOutWordBytes(FT) - 1u)) == 0);
+  const bool wide = kXpose != 0 && (kAccum || (((uintptr_t)a.out.ptr(b)) & (decOutWordBytes(FT) - 1u)) == 0);
   const bool fullPair = nFirst == kBlockSize && nSecond == kBlockSize;
   // one full block in the wave (odd block counts): fast path with an idle upper half
   const bool fullSingle = nFirst == kBlockSize && nSecond == 0u;
@@ -1354,7 +1407,7 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
       if (a.outSize) a.outSize[b] = kRanged ? rangeWords(total) : total;
     }
     if (!pdfOk || tileFirst >= endBlock) return;  // uniform
-    if constexpr (kAccum) {
+    if constexpr (kAllVouch) {
       if (!blocksOk) return;  // uniform
     }
     if constexpr (kScanLut) {
@@ -2070,6 +2123,14 @@ template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_update(DecodeArgs a) {
   static_assert(FT == kFloat16 || FT == kBFloat16, "decode-update: 16-bit float archives only");
   decodeTile<P, FT, kTileBlocks, DecodeForm::kUpdate>(a);
+}
+
+// Delta form: the whole decode of raw bytes XOR-ed with DecodeArgs::base into the output, which may be the base itself
+// (decodeTile, kDelta; DeltaSink).  Grid and order as k_ans_decode_accum; LDS decLdsBytes(P, 0, tiles, true).  Raw bytes only.
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_delta(DecodeArgs a) {
+  static_assert(FT == 0u, "delta decode: raw bytes only");
+  decodeTile<P, 0u, kTileBlocks, DecodeForm::kDelta>(a);
 }
 
 // Reducing form: grid and order as k_ans_decode_accum, DecodeArgs::numSources archives per accumulator (decodeReduceTile).

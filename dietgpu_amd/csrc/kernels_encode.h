@@ -86,7 +86,7 @@ __host__ __device__ constexpr uint32_t encSpillSlotWords(int P) { return roundUp
 // (Raw bytes keep the worst-case stage: a 1664-word stage with spill slots -- 4 workgroups per CU -- measured -2 %
 // for 43 MiB more temp memory, and nothing once the row stored under the ballot; docs/HISTORY.md section 5, "Config 2".)
 // (kCastSource, encIsCast and encArchiveType -- the SOURCE of an encoder / histogram instantiation -- are in plan_constants.h)
-__host__ __device__ constexpr uint32_t encSourceWordBytes(uint32_t ft) { return ft == 0u ? 1u : ((ft == kFloat32 || encIsCast(ft)) ? 4u : 2u); }
+__host__ __device__ constexpr uint32_t encSourceWordBytes(uint32_t ft) { return encArchiveType(ft) == 0u ? 1u : ((ft == kFloat32 || encIsCast(ft)) ? 4u : 2u); }
 
 __host__ __device__ constexpr uint32_t encStageCap(int P, bool spill, uint32_t ft, bool wide = false) {
   return spill ? (encArchiveType(ft) == kFloat16 ? kSpillStageWordsFp16 : (wide ? kSpillStageWordsWide : kSpillStageWords)) : encStageWords(P);
@@ -166,6 +166,7 @@ struct EncodeArgs {
   uint64_t seed;
   const uint64_t* seedPtr;
   uint32_t firstMember;
+  BatchView base;            // delta source only: the bytes element b is XOR-ed with, base.ptr(b); never written
 };
 
 struct TileShared {
@@ -282,6 +283,53 @@ struct ChunkSource<0> {  // raw bytes: the symbols are the input
     comp[0] = r.v.x; comp[1] = r.v.y; comp[2] = r.v.z; comp[3] = r.v.w;
   }
   __device__ __forceinline__ uint32_t wordAt(uint32_t i) const { return in[i]; }
+  __device__ __forceinline__ uint32_t splitAt(uint32_t, uint32_t w, bool) const { return w; }
+};
+
+// Delta source (raw bytes; dgpu_ans_delta_encode): the symbols are in[k] ^ base[k].  ChunkSource<0>'s chunk shape -- 16
+// rows, 16 symbols per lane -- with a second stream: TWO 16-byte loads in flight per lane and chunk, one of each stream
+// at the same offset into its element, XOR-ed where the chunk goes to the ring.  The two streams may lie differently
+// modulo 16: each load takes its own address as it is, and in the tail form each stream is bounded on its own by
+// loadSliceBounded (aligned windows for one, the shifted last 16 bytes for the other, as each one's base address
+// says), so no byte beyond either element is touched.  k_ans_encode takes the chunked paths only when BOTH streams pass
+// encVectorLoadsOk; otherwise the block runs the scalar path (wordAt), one byte of each stream per lane and row.
+// Neither stream is written.
+template <>
+struct ChunkSource<kDeltaSource> {
+  static constexpr uint32_t kRows = 16;
+  struct Raw { uint4 v, d; };
+  const uint8_t* in;    // this half's block
+  const uint8_t* base;  // ... of the base
+  __device__ __forceinline__ void init(const uint8_t* elemIn, uint8_t*, uint32_t, uint32_t block) {
+    in = elemIn + (size_t)block * kBlockSize;
+  }
+  __device__ __forceinline__ void initBase(const uint8_t* elemBase, uint32_t block) { base = elemBase + (size_t)block * kBlockSize; }
+  __device__ __forceinline__ Raw load(uint32_t c, uint32_t hl) const {
+    Raw r;
+    r.v = streamLoad<kNtEncLoads>(&((const uint4*)in)[c * 32u + hl]);
+    r.d = streamLoad<kNtEncLoads>(&((const uint4*)base)[c * 32u + hl]);
+    return r;
+  }
+  static __device__ __forceinline__ uint4 delta(const Raw& r) { return make_uint4(r.v.x ^ r.d.x, r.v.y ^ r.d.y, r.v.z ^ r.d.z, r.v.w ^ r.d.w); }
+  __device__ __forceinline__ void consume(const Raw& r, uint32_t, uint32_t hl, uint8_t* ring) const { *(uint4*)(ring + hl * 16u) = delta(r); }
+  // Tail forms: ChunkSource<0>'s, per stream.  What a part that straddles n holds beyond n differs between the two
+  // bounding forms (zero, or what the aligned window held); those symbols are never coded.
+  __device__ __forceinline__ Raw loadTail(uint32_t c, uint32_t hl, uint32_t n) const {
+    uint4 part[1];
+    Raw r;
+    loadSliceBounded<1>(in, c * 512u + hl * 16u, n, part);
+    r.v = part[0];
+    loadSliceBounded<1>(base, c * 512u + hl * 16u, n, part);
+    r.d = part[0];
+    return r;
+  }
+  __device__ __forceinline__ void consumeTail(const Raw& r, uint32_t c, uint32_t hl, uint8_t* ring, uint32_t) const { consume(r, c, hl, ring); }
+  static constexpr uint32_t kCompRegs = 4;
+  __device__ __forceinline__ void splitStore(const Raw& r, uint32_t, uint32_t, uint32_t (&comp)[kCompRegs]) const {
+    const uint4 x = delta(r);
+    comp[0] = x.x; comp[1] = x.y; comp[2] = x.z; comp[3] = x.w;
+  }
+  __device__ __forceinline__ uint32_t wordAt(uint32_t i) const { return (uint32_t)(in[i] ^ base[i]); }
   __device__ __forceinline__ uint32_t splitAt(uint32_t, uint32_t w, bool) const { return w; }
 };
 
@@ -815,7 +863,7 @@ struct ChunkSource<kBFloat16 | kCastSource | kStochasticSource> : ChunkSourceSto
 // positions in SGPRs (-2 VALU, +7 SALU: +8 %), a packed 8-byte table entry (half the LDS bytes, +3 VALU: +8 %),
 // table entries 4 rows ahead instead of 2 (+8 %), a hand-scheduled SDWA select (+5 %).
 template <uint32_t FT>
-constexpr bool encShiftUnderBallot() { return FT == 0u || encArchiveType(FT) == kBFloat16; }
+constexpr bool encShiftUnderBallot() { return encArchiveType(FT) == 0u || encArchiveType(FT) == kBFloat16; }
 // The incoming execution mask is saved and restored (s_and_saveexec), so a caller with inactive lanes keeps them
 // inactive; every caller in this library runs the full-block step with all 64 lanes active.
 __device__ __forceinline__ void stageWriteUnder(uint64_t vote, uint32_t addr, uint32_t state) {
@@ -1287,6 +1335,7 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
   static_assert(!encIsFeedback(FT) || (encIsCast(FT) && kSpill && !kWide && !kCount), "the feedback source extends the cast source; no counting form");
   static_assert(!encIsStochastic(FT) || (encIsCast(FT) && !encIsFeedback(FT) && kSpill && !kWide && !kCount),
                 "the stochastic source is a cast source; no counting and no feedback form");
+  static_assert(!encIsDelta(FT) || (FT == kDeltaSource && !kSpill && !kWide && !kCount), "the delta source is a raw-byte source; no counting form");
   static_assert(!kCount || (kSpill && kPersistent && !kWide && (encArchiveType(FT) == kFloat16 || encArchiveType(FT) == kBFloat16)),
                 "the counting form exists for persistent 16-bit float tiles");
   constexpr uint32_t kCountSlots = kCount ? encCountSlots(kTB) : 0u;
@@ -1403,7 +1452,7 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
       uint8_t* archive = a.out.ptr(b);
       uint8_t* ans = archive + ansOffsetInArchive(AT, size);
 
-      if (FT != 0 && tile == 0) {
+      if (AT != 0 && tile == 0) {
         // GpuFloatHeader (GpuFloatCompress.cuh:325-337) and the zero padding of the
         // non-comp plane(s) up to 16 bytes
         if (tid == 0) {
@@ -1438,7 +1487,9 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
       const uint32_t firstBlockOfWave = tile * kTB + wave * 2u;
       // (vector loads take any word-aligned address -- elements of a split tensor, rows of a matrix; an element below 16
       // bytes must be a 16-byte aligned window for the tail form's last load, see loadSliceBounded)
-      const bool aligned = encVectorLoadsOk<FT>(in, size);
+      bool aligned = encVectorLoadsOk<FT>(in, size);
+      // (delta source: each stream on its own; either one failing sends the block to the scalar path)
+      if constexpr (encIsDelta(FT)) aligned = aligned && encVectorLoadsOk<FT>(a.base.ptr(b), size);
       const bool waveFull = (uint64_t)(firstBlockOfWave + 2u) * kBlockSize <= (uint64_t)size && aligned;
       // ONE full block in the wave and no second one (odd block counts): the
       // lower half keeps the straight-line path; the upper half shadows it -- same block, same table, the same
@@ -1453,6 +1504,7 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
         const bool haveResidual = a.resIn.ptrs != nullptr || a.resIn.base != 0ull;  // (uniform)
         src.initResidual(haveResidual ? a.resIn.ptr(b) : nullptr, a.resOut.ptr(b), haveBlock ? block : (waveHalf ? firstBlockOfWave : 0u));
       }
+      if constexpr (encIsDelta(FT)) src.initBase(a.base.ptr(b), haveBlock ? block : (waveHalf ? firstBlockOfWave : 0u));
       // (the member's key, once per tile: consecutive tiles of a persistent workgroup belong to different elements)
       if constexpr (encIsStochastic(FT)) src.setKey(srMemberKey(a.seedPtr ? *a.seedPtr : a.seed, a.firstMember + b));
 
@@ -1511,7 +1563,7 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
         // pauses, as rounds 1-5 had it -- as a function with its pause bookkeeping it cost the raw-byte encoder 3 us of
         // 144 (profiles/r06_ab_raw_encoder_regression_u8.txt).  Many in flight: long pauses, and two levels for float
         // elements of more than 64 tiles (lookBackExclusive, lookBackTwoLevel).
-        const bool twoLevel = FT != 0u && a.groupWords != nullptr && numTiles > kLookbackGroup;  // (uniform)
+        const bool twoLevel = AT != 0u && a.groupWords != nullptr && numTiles > kLookbackGroup;  // (uniform)
         uint64_t* groupDesc = nullptr;
         uint32_t exclusive = 0;
         if (a.pollLong == 0u && !twoLevel) {
@@ -1533,7 +1585,7 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
             if (firstIncl < 64) break;
             base -= 64;
           }
-        } else if constexpr (FT != 0u) {
+        } else if constexpr (AT != 0u) {
           uint64_t* groupArrive = twoLevel ? a.groupWords + (size_t)b * a.groupsPerElement * (kGroupArriveStride + 1u) : nullptr;
           groupDesc = twoLevel ? groupArrive + (size_t)a.groupsPerElement * kGroupArriveStride : nullptr;
           exclusive = twoLevel ? lookBackTwoLevel(desc, groupArrive, groupDesc, tile, numTiles, aggregate, lane, failed, a.pollLong != 0u)
@@ -1580,7 +1632,7 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
         uint4* dst = (uint4*)(archive + dataOff);
         // 16-byte vectors of this block that still fit the caller's capacity (all of them under the reference's contract)
         // (a.capAtMax: the element's own maximum -- only a table that was not made from this data can reach it)
-        const uint64_t capacity = (FT != 0u && a.capAtMax) ? (uint64_t)encMaxArchiveBytes(AT, size) : (uint64_t)a.outCapacity;
+        const uint64_t capacity = (AT != 0u && a.capAtMax) ? (uint64_t)encMaxArchiveBytes(AT, size) : (uint64_t)a.outCapacity;
         const uint64_t room = capacity > dataOff ? (capacity - dataOff) / 16u : 0u;
         uint32_t fit = room > 0xffffffffull ? 0xffffffffu : (uint32_t)room;
         if (kSpill && spilled) {

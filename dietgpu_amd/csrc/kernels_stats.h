@@ -407,6 +407,7 @@ struct HistFuse {
   uint64_t seed;
   const uint64_t* seedPtr;
   uint32_t firstMember;
+  BatchView base;  // delta form of k_histogram only: the bytes every element is XOR-ed with before it is counted
 };
 
 // Which (element, part of how many) a histogram workgroup counts, and where its partial histogram goes.
@@ -602,7 +603,14 @@ __device__ __forceinline__ void histStore(uint32_t* __restrict__ hist, uint32_t 
   }
 }
 
-template <uint32_t S, bool kNt = true>
+// kDelta (the delta form, dgpu_ans_delta_encode): the bytes counted are in[k] ^ base[k] with base = fuse.base -- 16 bytes
+// of each stream per lane and step, eight loads in flight where the plain form has four, the XOR in registers.  The
+// vectors begin at the first 16-byte boundary of `in`; the vectors of `base` are the same offsets into ITS element and so
+// begin wherever base lies modulo 16 (global loads take any alignment).  Every form of the plain kernel -- partial
+// histograms, the atomic counters of one or two large elements, both lane-slot counts, both load policies, the fused
+// normalisation -- is a run-time path or a template parameter beside kDelta, so each exists in the delta form.  The pass
+// only reads.
+template <uint32_t S, bool kNt = true, bool kDelta = false>
 __global__ __launch_bounds__(256) void k_histogram(BatchView in, uint32_t* __restrict__ hist, uint32_t partial, HistFuse fuse) {
   __shared__ uint32_t bins[kNumSymbols * S];
   const uint32_t tid = threadIdx.x;
@@ -614,6 +622,8 @@ __global__ __launch_bounds__(256) void k_histogram(BatchView in, uint32_t* __res
   uint32_t* myBins = histMine<S>(bins, tid);
   const uint8_t* p = in.ptr(b);
   const uint32_t size = in.size(b);
+  [[maybe_unused]] const uint8_t* q = p;  // kDelta: the element's base
+  if constexpr (kDelta) q = fuse.base.ptr(b);
 
   // bytes before the first 16-byte boundary
   uint32_t head = (uint32_t)((16u - ((uintptr_t)p & 15u)) & 15u);
@@ -621,8 +631,18 @@ __global__ __launch_bounds__(256) void k_histogram(BatchView in, uint32_t* __res
   const uint32_t remaining = size - head;
   const uint32_t numVec = remaining / 16u;
   const uint4* pv = (const uint4*)(p + head);
+  [[maybe_unused]] const uint4* qv = (const uint4*)(q + head);
+  auto byteAt = [&](uint32_t i) -> uint32_t { return kDelta ? (uint32_t)(p[i] ^ q[i]) : (uint32_t)p[i]; };
+  auto vecAt = [&](uint32_t i) -> uint4 {
+    uint4 v = streamLoad<kNt>(&pv[i]);
+    if constexpr (kDelta) {
+      const uint4 d = streamLoad<kNt>(&qv[i]);
+      v = make_uint4(v.x ^ d.x, v.y ^ d.y, v.z ^ d.z, v.w ^ d.w);
+    }
+    return v;
+  };
 
-  if (w.part == 0 && tid < head) histAdd<S>(myBins, p[tid]);
+  if (w.part == 0 && tid < head) histAdd<S>(myBins, byteAt(tid));
 
   // Every workgroup streams ONE contiguous part of the element (whole 16 KiB steps; the last part takes the rest), four
   // 16-byte loads in flight per lane (the kernel is HBM-latency bound otherwise); see k_float_histogram.
@@ -631,14 +651,14 @@ __global__ __launch_bounds__(256) void k_histogram(BatchView in, uint32_t* __res
   const uint32_t vEnd = vBegin + perPart < numVec ? vBegin + perPart : numVec;
   uint32_t i = vBegin + tid;
   for (; i + 768u < vEnd; i += 1024u) {
-    const uint4 v0 = streamLoad<kNt>(&pv[i]), v1 = streamLoad<kNt>(&pv[i + 256u]), v2 = streamLoad<kNt>(&pv[i + 512u]), v3 = streamLoad<kNt>(&pv[i + 768u]);
+    const uint4 v0 = vecAt(i), v1 = vecAt(i + 256u), v2 = vecAt(i + 512u), v3 = vecAt(i + 768u);
     histAdd4<S>(myBins, v0.x); histAdd4<S>(myBins, v0.y); histAdd4<S>(myBins, v0.z); histAdd4<S>(myBins, v0.w);
     histAdd4<S>(myBins, v1.x); histAdd4<S>(myBins, v1.y); histAdd4<S>(myBins, v1.z); histAdd4<S>(myBins, v1.w);
     histAdd4<S>(myBins, v2.x); histAdd4<S>(myBins, v2.y); histAdd4<S>(myBins, v2.z); histAdd4<S>(myBins, v2.w);
     histAdd4<S>(myBins, v3.x); histAdd4<S>(myBins, v3.y); histAdd4<S>(myBins, v3.z); histAdd4<S>(myBins, v3.w);
   }
   for (; i < vEnd; i += 256u) {
-    const uint4 v = streamLoad<kNt>(&pv[i]);
+    const uint4 v = vecAt(i);
     histAdd4<S>(myBins, v.x);
     histAdd4<S>(myBins, v.y);
     histAdd4<S>(myBins, v.z);
@@ -647,7 +667,7 @@ __global__ __launch_bounds__(256) void k_histogram(BatchView in, uint32_t* __res
 
   if (w.part == 0) {
     uint32_t t = numVec * 16u + tid;
-    if (t < remaining) histAdd<S>(myBins, p[head + t]);
+    if (t < remaining) histAdd<S>(myBins, byteAt(head + t));
   }
   __syncthreads();
 

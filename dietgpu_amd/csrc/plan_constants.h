@@ -38,9 +38,14 @@ DGPU_HD constexpr bool encIsFeedback(uint32_t ft) { return (ft & kFeedbackSource
 // there is no counting and no feedback form.
 constexpr uint32_t kStochasticSource = 0x800u;
 DGPU_HD constexpr bool encIsStochastic(uint32_t ft) { return (ft & kStochasticSource) != 0u; }
-DGPU_HD constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~(kCastSource | kCountingSource | kFeedbackSource | kStochasticSource); }
+// kDeltaSource (with archive type 0, raw bytes): the symbols are in[k] ^ base[k], XOR-ed in registers from a second
+// input stream of the same size (kernels_encode.h, ChunkSource<kDeltaSource>; the delta form of k_histogram).  Planned
+// as the raw-byte call, but like the cast sources without single-block kernels: such elements run on 2-block tiles.
+constexpr uint32_t kDeltaSource = 0x1000u;
+DGPU_HD constexpr bool encIsDelta(uint32_t ft) { return (ft & kDeltaSource) != 0u; }
+DGPU_HD constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~(kCastSource | kCountingSource | kFeedbackSource | kStochasticSource | kDeltaSource); }
 // whether single-block elements of such a call have kernels of their own (k_ans_encode_pair, k_stats_single)
-DGPU_HD constexpr bool encHasSingleBlockKernels(uint32_t ft) { return (ft & (kCastSource | kCountingSource)) == 0u && ft != kFloat32; }
+DGPU_HD constexpr bool encHasSingleBlockKernels(uint32_t ft) { return (ft & (kCastSource | kCountingSource | kDeltaSource)) == 0u && ft != kFloat32; }
 
 // Encoder: blocks per tile = per workgroup.  8 (256 threads: 4 wave64 x 2 half-waves); 4 (128 threads) for batches whose
 // elements have at most 4 blocks -- an 8-block tile would leave half of its waves without a block there; a single

@@ -755,6 +755,72 @@ std::tuple<at::Tensor, at::Tensor> compress_data_stochastic(
   return {std::move(comp), std::move(sizes)};
 }
 
+// XOR-delta archives (no reference ops; dgpu_ans_delta_encode / dgpu_ans_delta_decode).  Tensors of any dtype are taken
+// as their bytes; a tensor and its base must agree in dtype, numel and device and both be contiguous.
+namespace {
+uint32_t deltaPairBytes(const at::Tensor& t, const at::Tensor& base, int dev) {
+  TORCH_CHECK(t.scalar_type() == base.scalar_type(), "dietgpu: a tensor and its base must have the same dtype");
+  TORCH_CHECK(t.numel() == base.numel(), "dietgpu: a tensor and its base must have the same number of elements");
+  TORCH_CHECK(t.device().is_cuda() && base.device().is_cuda() && t.get_device() == dev && base.get_device() == dev,
+              "dietgpu: a tensor and its base must be on the same GPU");
+  TORCH_CHECK(t.is_contiguous() && base.is_contiguous(), "dietgpu: tensors must be contiguous");
+  const uint64_t bytes = (uint64_t)t.numel() * t.element_size();
+  TORCH_CHECK(bytes <= std::numeric_limits<uint32_t>::max());
+  return (uint32_t)bytes;
+}
+}  // namespace
+
+// compress_data(False, ...) of ts_in[i] ^ ts_base[i], XOR-ed in the kernels.  No temp memory is passed: -> (comp, sizes).
+std::tuple<at::Tensor, at::Tensor> compress_data_delta(
+    const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tBases, const std::optional<at::Tensor>& outCompressed,
+    const std::optional<at::Tensor>& outCompressedSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.size() == tBases.size());
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  const size_t n = tIns.size();
+  std::vector<const void*> inPtrs(n), basePtrs(n);
+  std::vector<uint32_t> inSize(n);
+  uint64_t maxBytes = 0;
+  for (size_t i = 0; i < n; ++i) {
+    inSize[i] = deltaPairBytes(tIns[i], tBases[i], dev);
+    inPtrs[i] = tIns[i].data_ptr();
+    basePtrs[i] = tBases[i].data_ptr();
+    maxBytes = std::max<uint64_t>(maxBytes, inSize[i]);
+  }
+  at::Tensor comp, sizes;
+  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxAnsSize(maxBytes), dev, tIns[0].device(), comp, sizes);
+  std::vector<void*> compPtrs(n);
+  for (size_t i = 0; i < n; ++i) compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
+  check(dgpu_ans_delta_encode(precision(), (uint32_t)n, inPtrs.data(), basePtrs.data(), inSize.data(), compPtrs.data(),
+                              (uint32_t*)sizes.data_ptr(), streamOf(dev)),
+        "ansEncodeBatchDelta", false);
+  return {std::move(comp), std::move(sizes)};
+}
+
+// ts_out[i] = decoded archive ts_in[i] ^ ts_base[i]; ts_out[i] may BE ts_base[i] (in place).  -> 0 (no temp memory).
+int64_t decompress_data_delta(
+    const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tBases, const std::vector<at::Tensor>& tOuts,
+    const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.size() == tOuts.size() && tIns.size() == tBases.size());
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  const size_t n = tIns.size();
+  std::vector<const void*> basePtrs(n);
+  DecodeTensors m = marshalDecode(false, tIns, tOuts, dev, [&](size_t i) {
+    deltaPairBytes(tOuts[i], tBases[i], dev);
+    basePtrs[i] = tBases[i].data_ptr();
+  });
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  check(dgpu_ans_delta_decode(precision(), (uint32_t)n, m.inPtrs.data(), m.inBytes.data(), basePtrs.data(), m.outPtrs.data(),
+                              m.outCapacity.data(), ptrOrNull<uint8_t>(outStatus), ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
+        "ansDecodeBatchDelta", false);
+  return 0;
+}
+
 // Rolling-table compress (no reference op): compress_data / compress_data_cast with the tables made from the counts the
 // last call left (counts_in) and this call's counts taken by the encoder (counts_out): dgpu_float_rolling_compress.
 // float_type (1 = float16, 2 = bfloat16) is that of the archives; source_float32: ts_in are float32 and are rounded.
@@ -1076,6 +1142,12 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "compress_data_stochastic(Tensor[] ts_in, int float_type, int seed, Tensor? seed_dev=None, int first_member=0, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor)",
       &dietgpu_amd::compress_data_stochastic);
+  m.def(
+      "compress_data_delta(Tensor[] ts_in, Tensor[] ts_base, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor)",
+      &dietgpu_amd::compress_data_delta);
+  m.def(
+      "decompress_data_delta(Tensor[] ts_in, Tensor[] ts_base, Tensor[] ts_out, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
+      &dietgpu_amd::decompress_data_delta);
   m.def(
       "compress_data_rolling(Tensor[] ts_in, Tensor? counts_in, Tensor? counts_out, int float_type, bool source_float32=False, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::compress_data_rolling);

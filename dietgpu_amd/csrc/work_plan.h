@@ -38,11 +38,11 @@ struct LaunchGroup {
 
 // ---- Geometry ----
 // blocks per encoder tile for a batch whose largest element has `maxSize` symbols; ft: what is encoded (0: raw bytes; a
-// float type, with kCastSource for a cast call or kCountingSource for a counting one, which have no single-block
-// kernels: their single-block elements run on 2-block tiles)
+// float type, with kCastSource for a cast call or kCountingSource for a counting one; kDeltaSource for a delta call of
+// raw bytes -- these have no single-block kernels: their single-block elements run on 2-block tiles)
 inline uint32_t encTileBlocksFor(uint32_t maxSize, uint32_t ft = 0) {
   const uint32_t blocks = divUp(maxSize, kBlockSize);
-  if ((ft & (kCastSource | kCountingSource)) != 0u && blocks <= kBlocksPerTinyTile) return kBlocksPerTinyTile;
+  if ((ft & (kCastSource | kCountingSource | kDeltaSource)) != 0u && blocks <= kBlocksPerTinyTile) return kBlocksPerTinyTile;
   return blocks <= kBlocksPerSingleTile ? kBlocksPerSingleTile
       : blocks <= kBlocksPerTinyTile    ? kBlocksPerTinyTile
       : blocks <= kBlocksPerSmallTile   ? kBlocksPerSmallTile
@@ -151,8 +151,9 @@ inline bool listEncodeGroup(const std::vector<uint32_t>& elems, bool histInIndex
   listTilesElementMajor(elems, tiles, &tileBase, work);
   g->numTiles = (uint32_t)(work->size() - g->tilesAt);
   g->histAt = (uint32_t)work->size();
-  const uint32_t wordBytes = ft ? floatWordBytes(encArchiveType(ft)) : 1u;
-  if (needHist && !listHistParts(histInIndexOrder ? nullptr : elems.data(), elems.size(), sizes, wordBytes, ft == 0, g, work)) return false;
+  const bool raw = encArchiveType(ft) == 0u;  // (raw bytes, also of a delta call)
+  const uint32_t wordBytes = raw ? 1u : floatWordBytes(encArchiveType(ft));
+  if (needHist && !listHistParts(histInIndexOrder ? nullptr : elems.data(), elems.size(), sizes, wordBytes, raw, g, work)) return false;
   g->tileBaseAt = (uint32_t)work->size();
   work->insert(work->end(), tileBase.begin(), tileBase.end());
   return true;

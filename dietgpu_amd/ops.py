@@ -459,6 +459,67 @@ def compress_data_stochastic(ts_in, dtype, seed, first_member=0, out_compressed=
     return comp, sizes
 
 
+# ------------------------------------------------------------ XOR-delta archives
+# (no reference op: dgpu_ans_delta_encode / dgpu_ans_delta_decode, include/dietgpu_amd.h)
+def _delta_pairs(ts_a, ts_b, what):
+    """The checks of a delta call's tensor pairs (tensors of ANY dtype, taken as their bytes) -> the device index."""
+    _check(len(ts_a) > 0)
+    _check(len(ts_a) == len(ts_b), f"{what}: as many base tensors as tensors")
+    for a, b in zip(ts_a, ts_b):
+        _check(a.dtype == b.dtype, f"{what}: a tensor and its base must have the same dtype")
+        _check(a.numel() == b.numel(), f"{what}: a tensor and its base must have the same number of elements")
+        _check(a.device == b.device, f"{what}: a tensor and its base must be on the same device")
+        _check(a.is_contiguous() and b.is_contiguous(), f"{what}: tensors must be contiguous")
+        _check(a.numel() * a.element_size() <= _U32_MAX)
+    _check(ts_a[0].is_cuda, "tensors must be on the GPU")
+    dev = ts_a[0].get_device()
+    for a in ts_a:
+        _check(a.is_cuda and a.get_device() == dev)
+    return dev
+
+
+def compress_data_delta(ts_in, ts_base, out_compressed=None, out_compressed_sizes=None, prob_bits=K_DEFAULT_PRECISION):
+    """Compresses the bytes of ts_in[i] XOR-ed with the bytes of ts_base[i] -- a tensor against a near copy of it that the
+    receiver already holds -- in the kernels of the raw-byte compress: no scratch tensor, no extra pass.  The archive is
+    byte for byte what `compress_data(False, [a ^ b])` writes: an ordinary raw-byte archive
+    -> (comp [B, maxSize] u8, sizes [B] i32).  Tensors of any dtype, each pair alike in dtype, numel, device and both
+    contiguous; neither is modified.  No temp memory is passed (the call's temporaries are the stream's own); no
+    checksum."""
+    dev = _delta_pairs(ts_in, ts_base, "compress_data_delta")
+    op = _amd_op(prob_bits, "compress_data_delta")
+    if op is not None:
+        return op(ts_in, ts_base, out_compressed, out_compressed_sizes)
+    nbytes = [t.numel() * t.element_size() for t in ts_in]
+    rows, cols = len(ts_in), max_any_compressed_size(max(nbytes))
+    with torch.cuda.device(dev):
+        comp, sizes = _validate_out(out_compressed, out_compressed_sizes, rows, cols, dev, ts_in[0].device)
+        row = comp.size(1)
+        out_ptrs = (C.c_void_p * rows)(*[comp.data_ptr() + i * row for i in range(rows)])
+        check(lib().dgpu_ans_delta_encode(prob_bits, rows, _ptr_array(ts_in), _ptr_array(ts_base), _u32_array(nbytes), out_ptrs,
+                                          _ptr(sizes), _stream()))
+    return comp, sizes
+
+
+def decompress_data_delta(ts_in, ts_base, ts_out=None, out_status=None, out_sizes=None, prob_bits=K_DEFAULT_PRECISION):
+    """Decodes raw-byte archive ts_in[i] and XORs it with the bytes of ts_base[i]: ts_out[i] = decoded ^ ts_base[i], the
+    inverse of compress_data_delta.  ts_out=None: IN PLACE, ts_base[i] becomes the new tensor.  Otherwise ts_out[i] matches
+    ts_base[i] in dtype, numel and device and does not overlap it.  out_status[i] is 0, and ts_out[i] keeps every byte --
+    in place: the base survives -- for a malformed or truncated archive or one that does not fit; out_sizes[i] is the
+    size in bytes its header states.  No temp memory is used -> 0."""
+    outs = ts_base if ts_out is None else ts_out
+    dev = _delta_pairs(outs, ts_base, "decompress_data_delta")
+    _check(len(ts_in) == len(ts_base))
+    op = _amd_op(prob_bits, "decompress_data_delta")
+    if op is not None:
+        return op(ts_in, ts_base, outs, out_status, out_sizes)
+    caps = _decode_capacities(False, ts_in, outs, dev)
+    _validate_status(out_status, out_sizes, len(ts_in), dev)
+    with torch.cuda.device(dev):
+        check(lib().dgpu_ans_delta_decode(prob_bits, len(ts_in), _ptr_array(ts_in), _in_bytes(ts_in), _ptr_array(ts_base),
+                                          _ptr_array(outs), _u32_array(caps), _ptr(out_status), _ptr(out_sizes), _stream()))
+    return 0
+
+
 # ------------------------------------------------------- rolling-table compress
 # (no reference op: dgpu_float_rolling_compress, include/dietgpu_amd.h)
 def _validate_counts(counts, rows, dev, name):

@@ -74,7 +74,8 @@ const char* dgpu_version(void);
  * dgpu_float_reduce_norm_temp_bytes, dgpu_float_decode_reduce_norm, dgpu_float_reduce_compress_norm and
  * dgpu_float_decode_scaled were added at version 8, dgpu_float_feedback_compress and
  * dgpu_float_decode_accumulate_scaled after them, dgpu_float_decode_update after those,
- * dgpu_float_stochastic_compress after dgpu_float_decode_update). */
+ * dgpu_float_stochastic_compress after dgpu_float_decode_update, dgpu_ans_delta_encode and dgpu_ans_delta_decode after
+ * that). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -572,6 +573,49 @@ int dgpu_float_stochastic_compress(
     uint32_t numInBatch, const void* const* in /* float32 */, const uint32_t* inSize /* words */,
     uint64_t seed, const uint64_t* seed_dev /* nullable */, uint32_t firstMember,
     void* const* out, uint32_t* outSize_dev, void* stream);
+
+/* ---- XOR-delta archives (no upstream equivalent) ------------------------------------------
+ * For a tensor that is a near copy of something the receiver already holds -- the weights a trainer pushes after an
+ * optimiser step, a checkpoint against the one before it, a replica being re-synchronised: the archive codes in ^ base,
+ * which is mostly zero bytes, and the decoder XORs the base back.  Both directions run in the kernels of the raw-byte
+ * codec: no scratch tensor and no extra pass over the data on either side.
+ *
+ * dgpu_ans_delta_encode: out[i] / outSize_dev[i] are byte for byte what dgpu_ans_encode_batch_pointer(useChecksum = 0,
+ * no caller histogram) writes for the bytes d[k] = in[i][k] ^ base[i][k], k < inSize[i]: an ORDINARY raw-byte ANS archive
+ * that every decoder of this header reads.  The histogram pass and the encoder each read both streams and XOR in
+ * registers.
+ *   - in[i] and base[i] are 4-byte aligned (each may lie anywhere modulo 16, independently of the other), hold inSize[i]
+ *     bytes and are never written; they may overlap each other (in[i] == base[i] gives the archive of zeros).  out[i] is
+ *     16-byte aligned with room for dgpu_ans_max_compressed_size(inSize[i]).  probBits 9 / 10 / 11, numInBatch <= 65535,
+ *     inSize[i] within the size guard of dgpu_ans_encode_batch_pointer, no array null when numInBatch > 0:
+ *     DGPU_ERR_INVALID_ARGUMENT with a dgpu_last_error() text otherwise, before anything is enqueued.  An empty batch
+ *     returns 0.  There is no checksum and no caller histogram.
+ *   - Planned as dgpu_ans_encode_batch_pointer -- stride detection (in, base and out must all be progressions),
+ *     parameter cache, work lists, size classes, both dispatch forms, every histogram form -- except that single-block
+ *     elements run on the 2-block tiles: the single-block kernels have no delta form.
+ *
+ * dgpu_ans_delta_decode: out[i][k] = decoded[k] ^ base[i][k] for the raw-byte archive in[i] of inBytes[i] bytes.
+ *   - IN PLACE is legal and is the main use: out[i] == base[i] turns the base into the new tensor.  Otherwise out[i] and
+ *     base[i] must not overlap (a partial overlap is rejected), and neither may overlap an archive or another member.
+ *     base[i] holds at least as many bytes as the archive states, which outCapacity[i] bounds; any alignment.
+ *   - Every archive check of dgpu_ans_decode_batch_pointer_bounded applies; outSuccess_dev[i] and outSize_dev[i] behave
+ *     as there.  A member that fails (a malformed or truncated archive, one that does not fit outCapacity[i]) writes NO
+ *     byte of out[i] -- in place, its base survives -- and does not disturb the others.  No byte outside
+ *     [out[i], out[i] + size) is written.  A checksum in the archive is ignored.
+ *   - in[i] 16-byte aligned, probBits 9 / 10 / 11, numInBatch <= 65535, outCapacity[i] <= 0xfffff000, no array null
+ *     when numInBatch > 0: DGPU_ERR_INVALID_ARGUMENT with a dgpu_last_error() text otherwise, before anything is
+ *     enqueued.  An empty batch returns 0.  One kernel geometry per call, from its largest capacity (16-block tiles,
+ *     4-block tiles for members of up to 8 blocks).
+ *
+ * Neither call has temp-memory parameters: temporaries come from the stream's library-owned slab
+ * (dgpu_release_stream_state).  Both are asynchronous and capturable into a HIP graph under the conditions of their
+ * siblings (the pointer arrays resident from an earlier identical call). */
+int dgpu_ans_delta_encode(
+    int probBits, uint32_t numInBatch, const void* const* in, const void* const* base, const uint32_t* inSize /* bytes */,
+    void* const* out, uint32_t* outSize_dev, void* stream);
+int dgpu_ans_delta_decode(
+    int probBits, uint32_t numInBatch, const void* const* in, const uint32_t* inBytes, const void* const* base,
+    void* const* out, const uint32_t* outCapacity /* bytes */, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
 
 /* ---- rolling-table compress (no upstream equivalent) ------------------------------------
  * (Named like its siblings dgpu_float_cast_compress and dgpu_float_reduce_compress: the call is a compress with a
