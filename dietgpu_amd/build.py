@@ -32,7 +32,7 @@ def build(force=False, verbose=False):
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
            "-o", LIB_PATH] + [os.path.join(CSRC, s) for s in _SOURCES]
     if verbose:
-        print(" ".join(cmd))
+        print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
     return LIB_PATH
 
@@ -40,22 +40,42 @@ def build(force=False, verbose=False):
 TORCH_LIB_PATH = os.path.join(LIB_DIR, "libdietgpu_torch.so")
 
 
-def build_torch_ops(force=False, verbose=False):
-    """torch.ops.dietgpu.* (csrc/torch_ops.cpp): plain host C++ against PyTorch-ROCm and the C ABI."""
+TORCH_OBJ_PATH = os.path.join(LIB_DIR, "torch_ops.o")
+
+
+def compile_torch_ops(verbose=False):
+    """torch_ops.cpp -> lib/torch_ops.o.  Needs nothing of the core library but its header, so it can run beside the
+    (much longer) compile of the kernels; build_torch_ops links it."""
+    import torch
+
+    os.makedirs(LIB_DIR, exist_ok=True)
+    tl = os.path.dirname(torch.__file__)
+    abi = int(torch._C._GLIBCXX_USE_CXX11_ABI)
+    cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-c", "-D__HIP_PLATFORM_AMD__", "-DUSE_ROCM",
+           f"-D_GLIBCXX_USE_CXX11_ABI={abi}", f"-I{tl}/include", f"-I{tl}/include/torch/csrc/api/include",
+           "-I/opt/rocm/include", os.path.join(CSRC, "torch_ops.cpp"), "-o", TORCH_OBJ_PATH]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return TORCH_OBJ_PATH
+
+
+def build_torch_ops(force=False, verbose=False, compiled=False):
+    """torch.ops.dietgpu.* (csrc/torch_ops.cpp): plain host C++ against PyTorch-ROCm and the C ABI.  compiled: the
+    object is there already (compile_torch_ops), only the link is left."""
     src = os.path.join(CSRC, "torch_ops.cpp")
     if (not force and os.path.exists(TORCH_LIB_PATH)
             and os.path.getmtime(TORCH_LIB_PATH) >= max(os.path.getmtime(src), os.path.getmtime(LIB_PATH))):
         return TORCH_LIB_PATH
     import torch
 
+    if not compiled:
+        compile_torch_ops(verbose)
     tl = os.path.dirname(torch.__file__)
-    abi = int(torch._C._GLIBCXX_USE_CXX11_ABI)
-    cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-DUSE_ROCM",
-           f"-D_GLIBCXX_USE_CXX11_ABI={abi}", f"-I{tl}/include", f"-I{tl}/include/torch/csrc/api/include",
-           "-I/opt/rocm/include", src, "-o", TORCH_LIB_PATH, f"-L{LIB_DIR}", "-ldietgpu_amd", f"-L{tl}/lib",
+    cmd = ["g++", "-shared", TORCH_OBJ_PATH, "-o", TORCH_LIB_PATH, f"-L{LIB_DIR}", "-ldietgpu_amd", f"-L{tl}/lib",
            "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip", "-ltorch_hip", "-Wl,-rpath,$ORIGIN"]
     if verbose:
-        print(" ".join(cmd))
+        print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
     return TORCH_LIB_PATH
 

@@ -1086,6 +1086,14 @@ struct StochasticSeed {
   const uint64_t* seed_dev = nullptr;
   uint32_t firstMember = 0;
 };
+// dgpu_fp8_cast_compress: the factor the histogram and the encoder multiply every word by before they round it -- the
+// host float, or device memory that both kernels read when they run (dev; stride 0: one factor, 1: one per member).
+// Kernel arguments like the seed: calls that differ only in the factor share the parameter block.
+struct CastFactor {
+  float scale = 1.0f;
+  const float* dev = nullptr;
+  uint32_t stride = 0;
+};
 struct EncodeShared {
   uint32_t* checksumTemp = nullptr;  // [B] the batch's checksums (computed by the first class's call)
   uint4* table = nullptr;            // [B][256] encoder tables, indexed by the element's own index
@@ -1102,7 +1110,8 @@ int encodeCommon(
                                        the normalisation reads them and puts them back to zero */,
     const RollingCounts& rolling = RollingCounts{},
     const DeviceBatch* residual = nullptr /* feedback source: its resIn / resOut; delta source: its base */,
-    const StochasticSeed& sr = StochasticSeed{} /* stochastic source: handed to both launches */) {
+    const StochasticSeed& sr = StochasticSeed{} /* stochastic source: handed to both launches */,
+    const CastFactor& cf = CastFactor{} /* FP8 source: handed to both launches */) {
   // (kCountingSource is the planner's: from here on the source is what the kernels are instantiated for)
   sourceType &= ~kCountingSource;
   // (rolling.countsIn arrives as hist_dev -- encodeBatch passes it as the call's histogram; here it only says that the
@@ -1265,6 +1274,10 @@ int encodeCommon(
     fuse.seedPtr = sr.seed_dev;
     fuse.firstMember = sr.firstMember;
     fuse.base = residual ? residual->base : BatchView{};
+    fuse.scale = cf.scale;
+    fuse.scalePtr = cf.dev;
+    fuse.scaleStride = cf.stride;
+    fuse.fp8E5M2 = (sourceType & kFp8E5M2) ? 1u : 0u;
     // bins with 32 lane slots unless a workgroup sees too little data to pay for zeroing / folding them
     const bool smallBins = histList ? listedHistPartBytes <= 64u * 1024u : (uint64_t)maxSize * wordBytes / grid.x <= 64u * 1024u;
     rc = launchVariant(histogramVariant(sourceType, smallBins, histogramLoadsNonTemporal(floatType)), grid, stream, in, histTemp, 1u, fuse);
@@ -1310,6 +1323,10 @@ int encodeCommon(
     e.seedPtr = sr.seed_dev;
     e.firstMember = sr.firstMember;
     e.base = residual ? residual->base : BatchView{};
+    e.scale = cf.scale;
+    e.scalePtr = cf.dev;
+    e.scaleStride = cf.stride;
+    e.fp8E5M2 = (sourceType & kFp8E5M2) ? 1u : 0u;
     int rc = launchVariant(enc, dim3(grid), stream, e);
     if (rc) return rc;
   }
@@ -1322,7 +1339,7 @@ int encodeBatch(
     void* temp_dev, size_t tempBytes, size_t* tempUsed, uint32_t ft, int P, int useChecksum, Batch& b,
     const uint32_t* histogram_dev /*may be null*/, uint32_t* outSize_dev, hipStream_t stream,
     uint32_t outCapacity = 0xffffffffu /* as encodeCommon's */, const RollingCounts& rolling = RollingCounts{},
-    const StochasticSeed& sr = StochasticSeed{}) {
+    const StochasticSeed& sr = StochasticSeed{}, const CastFactor& cf = CastFactor{}) {
   // a counting call is planned without single-block kernels, one with last call's counts as one with a caller's histogram
   if (rolling.countsOut) ft |= kCountingSource;
   if (rolling.countsIn) histogram_dev = rolling.countsIn;
@@ -1330,8 +1347,9 @@ int encodeBatch(
   TempArena arena(temp_dev, tempBytes, streamLease);
   DeviceBatch d;
   // (a feedback call, and a stochastic one, is planned as the cast call it extends: same geometry, same lists, same
-  // cached plan; a delta call keeps its flag: the raw-byte plan without single-block kernels)
-  const uint32_t planType = ft & ~(kFeedbackSource | kStochasticSource);
+  // cached plan; a delta call keeps its flag: the raw-byte plan without single-block kernels; so does an FP8 call,
+  // whichever of the two types it rounds to)
+  const uint32_t planType = ft & ~(kFeedbackSource | kStochasticSource | kFp8E5M2);
   std::vector<LaunchGroup> groups{encodeRectangle(b.maxSize, planType)};
   int rc = resolveBatch(b, false, streamLease, &d, [&] { planEncodeCall(planPolicy(), b.sizes, planType, b.maxSize, histogram_dev != nullptr, &groups, &b.work); });
   if (rc) return rc;
@@ -1340,7 +1358,7 @@ int encodeBatch(
   EncodeShared shared;
   for (const LaunchGroup& g : groups) {
     rc = encodeCommon(arena, streamLease, stream, P, useChecksum != 0, b.n, d.in, d.out, ft, g, d.work, shared, histogram_dev, outSize_dev, outCapacity, nullptr, rolling,
-                      (encIsFeedback(ft) || encIsDelta(ft)) ? &d : nullptr, sr);
+                      (encIsFeedback(ft) || encIsDelta(ft)) ? &d : nullptr, sr, cf);
     if (rc) break;
   }
   if (tempUsed) *tempUsed = arena.requested();
@@ -2581,6 +2599,74 @@ int dgpu_ans_delta_decode(
   DecodeArgs d = decodeArgs(b, dev, 0u, outSuccess_dev, outSize_dev);
   d.base = dev.base;
   return launchDecode(d, group, dev.work, DecodeForm::kDelta, probBits, (hipStream_t)stream);
+}
+
+// ---- FP8 archives (no upstream equivalent) -----------------------------------------------
+// Raw-byte ANS archives of float32 words rounded to an OCP FP8 type, and their decode into float32 accumulators
+// (kernels_stats.h, fp8Round / fp8Widen and k_histogram's FP8 form; kernels_encode.h, ChunkSource<kFp8Source>;
+// kernels_decode.h, Fp8AccumSink): the raw pointer calls with a source flag / a decode form and a factor among the kernel
+// arguments.  Temporaries come from the stream's slab.
+static bool validFp8Type(uint32_t t) { return t == DGPU_FP8_E4M3FN || t == DGPU_FP8_E5M2; }
+static int checkFactor(const char* what, float scale, const float* scale_dev, uint32_t scalePerMember) {
+  DGPU_REQUIRE(scalePerMember <= 1u, std::string(what) + ": scalePerMember must be 0 (one factor) or 1 (one per member)");
+  DGPU_REQUIRE(scale_dev != nullptr || (std::isfinite(scale) && scale != 0.0f), std::string(what) + ": a host scale must be finite and not zero");
+  DGPU_REQUIRE((uintptr_t)scale_dev % 4u == 0u, std::string(what) + ": scale_dev must be 4-byte aligned");
+  return DGPU_OK;
+}
+
+int dgpu_fp8_cast_compress(
+    uint32_t fp8Type, int probBits, uint32_t numInBatch, const void* const* in, const uint32_t* inSize, float scale, const float* scale_dev,
+    uint32_t scalePerMember, void* const* out, uint32_t* outSize_dev, void* stream) {
+  DGPU_REQUIRE(validFp8Type(fp8Type), "fp8Type must be DGPU_FP8_E4M3FN or DGPU_FP8_E5M2");
+  DGPU_REQUIRE(validProbBits(probBits), "probBits must be 9, 10 or 11");
+  DGPU_REQUIRE(numInBatch <= 65535u, "numInBatch must be <= 65535");
+  int rc = checkFactor("fp8 cast-compress", scale, scale_dev, scalePerMember);
+  if (rc) return rc;
+  DGPU_REQUIRE(numInBatch == 0 || (in && inSize && out), "fp8 cast-compress: null array with numInBatch > 0");
+  for (uint32_t i = 0; i < numInBatch; ++i) {
+    DGPU_REQUIRE(encodableSize(inSize[i]), "tensor larger than 1717538816 words: its maximum compressed size exceeds INT32_MAX (GpuANSEncode.cu:22)");
+  }
+  Batch b;
+  rc = pointerBatch(&b, numInBatch, ptrSide(in, 4, "fp8 cast-compress: float32 input must be 4-byte aligned"), ptrSide(out, 16, kMsgCompOut), inSize);
+  if (rc) return rc;
+  if (numInBatch == 0) return DGPU_OK;
+  CastFactor cf;
+  cf.scale = scale;
+  cf.dev = scale_dev;
+  cf.stride = scalePerMember;
+  return encodeBatch(nullptr, 0, nullptr, kFp8Source | (fp8Type == DGPU_FP8_E5M2 ? kFp8E5M2 : 0u), probBits, 0, b, nullptr, outSize_dev, (hipStream_t)stream,
+                     0xffffffffu, RollingCounts{}, StochasticSeed{}, cf);
+}
+
+int dgpu_fp8_decode_accumulate(
+    uint32_t fp8Type, int probBits, int accumulate, uint32_t numInBatch, const void* const* in, const uint32_t* inBytes, float scale,
+    const float* scale_dev, uint32_t scalePerMember, void* const* acc, const uint32_t* accWords, uint8_t* outSuccess_dev, uint32_t* outSize_dev,
+    void* stream) {
+  DGPU_REQUIRE(validFp8Type(fp8Type), "fp8Type must be DGPU_FP8_E4M3FN or DGPU_FP8_E5M2");
+  DGPU_REQUIRE(accumulate == 0 || accumulate == 1, "fp8 decode-accumulate: accumulate must be 0 or 1");
+  int rc = checkFactor("fp8 decode-accumulate", scale, scale_dev, scalePerMember);
+  if (rc) return rc;
+  bool done;
+  rc = checkCall(probBits, numInBatch, 0u, /*tempUsed*/ nullptr, /*errBatch*/ nullptr, &done);
+  if (done) return rc;
+  DGPU_REQUIRE(in && inBytes && acc && accWords, "fp8 decode-accumulate: null array with numInBatch > 0");
+  Batch b;
+  rc = pointerBatch(&b, numInBatch, ptrSide(in, 16, kMsgCompIn), ptrSide(acc, 4, "fp8 decode-accumulate: accumulators must be 4-byte aligned"), accWords, inBytes);
+  if (rc) return rc;
+  // (the tiles are planned in symbols, 32 bits: the blocks of a capacity must not round up to 2^32 of them)
+  DGPU_REQUIRE(b.maxSize <= 0xfffff000u, "fp8 decode-accumulate: accWords must not exceed 0xfffff000");
+  StreamLease streamLease((hipStream_t)stream);
+  DeviceBatch dev;
+  LaunchGroup group;
+  rc = planFloatDecode(b, streamLease, &dev, &group);  // (one geometry per call, 16- or 4-block tiles, as the other sink forms)
+  if (rc) return rc;
+  DecodeArgs d = decodeArgs(b, dev, 0u, outSuccess_dev, outSize_dev);
+  d.accumulate = (uint32_t)accumulate;
+  d.scale = scale;
+  d.scalePtr = scale_dev;
+  d.scaleStride = scalePerMember;
+  d.fp8E5M2 = fp8Type == DGPU_FP8_E5M2 ? 1u : 0u;
+  return launchDecode(d, group, dev.work, DecodeForm::kFp8Accum, probBits, (hipStream_t)stream);
 }
 
 // ---- rolling-table compress (no upstream equivalent) ------------------------------------

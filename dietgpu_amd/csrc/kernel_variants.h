@@ -127,12 +127,15 @@ inline EncodeVariant encoderVariantCounting(int P, uint32_t ft, uint32_t tileBlo
 // The delta source (kDeltaSource: raw bytes XOR-ed with a base, ChunkSource<kDeltaSource>) exists as the raw-byte
 // encoder's tiles of 2, 4 and 8 blocks in both dispatch forms.  There is no delta form of the single-block kernels:
 // single-block members of a delta call run on 2-block tiles.
-inline EncodeVariant encoderVariantDelta(int P, uint32_t tileBlocks, bool hwDispatch) {
+// The FP8 source (kFp8Source: float32 words rounded to an OCP FP8 byte, ChunkSource<kFp8Source>) exists in exactly the
+// same forms; which of the two FP8 types is a kernel argument (`fp8`: that source instead of the delta source).
+inline EncodeVariant encoderVariantDelta(int P, uint32_t tileBlocks, bool hwDispatch, bool fp8 = false) {
   return withProbBits(P, [&](auto p) -> EncodeVariant {
     constexpr int kP = decltype(p)::value;
-    auto tiled = [](auto tb, auto persistent) -> EncodeVariant {
+    auto tiled = [fp8](auto tb, auto persistent) -> EncodeVariant {
       constexpr uint32_t kTB = decltype(tb)::value;
       constexpr bool kPersistent = decltype(persistent)::value;
+      if (fp8) return {k_ans_encode<kP, kFp8Source, false, kTB, kPersistent, false>, encThreads(kTB), encLdsBytes(kP, false, kFp8Source, kTB), "k_ans_encode_fp8"};
       return {k_ans_encode<kP, kDeltaSource, false, kTB, kPersistent, false>, encThreads(kTB), encLdsBytes(kP, false, kDeltaSource, kTB), "k_ans_encode_delta"};
     };
     constexpr std::true_type yes{};
@@ -152,6 +155,7 @@ inline EncodeVariant encoderVariantDelta(int P, uint32_t tileBlocks, bool hwDisp
 inline EncodeVariant encoderVariant(int P, uint32_t ft, uint32_t tileBlocks, bool hwDispatch, bool wide) {
   if (encIsCast(ft)) return encoderVariantCast(P, encArchiveType(ft), tileBlocks, hwDispatch, ft & (kFeedbackSource | kStochasticSource));
   if (encIsDelta(ft)) return encoderVariantDelta(P, tileBlocks, hwDispatch);
+  if (encIsFp8(ft)) return encoderVariantDelta(P, tileBlocks, hwDispatch, true);
   return withProbBitsAndFloatType(P, ft, [&](auto p, auto f) -> EncodeVariant {
     constexpr int kP = decltype(p)::value;
     constexpr uint32_t kFT = decltype(f)::value;
@@ -211,6 +215,9 @@ constexpr uint32_t rawOnly(uint32_t) { return 0u; }                             
 //     seed / firstMember); float16 and bfloat16 only, the LDS of kAccum;
 //   * kDelta: the whole bounded decode of raw bytes XOR-ed with DecodeArgs::base into the output, which may BE the base
 //     (DeltaSink); raw bytes only, with store buffers also on 16-block tiles (decXposeBytes, delta);
+//   * kFp8Accum: the whole bounded decode of raw bytes that are OCP FP8 values, widened, multiplied by the member's
+//     factor and stored to or added into float32 accumulators (Fp8AccumSink; DecodeArgs::fp8E5M2 says which type); raw
+//     bytes only, the LDS of kDelta;
 //   * kRanged: decodes a block range of every element (a range of one or two blocks takes the 4-block form).
 #define DGPU_DECODE_FORMS(X)                                                                                           \
   X(kAccum, k_ans_decode_accum, floatsOnly, decLdsBytes(P, T, TB))                                                     \
@@ -226,6 +233,7 @@ constexpr uint32_t rawOnly(uint32_t) { return 0u; }                             
   X(kAccumScaled, k_ans_decode_accum_scaled, floatsOnly, decLdsBytes(P, T, TB))                                        \
   X(kUpdate, k_ans_decode_update, halvesOnly, decLdsBytes(P, T, TB))                                                   \
   X(kDelta, k_ans_decode_delta, rawOnly, decLdsBytes(P, T, TB, true))                                                  \
+  X(kFp8Accum, k_ans_decode_fp8_accum, rawOnly, decLdsBytes(P, T, TB, true))                                           \
   X(kRanged, k_ans_decode_range, sameType, decLdsBytes(P, T, TB))
 
 // The decoder of tiles of `tileBlocks` blocks.  A form of the list above takes the 4-block instantiation for tiles of
@@ -261,7 +269,7 @@ inline DecodeVariant decoderVariant(int P, uint32_t ft, uint32_t tileBlocks, Dec
 
 // The histogram pass: bins with kHistSlotsSmall or kHistSlotsLarge lane slots, non-temporal or ordinary input loads.
 // (ft with kCastSource: the cast form, which bins the exponent byte of the rounded word; with kFeedbackSource or
-// kStochasticSource as well: that source's rounding; kDeltaSource: the delta form of the raw-byte pass)
+// kStochasticSource as well: that source's rounding; kDeltaSource / kFp8Source: the delta / FP8 form of the raw-byte pass)
 inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTemporal) {
   auto pick = [&](auto f) -> HistogramVariant {
     constexpr uint32_t kFT = decltype(f)::value;
@@ -272,6 +280,8 @@ inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTe
         return {k_histogram<kS, kNt>, 256u, 0u, "k_histogram"};
       } else if constexpr (kFT == kDeltaSource) {
         return {k_histogram<kS, kNt, true>, 256u, 0u, "k_histogram_delta"};
+      } else if constexpr (kFT == kFp8Source) {
+        return {k_histogram<kS, kNt, false, true>, 256u, 0u, "k_histogram_fp8"};
       } else {
         return {k_float_histogram<kFT, kS, kNt>, 256u, 0u,
                 encIsStochastic(kFT) ? "k_float_histogram_stochastic"
@@ -284,6 +294,7 @@ inline HistogramVariant histogramVariant(uint32_t ft, bool smallBins, bool nonTe
     return smallBins ? of(small, std::false_type{}) : of(large, std::false_type{});
   };
   if (encIsDelta(ft)) return pick(UintC<kDeltaSource>{});
+  if (encIsFp8(ft)) return pick(UintC<kFp8Source>{});
   if (encIsFeedback(ft)) {
     return encArchiveType(ft) == kFloat16 ? pick(UintC<kFloat16 | kCastSource | kFeedbackSource>{}) : pick(UintC<kBFloat16 | kCastSource | kFeedbackSource>{});
   }

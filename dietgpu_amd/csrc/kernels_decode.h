@@ -92,6 +92,9 @@ struct DecodeArgs {
   const uint64_t* seedPtr = nullptr;
   // k_ans_decode_delta only: the bytes member b's decoded bytes are XOR-ed with, base.ptr(b); may equal out.ptr(b)
   BatchView base = BatchView{};
+  // k_ans_decode_fp8_accum only: the decoded bytes are e5m2 (!= 0) or e4m3fn values; it also takes accumulate and
+  // scale / scalePtr / scaleStride, above
+  uint32_t fp8E5M2 = 0;
 };
 __device__ __forceinline__ uint64_t decodeInBytes(const DecodeArgs& a, uint32_t b) {
   return a.inBytes ? (uint64_t)a.inBytes[b] : (a.uniformInBytes ? (uint64_t)a.uniformInBytes : ~0ull);
@@ -774,6 +777,76 @@ struct DeltaSink : RowSink<0> {
 };
 
 // ---------------------------------------------------------------------------
+// FP8 accumulating sink (k_ans_decode_fp8_accum; raw bytes): RowSink<0> whose every decoded byte is an OCP FP8 value
+// (e5m2, or e4m3fn; wave-uniform, a kernel argument) that is widened to float32 (fp8Widen: exact), multiplied by the
+// member's factor and stored to (accumulate == 0: the accumulator is not read) or added into a float32 accumulator --
+// ONE IEEE multiply and ONE IEEE add, written unfused as AccumSink's kPreScaled pair.  Staging is RowSink<0>'s; the
+// accumulator words travel where AccumSink's travel (Pre / GroupPre):
+//   * wide path: a lane owns the 8 consecutive bytes of a group that RowSink<0>::flushGroup would store; it requests its
+//     32 bytes of accumulator two groups ahead (prefetchGroup: two 16-byte loads, none with accumulate == 0), and at
+//     the flush widens the 8 bytes, multiplies, adds and leaves two 16-byte stores -- 1 KiB contiguous per half-wave
+//     and group, under the decoder's store policy (kNtDecStores), as AccumSink's;
+//   * narrow path: one float32 per lane and row, the accumulator word requested one group ahead.
+// Accumulators are float-aligned (the host checks it), so the wide path serves every member.
+struct Fp8GroupPre {  // the 8 accumulator words of a lane's group
+  u32x4w a0, a1;
+};
+struct Fp8AccumSink : RowSink<0> {
+  float* acc;  // the lane's word of row 0 of its block
+  uint32_t accumulate;
+  float factor;
+  bool e5m2;
+  __device__ __forceinline__ void init(uint8_t* outBase, const uint8_t*, uint32_t, size_t first, uint32_t hl) {
+    acc = (float*)outBase + first + hl;
+  }
+  typedef uint32_t Pre;
+  typedef Fp8GroupPre GroupPre;
+  // the float32 bits that are stored for byte `sym` and accumulator word `a`
+  __device__ __forceinline__ uint32_t word(uint32_t sym, uint32_t a) const {
+    const float v = accMulUnfused(fp8Widen(sym, e5m2), factor);
+    return accumulate ? accAddUnfused(a, v) : __builtin_bit_cast(uint32_t, v);
+  }
+  __device__ __forceinline__ uint32_t prefetch(uint32_t row) const {
+    uint32_t a = 0;
+    if (accumulate) a = *(const uint32_t*)&acc[row * 32u];
+    return a;
+  }
+  __device__ __forceinline__ void store(uint32_t row, uint32_t e0, uint32_t a) const {
+    streamStore<kNtDecStores>((uint32_t*)&acc[row * 32u], word(e0 >> 24, a));
+  }
+  __device__ __forceinline__ Fp8GroupPre prefetchGroup(uint32_t g, uint32_t hl) const {
+    Fp8GroupPre p;
+    p.a0 = p.a1 = u32x4w{0u, 0u, 0u, 0u};
+    if (accumulate) {
+      const u32x4w4* src = (const u32x4w4*)(acc - hl + g * 256u + hl * 8u);
+      p.a0 = src[0];
+      p.a1 = src[1];
+    }
+    return p;
+  }
+  __device__ __forceinline__ void flushGroup(uint32_t xpose, uint32_t g, uint32_t hl, const Fp8GroupPre& p) const {
+    // (the staged rows are {0, sym} halves: byte 1 and byte 3 of every dword are the symbols of rows 2 k and 2 k + 1)
+    const u32x4w v = *(const LdsU4w*)(uintptr_t)(xpose + hl * 16u);
+    u32x4w o0, o1;
+#pragma unroll
+    for (uint32_t k = 0; k < 2u; ++k) {
+      o0[2u * k] = word((v[k] >> 8) & 0xffu, p.a0[2u * k]);
+      o0[2u * k + 1u] = word(v[k] >> 24, p.a0[2u * k + 1u]);
+      o1[2u * k] = word((v[2u + k] >> 8) & 0xffu, p.a1[2u * k]);
+      o1[2u * k + 1u] = word(v[2u + k] >> 24, p.a1[2u * k + 1u]);
+    }
+    u32x4w4* dst = (u32x4w4*)(acc - hl + g * 256u + hl * 8u);
+    if (kNtDecStores) {
+      __builtin_nontemporal_store(o0, &dst[0]);
+      __builtin_nontemporal_store(o1, &dst[1]);
+    } else {
+      dst[0] = o0;
+      dst[1] = o1;
+    }
+  }
+};
+
+// ---------------------------------------------------------------------------
 // Compressed-word ring: 4 chunks of 256 words (512 bytes) per block.  Chunk k of
 // the block's data lives in slot k & 3.  Words are consumed from the top of the
 // block downwards, at most 32 per row = 256 per 8-row group = one chunk per
@@ -800,6 +873,9 @@ __host__ __device__ constexpr uint32_t decThreads(uint32_t tileBlocks) { return 
 // one-byte stores -- to a form whose base is as many bytes as its output: it moves the memory traffic of the 16-bit
 // float decode (one more input stream of the output's size), which is the case the buffers were measured for.  48 KiB,
 // three workgroups per CU, ONE 8-byte load and ONE 8-byte store per lane and group.
+// The FP8 accumulating form (k_ans_decode_fp8_accum, Fp8AccumSink) passes `delta` too: its narrow path would be 128
+// four-byte stores (and as many loads when it adds) per lane and block in 128-byte pieces, where the buffers leave 32
+// bytes per lane and group contiguous; it writes FOUR times the bytes it decodes, so it is the stores it lives on.
 __host__ __device__ constexpr uint32_t decXposeBytes(int P, uint32_t ft, uint32_t tileBlocks, bool delta = false) {
   (void)P;
   if (ft == 0 && tileBlocks >= 16u && !delta) return 0u;
@@ -821,7 +897,7 @@ __host__ __device__ constexpr uint32_t decLdsBytes(int P, uint32_t ft, uint32_t 
   return decLutBytes(P, tileBlocks) + tileBlocks * kRingBytes + tileBlocks * decXposeBytes(P, ft, tileBlocks, delta);
 }
 static_assert(decLdsBytes(10, 0u, 16u) == 40u * 1024u && decLdsBytes(10, 0u, 16u, true) == 48u * 1024u && 3u * decLdsBytes(11, 0u, 16u, true) <= 160u * 1024u,
-              "raw bytes on 16-block tiles: four workgroups per CU without store buffers, three with them (delta)");
+              "raw bytes on 16-block tiles: four workgroups per CU without store buffers, three with them (delta, FP8 accumulate)");
 
 // kIdleUpper (full path only): the upper half of the wave has no block (the element's block count is odd, or
 // it has a single block): its lanes run the same straight-line code on don't-care data and only their
@@ -1136,8 +1212,14 @@ __device__ __forceinline__ void decodeBlock(
 // kAccum's addition: every tile checks all the element's block descriptors and no tile of a failing element stores -- in
 // place, a failing member keeps every bit of its base.  The base is read below the size the header states only, which
 // the capacity bounds.  Store buffers on every tile size (decXposeBytes, delta).
+//
+// kFp8Accum: the whole bounded decode of RAW bytes that are OCP FP8 values (DecodeArgs::fp8E5M2), widened to float32,
+// multiplied by the member's factor (as kAccumScaled takes it; 1 without one) and stored to or added into float32
+// accumulators (Fp8AccumSink): kAccumScaled's contract on a raw-byte archive.  The capacity is in accumulator words, one
+// per decoded byte.  Every tile checks all the element's block descriptors and no tile of a failing element stores.
+// Store buffers on every tile size, as kDelta.
 // (kReduce: decodeReduceTile, below)
-enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats, kReduceNorm, kReduceNormStats, kWholeScaled, kAccumScaled, kUpdate, kDelta };
+enum class DecodeForm { kWhole, kRanged, kAccum, kReduce, kReduceStats, kReduceMixed, kReduceMixedStats, kReduceScaled, kReduceScaledStats, kReduceNorm, kReduceNormStats, kWholeScaled, kAccumScaled, kUpdate, kDelta, kFp8Accum };
 template <int P, uint32_t FT, uint32_t kTileBlocks, DecodeForm kForm>
 __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   constexpr bool kRanged = kForm == DecodeForm::kRanged, kAccumScaled = kForm == DecodeForm::kAccumScaled;
@@ -1145,23 +1227,25 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   constexpr bool kAccum = kForm == DecodeForm::kAccum || kAccumScaled || kUpdate;      // the accumulating forms
   constexpr bool kScaledForm = kForm == DecodeForm::kWholeScaled || kAccumScaled || kUpdate;  // the forms with a factor
   constexpr bool kDelta = kForm == DecodeForm::kDelta;
-  constexpr bool kAllVouch = kAccum || kDelta;  // every tile checks all the element's descriptors: a failing member stores nothing
-  static_assert(kForm == DecodeForm::kWhole || kForm == DecodeForm::kRanged || kAccum || kScaledForm || kDelta,
+  constexpr bool kFp8 = kForm == DecodeForm::kFp8Accum;
+  constexpr bool kAllVouch = kAccum || kDelta || kFp8;  // every tile checks all the element's descriptors: a failing member stores nothing
+  static_assert(kForm == DecodeForm::kWhole || kForm == DecodeForm::kRanged || kAccum || kScaledForm || kDelta || kFp8,
                 "decode-reduce has a body of its own: decodeReduceTile");
   static_assert(!kDelta || FT == 0u, "delta decode: raw bytes only");
+  static_assert(!kFp8 || FT == 0u, "FP8 decode-accumulate: raw bytes only");
   static_assert(!(kAccum || kScaledForm) || FT != 0u, "accumulating and scaled decode: float archives only");
   static_assert(!kUpdate || FT == kFloat16 || FT == kBFloat16, "decode-update: 16-bit float archives only");
   using Sink = std::conditional_t<kUpdate, UpdateSink<kUpdate ? FT : kBFloat16>,
                                   std::conditional_t<kAccum, AccumSink<FT ? FT : kFloat32, 0u, false, false, kAccumScaled>,
                                                      std::conditional_t<kScaledForm, ScaledSink<FT ? FT : kFloat32>,
-                                                                        std::conditional_t<kDelta, DeltaSink, RowSink<FT>>>>>;
+                                                                        std::conditional_t<kDelta, DeltaSink, std::conditional_t<kFp8, Fp8AccumSink, RowSink<FT>>>>>>;
   constexpr uint32_t kDecThreads = decThreads(kTileBlocks);
   // the LUT-build scratch (cdf, pdf: 2 KiB, read while the LUT is stored) sits in the ring area
   static_assert(kTileBlocks * kRingBytes >= 2048u, "");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   // rings: 16 x 2 KiB at LDS offset 0 (2 KiB aligned), then the LUT, then the transposition buffers
   uint2* sLut = (uint2*)(smem + kTileBlocks * kRingBytes);
-  constexpr uint32_t kXpose = decXposeBytes(P, FT, kTileBlocks, kDelta);
+  constexpr uint32_t kXpose = decXposeBytes(P, FT, kTileBlocks, kDelta || kFp8);
 
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
@@ -1240,7 +1324,7 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   const bool blockEarly = FT != 0u && inRange && block < nbSpec && (!extentKnown || (uint64_t)ansOff + ansOverhead(nbSpec) <= inBytes);
   const AnsHeader header = *(const AnsHeader*)ans;
   float factor = 1.0f;  // kScaledForm: the member's factor, in the round trip of the header
-  if constexpr (kScaledForm) factor = a.scalePtr ? a.scalePtr[(size_t)b * a.scaleStride] : a.scale;
+  if constexpr (kScaledForm || kFp8) factor = a.scalePtr ? a.scalePtr[(size_t)b * a.scaleStride] : a.scale;
   uint64_t seed = 0;    // kUpdate: the call's seed, in the same round trip
   if constexpr (kUpdate) seed = a.seedPtr ? *a.seedPtr : a.seed;
   uint2 pdfRaw = make_uint2(0u, 0u);
@@ -1331,6 +1415,7 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   if constexpr (kAccumScaled) sink.preFactor = factor;
   else if constexpr (kScaledForm) sink.factor = factor;
   if constexpr (kUpdate) sink.key = srMemberKey(seed, a.firstMember + b);
+  if constexpr (kFp8) sink.accumulate = a.accumulate, sink.factor = factor, sink.e5m2 = a.fp8E5M2 != 0u;
   // (a half without a block points at its wave's first block: its prefetches must stay inside the archive -- kAccum:
   // and inside the accumulator)
   uint32_t sinkBlock = haveBlock ? block : (block & ~1u);
@@ -1349,7 +1434,7 @@ __device__ __forceinline__ void decodeTile(const DecodeArgs& a) {
   const bool noRing = wFirst <= kRingBytes / 2u && wSecond <= kRingBytes / 2u;
   // (the wide stores cover whole 8-row groups of words that exist; they take any word-aligned output element)
   // (kAccum: accumulators are float-aligned, the host checks it)
-  const bool wide = kXpose != 0 && (kAccum || (((uintptr_t)a.out.ptr(b)) & (decOutWordBytes(FT) - 1u)) == 0);
+  const bool wide = kXpose != 0 && (kAccum || kFp8 || (((uintptr_t)a.out.ptr(b)) & (decOutWordBytes(FT) - 1u)) == 0);
   const bool fullPair = nFirst == kBlockSize && nSecond == kBlockSize;
   // one full block in the wave (odd block counts): fast path with an idle upper half
   const bool fullSingle = nFirst == kBlockSize && nSecond == 0u;
@@ -2131,6 +2216,15 @@ template <int P, uint32_t FT, uint32_t kTileBlocks>
 __global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_delta(DecodeArgs a) {
   static_assert(FT == 0u, "delta decode: raw bytes only");
   decodeTile<P, 0u, kTileBlocks, DecodeForm::kDelta>(a);
+}
+
+// FP8 accumulating form: raw-byte archives of OCP FP8 values into float32 accumulators (decodeTile, kFp8Accum;
+// Fp8AccumSink).  Grid and order as k_ans_decode_accum; LDS decLdsBytes(P, 0, tiles, true).  Raw bytes only; the FP8 type
+// is an argument, so one instantiation serves both.
+template <int P, uint32_t FT, uint32_t kTileBlocks>
+__global__ __launch_bounds__(decThreads(kTileBlocks)) void k_ans_decode_fp8_accum(DecodeArgs a) {
+  static_assert(FT == 0u, "FP8 decode-accumulate: raw bytes only");
+  decodeTile<P, 0u, kTileBlocks, DecodeForm::kFp8Accum>(a);
 }
 
 // Reducing form: grid and order as k_ans_decode_accum, DecodeArgs::numSources archives per accumulator (decodeReduceTile).

@@ -86,7 +86,9 @@ __host__ __device__ constexpr uint32_t encSpillSlotWords(int P) { return roundUp
 // (Raw bytes keep the worst-case stage: a 1664-word stage with spill slots -- 4 workgroups per CU -- measured -2 %
 // for 43 MiB more temp memory, and nothing once the row stored under the ballot; docs/HISTORY.md section 5, "Config 2".)
 // (kCastSource, encIsCast and encArchiveType -- the SOURCE of an encoder / histogram instantiation -- are in plan_constants.h)
-__host__ __device__ constexpr uint32_t encSourceWordBytes(uint32_t ft) { return encArchiveType(ft) == 0u ? 1u : ((ft == kFloat32 || encIsCast(ft)) ? 4u : 2u); }
+__host__ __device__ constexpr uint32_t encSourceWordBytes(uint32_t ft) {
+  return encIsFp8(ft) ? 4u : (encArchiveType(ft) == 0u ? 1u : ((ft == kFloat32 || encIsCast(ft)) ? 4u : 2u));
+}
 
 __host__ __device__ constexpr uint32_t encStageCap(int P, bool spill, uint32_t ft, bool wide = false) {
   return spill ? (encArchiveType(ft) == kFloat16 ? kSpillStageWordsFp16 : (wide ? kSpillStageWordsWide : kSpillStageWords)) : encStageWords(P);
@@ -167,6 +169,13 @@ struct EncodeArgs {
   const uint64_t* seedPtr;
   uint32_t firstMember;
   BatchView base;            // delta source only: the bytes element b is XOR-ed with, base.ptr(b); never written
+  // FP8 source only: member b's words are multiplied by scalePtr[b * scaleStride] (device memory, read when the kernel
+  // runs; stride 0: one factor for the call, 1: one per member) or by `scale` when scalePtr is null, then rounded to
+  // e5m2 (fp8E5M2 != 0) or e4m3fn
+  float scale = 1.0f;
+  const float* scalePtr = nullptr;
+  uint32_t scaleStride = 0;
+  uint32_t fp8E5M2 = 0;
 };
 
 struct TileShared {
@@ -330,6 +339,56 @@ struct ChunkSource<kDeltaSource> {
     comp[0] = x.x; comp[1] = x.y; comp[2] = x.z; comp[3] = x.w;
   }
   __device__ __forceinline__ uint32_t wordAt(uint32_t i) const { return (uint32_t)(in[i] ^ base[i]); }
+  __device__ __forceinline__ uint32_t splitAt(uint32_t, uint32_t w, bool) const { return w; }
+};
+
+// FP8 source (raw-byte archive; dgpu_fp8_cast_compress): the input is float32 WORDS and the symbol of a word is its
+// OCP FP8 byte, fp8Scaled(word, factor) -- the function the FP8 histogram counts with (kernels_stats.h).  The FP8 tensor
+// never exists in memory: a symbol costs 4 bytes of input and nothing else.
+// Chunk shape: 8 rows, as the float32 sources -- a lane owns 8 consecutive words of the 256-symbol chunk, TWO 16-byte
+// loads in flight per lane while the chunk before is coded.  The raw-byte chunk of 16 rows would be four loads, 16
+// registers in flight across a row loop that has none to spare (what ChunkSource<kFloat32> found); with 8 rows the
+// source holds the plain raw encoder's residency.  The lane rounds its 8 words, packs 4 bytes per dword and hands the
+// ring 8 bytes where ChunkSource<0> hands it 16; the row loop, the stage and the archive are the raw-byte encoder's.
+// Tail form: the cast sources' -- each 16-byte piece bounded by loadSliceBounded, no byte beyond the element touched;
+// what a piece holds beyond n is rounded like any word and never coded.  Scalar path (wordAt): the element's own 4
+// bytes per lane and row.  The words may begin at any 4-byte boundary (encVectorLoadsOk).  The input is never written.
+template <>
+struct ChunkSource<kFp8Source> {
+  static constexpr uint32_t kRows = 8;
+  struct Raw { uint4 v[2]; };
+  const uint32_t* in;  // this half's block (4096 float32 words)
+  float factor;        // wave-uniform: the member's
+  bool e5m2;           // wave-uniform: the call's type
+  __device__ __forceinline__ void init(const uint8_t* elemIn, uint8_t*, uint32_t, uint32_t block) {
+    in = (const uint32_t*)elemIn + (size_t)block * kBlockSize;
+  }
+  __device__ __forceinline__ void initCast(float f, bool toE5M2) { factor = f, e5m2 = toE5M2; }
+  __device__ __forceinline__ Raw load(uint32_t c, uint32_t hl) const {
+    const uint4* p = (const uint4*)(in + c * 256u + hl * 8u);
+    Raw r;
+    r.v[0] = streamLoad<kNtEncLoads>(&p[0]);
+    r.v[1] = streamLoad<kNtEncLoads>(&p[1]);
+    return r;
+  }
+  static constexpr uint32_t kCompRegs = 2;
+  __device__ __forceinline__ void splitStore(const Raw& r, uint32_t, uint32_t, uint32_t (&comp)[kCompRegs]) const {
+    comp[0] = fp8Scaled4(r.v[0], factor, e5m2);
+    comp[1] = fp8Scaled4(r.v[1], factor, e5m2);
+  }
+  __device__ __forceinline__ void consume(const Raw& r, uint32_t c, uint32_t hl, uint8_t* ring) const {
+    uint32_t comp[2];
+    splitStore(r, c, hl, comp);
+    *(uint2*)(ring + hl * 8u) = make_uint2(comp[0], comp[1]);
+  }
+  __device__ __forceinline__ Raw loadTail(uint32_t c, uint32_t hl, uint32_t n) const {
+    const uint32_t first = c * 256u + hl * 8u;
+    Raw r;
+    loadSliceBounded<2>((const uint8_t*)in, first * 4u, n * 4u, r.v);
+    return r;
+  }
+  __device__ __forceinline__ void consumeTail(const Raw& r, uint32_t c, uint32_t hl, uint8_t* ring, uint32_t) const { consume(r, c, hl, ring); }
+  __device__ __forceinline__ uint32_t wordAt(uint32_t i) const { return fp8Scaled(in[i], factor, e5m2); }
   __device__ __forceinline__ uint32_t splitAt(uint32_t, uint32_t w, bool) const { return w; }
 };
 
@@ -1336,6 +1395,7 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
   static_assert(!encIsStochastic(FT) || (encIsCast(FT) && !encIsFeedback(FT) && kSpill && !kWide && !kCount),
                 "the stochastic source is a cast source; no counting and no feedback form");
   static_assert(!encIsDelta(FT) || (FT == kDeltaSource && !kSpill && !kWide && !kCount), "the delta source is a raw-byte source; no counting form");
+  static_assert(!encIsFp8(FT) || (FT == kFp8Source && !kSpill && !kWide && !kCount), "the FP8 source is a raw-byte source; no counting form");
   static_assert(!kCount || (kSpill && kPersistent && !kWide && (encArchiveType(FT) == kFloat16 || encArchiveType(FT) == kBFloat16)),
                 "the counting form exists for persistent 16-bit float tiles");
   constexpr uint32_t kCountSlots = kCount ? encCountSlots(kTB) : 0u;
@@ -1505,6 +1565,8 @@ __global__ __launch_bounds__(encThreads(kTB)) __attribute__((amdgpu_waves_per_eu
         src.initResidual(haveResidual ? a.resIn.ptr(b) : nullptr, a.resOut.ptr(b), haveBlock ? block : (waveHalf ? firstBlockOfWave : 0u));
       }
       if constexpr (encIsDelta(FT)) src.initBase(a.base.ptr(b), haveBlock ? block : (waveHalf ? firstBlockOfWave : 0u));
+      // (the member's factor, once per tile, from where the histogram read it)
+      if constexpr (encIsFp8(FT)) src.initCast(a.scalePtr ? a.scalePtr[(size_t)b * a.scaleStride] : a.scale, a.fp8E5M2 != 0u);
       // (the member's key, once per tile: consecutive tiles of a persistent workgroup belong to different elements)
       if constexpr (encIsStochastic(FT)) src.setKey(srMemberKey(a.seedPtr ? *a.seedPtr : a.seed, a.firstMember + b));
 

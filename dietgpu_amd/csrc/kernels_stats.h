@@ -408,6 +408,11 @@ struct HistFuse {
   const uint64_t* seedPtr;
   uint32_t firstMember;
   BatchView base;  // delta form of k_histogram only: the bytes every element is XOR-ed with before it is counted
+  // FP8 form of k_histogram only: as EncodeArgs::scale / scalePtr / scaleStride / fp8E5M2
+  float scale = 1.0f;
+  const float* scalePtr = nullptr;
+  uint32_t scaleStride = 0;
+  uint32_t fp8E5M2 = 0;
 };
 
 // Which (element, part of how many) a histogram workgroup counts, and where its partial histogram goes.
@@ -548,6 +553,58 @@ __device__ __forceinline__ uint32_t castRoundStochastic(uint32_t x, uint32_t r16
   }
 }
 
+// float32 -> OCP FP8 byte (dgpu_fp8_cast_compress: ChunkSource<kFp8Source>, the FP8 form of k_histogram) -- one helper,
+// so that the histogram and the encoder cannot disagree about a word.  `x` are the float32 bits, e5m2 is wave-uniform
+// (false: e4m3fn), and the constants it selects live in scalar registers.  Integer rounding on the bits, not
+// v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32: what those leave for overflow and NaN depends on the clamp mode, and e4m3fn must
+// NOT saturate here.
+//   * |x| is clamped to the first value of no finite code -- e4m3fn 480 (whose rounding below IS 0x7f, the NaN: there
+//     is no infinity and no saturation; the tie 464 rounds to even, 0x7e = 448), e5m2 65536 (0x7c, the infinity; the tie
+//     61440 rounds there too);
+//   * normals: re-biased, (bits + half - 1 + lsb) >> (23 - mantissa bits), nearest even; the carry walks into the
+//     exponent;
+//   * below the smallest normal (e4m3fn 2^-6, e5m2 2^-14): ONE float32 add to the power of two whose last place is the
+//     denormal step (2^14: 2^-9; 2^7: 2^-16) rounds to nearest even in the adder, and the bits above that power are the
+//     code; a float32 denormal is absorbed whether or not the adder flushes it;
+//   * NaN: 0x7f; the sign bit is kept everywhere, for zeros too.
+// fp8Scaled: the word is first multiplied by the call's factor, ONE IEEE float32 multiply that nothing is fused into.
+__device__ __forceinline__ uint32_t fp8Round(uint32_t x, bool e5m2) {
+#pragma clang fp contract(off)
+  const uint32_t shift = e5m2 ? 21u : 20u;
+  const uint32_t top = e5m2 ? 0x47800000u : 0x43f00000u;
+  const uint32_t minNormal = e5m2 ? (113u << 23) : (121u << 23);
+  const uint32_t magic = e5m2 ? (134u << 23) : (141u << 23);
+  const uint32_t rebias = e5m2 ? 0xc80fffffu : 0xc407ffffu;  // (bias - 127) << 23, plus half a last place less one
+  const uint32_t a = x & 0x7fffffffu;
+  const uint32_t c = a < top ? a : top;
+  const uint32_t normal = (c + rebias + ((c >> shift) & 1u)) >> shift;
+  const uint32_t denormal = __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, c) + __builtin_bit_cast(float, magic)) - magic;
+  uint32_t r = c < minNormal ? denormal : normal;
+  r = a > 0x7f800000u ? 0x7fu : r;
+  return r | ((x >> 24) & 0x80u);
+}
+__device__ __forceinline__ uint32_t fp8Scaled(uint32_t x, float s, bool e5m2) {
+#pragma clang fp contract(off)
+  const float v = __builtin_bit_cast(float, x) * s;
+  return fp8Round(__builtin_bit_cast(uint32_t, v), e5m2);
+}
+// four words -> one dword of four FP8 bytes (x0's lowest)
+__device__ __forceinline__ uint32_t fp8Scaled4(uint4 x, float s, bool e5m2) {
+  const uint32_t lo = fp8Scaled(x.x, s, e5m2) | (fp8Scaled(x.y, s, e5m2) << 8);
+  const uint32_t hi = fp8Scaled(x.z, s, e5m2) | (fp8Scaled(x.w, s, e5m2) << 8);
+  return lo | (hi << 16);
+}
+// OCP FP8 byte -> float32 (exact; dgpu_fp8_decode_accumulate, Fp8AccumSink).  An e5m2 byte is the high byte of a float16;
+// an e4m3fn byte moved one bit down is a float16 with 2^-8 of its value, denormals included -- v_cvt_f32_f16 widens
+// both, float16 denormals to float32 normals -- and the one e4m3fn code the float16 does not know, the NaN, is set apart.
+__device__ __forceinline__ float fp8Widen(uint32_t b, bool e5m2) {
+#pragma clang fp contract(off)
+  const uint32_t h = e5m2 ? (b << 8) : (((b & 0x7fu) << 7) | ((b & 0x80u) << 8));
+  const float f = (float)__builtin_bit_cast(_Float16, (uint16_t)h) * (e5m2 ? 1.0f : 256.0f);
+  const bool nan = !e5m2 && (b & 0x7fu) == 0x7fu;
+  return nan ? __builtin_bit_cast(float, 0x7fc00000u | ((b & 0x80u) << 24)) : f;
+}
+
 // Histogram kernel: 16-byte loads with a byte-wise head/tail so any start
 // alignment works (the reference test uses stride size+11,
 // ANSStatisticsTest.cu:52-57).  grid = (xBlocks, B), 256 threads.
@@ -610,8 +667,18 @@ __device__ __forceinline__ void histStore(uint32_t* __restrict__ hist, uint32_t 
 // histograms, the atomic counters of one or two large elements, both lane-slot counts, both load policies, the fused
 // normalisation -- is a run-time path or a template parameter beside kDelta, so each exists in the delta form.  The pass
 // only reads.
-template <uint32_t S, bool kNt = true, bool kDelta = false>
+// kFp8 (the FP8 form, dgpu_fp8_cast_compress): the element is float32 WORDS, in.size(b) of them, and the byte counted for a
+// word is fp8Scaled(word, factor) -- the encoder's own function, with the factor both kernels read from the same place
+// (fuse.scalePtr: device memory, or fuse.scale).  A 16-byte vector holds FOUR symbols where the plain form's holds
+// sixteen: head, parts and tail are counted in symbols with that vector size, the loop keeps four loads in flight per
+// lane, and the bytes go from the registers they are rounded in straight to the bins (they are never packed).  The
+// words may begin at any 4-byte boundary.  Every run-time path of the plain kernel exists in this form, as in the delta
+// form.  The pass only reads.
+template <uint32_t S, bool kNt = true, bool kDelta = false, bool kFp8 = false>
 __global__ __launch_bounds__(256) void k_histogram(BatchView in, uint32_t* __restrict__ hist, uint32_t partial, HistFuse fuse) {
+  static_assert(!(kDelta && kFp8), "");
+  constexpr uint32_t kSymBytes = kFp8 ? 4u : 1u;        // input bytes per symbol
+  constexpr uint32_t kVecSyms = 16u / kSymBytes;        // symbols per 16-byte vector
   __shared__ uint32_t bins[kNumSymbols * S];
   const uint32_t tid = threadIdx.x;
   const HistWork w = histWorkOf(fuse, in, 1u);
@@ -624,15 +691,21 @@ __global__ __launch_bounds__(256) void k_histogram(BatchView in, uint32_t* __res
   const uint32_t size = in.size(b);
   [[maybe_unused]] const uint8_t* q = p;  // kDelta: the element's base
   if constexpr (kDelta) q = fuse.base.ptr(b);
+  [[maybe_unused]] float factor = 1.0f;   // kFp8: the member's factor
+  [[maybe_unused]] const bool e5m2 = fuse.fp8E5M2 != 0u;
+  if constexpr (kFp8) factor = fuse.scalePtr ? fuse.scalePtr[(size_t)b * fuse.scaleStride] : fuse.scale;
 
-  // bytes before the first 16-byte boundary
-  uint32_t head = (uint32_t)((16u - ((uintptr_t)p & 15u)) & 15u);
+  // symbols before the first 16-byte boundary
+  uint32_t head = (uint32_t)((16u - ((uintptr_t)p & 15u)) & 15u) / kSymBytes;
   head = head < size ? head : size;
   const uint32_t remaining = size - head;
-  const uint32_t numVec = remaining / 16u;
-  const uint4* pv = (const uint4*)(p + head);
+  const uint32_t numVec = remaining / kVecSyms;
+  const uint4* pv = (const uint4*)(p + (size_t)head * kSymBytes);
   [[maybe_unused]] const uint4* qv = (const uint4*)(q + head);
-  auto byteAt = [&](uint32_t i) -> uint32_t { return kDelta ? (uint32_t)(p[i] ^ q[i]) : (uint32_t)p[i]; };
+  auto byteAt = [&](uint32_t i) -> uint32_t {
+    if constexpr (kFp8) return fp8Scaled(((const uint32_t*)p)[i], factor, e5m2);
+    else return kDelta ? (uint32_t)(p[i] ^ q[i]) : (uint32_t)p[i];
+  };
   auto vecAt = [&](uint32_t i) -> uint4 {
     uint4 v = streamLoad<kNt>(&pv[i]);
     if constexpr (kDelta) {
@@ -640,6 +713,17 @@ __global__ __launch_bounds__(256) void k_histogram(BatchView in, uint32_t* __res
       v = make_uint4(v.x ^ d.x, v.y ^ d.y, v.z ^ d.z, v.w ^ d.w);
     }
     return v;
+  };
+  // the symbols of one vector into the bins
+  auto addVec = [&](const uint4& v) {
+    if constexpr (kFp8) {
+      histAdd<S>(myBins, fp8Scaled(v.x, factor, e5m2));
+      histAdd<S>(myBins, fp8Scaled(v.y, factor, e5m2));
+      histAdd<S>(myBins, fp8Scaled(v.z, factor, e5m2));
+      histAdd<S>(myBins, fp8Scaled(v.w, factor, e5m2));
+    } else {
+      histAdd4<S>(myBins, v.x); histAdd4<S>(myBins, v.y); histAdd4<S>(myBins, v.z); histAdd4<S>(myBins, v.w);
+    }
   };
 
   if (w.part == 0 && tid < head) histAdd<S>(myBins, byteAt(tid));
@@ -652,21 +736,15 @@ __global__ __launch_bounds__(256) void k_histogram(BatchView in, uint32_t* __res
   uint32_t i = vBegin + tid;
   for (; i + 768u < vEnd; i += 1024u) {
     const uint4 v0 = vecAt(i), v1 = vecAt(i + 256u), v2 = vecAt(i + 512u), v3 = vecAt(i + 768u);
-    histAdd4<S>(myBins, v0.x); histAdd4<S>(myBins, v0.y); histAdd4<S>(myBins, v0.z); histAdd4<S>(myBins, v0.w);
-    histAdd4<S>(myBins, v1.x); histAdd4<S>(myBins, v1.y); histAdd4<S>(myBins, v1.z); histAdd4<S>(myBins, v1.w);
-    histAdd4<S>(myBins, v2.x); histAdd4<S>(myBins, v2.y); histAdd4<S>(myBins, v2.z); histAdd4<S>(myBins, v2.w);
-    histAdd4<S>(myBins, v3.x); histAdd4<S>(myBins, v3.y); histAdd4<S>(myBins, v3.z); histAdd4<S>(myBins, v3.w);
+    addVec(v0);
+    addVec(v1);
+    addVec(v2);
+    addVec(v3);
   }
-  for (; i < vEnd; i += 256u) {
-    const uint4 v = vecAt(i);
-    histAdd4<S>(myBins, v.x);
-    histAdd4<S>(myBins, v.y);
-    histAdd4<S>(myBins, v.z);
-    histAdd4<S>(myBins, v.w);
-  }
+  for (; i < vEnd; i += 256u) addVec(vecAt(i));
 
   if (w.part == 0) {
-    uint32_t t = numVec * 16u + tid;
+    uint32_t t = numVec * kVecSyms + tid;
     if (t < remaining) histAdd<S>(myBins, byteAt(head + t));
   }
   __syncthreads();

@@ -43,9 +43,19 @@ DGPU_HD constexpr bool encIsStochastic(uint32_t ft) { return (ft & kStochasticSo
 // as the raw-byte call, but like the cast sources without single-block kernels: such elements run on 2-block tiles.
 constexpr uint32_t kDeltaSource = 0x1000u;
 DGPU_HD constexpr bool encIsDelta(uint32_t ft) { return (ft & kDeltaSource) != 0u; }
-DGPU_HD constexpr uint32_t encArchiveType(uint32_t ft) { return ft & ~(kCastSource | kCountingSource | kFeedbackSource | kStochasticSource | kDeltaSource); }
+// kFp8Source (with archive type 0, raw bytes): the symbols are float32 words, multiplied by a factor and rounded to an
+// OCP FP8 type in registers (kernels_stats.h, fp8Round; kernels_encode.h, ChunkSource<kFp8Source>; the FP8 form of
+// k_histogram).  The HOST's source word also carries WHICH type -- kFp8E5M2 set: e5m2, clear: e4m3fn -- which reaches
+// the kernels as an argument, not as a template parameter: one instantiation serves both.  Planned as the delta call:
+// the raw-byte plan without single-block kernels.
+constexpr uint32_t kFp8Source = 0x2000u;
+constexpr uint32_t kFp8E5M2 = 0x4000u;
+DGPU_HD constexpr bool encIsFp8(uint32_t ft) { return (ft & kFp8Source) != 0u; }
+DGPU_HD constexpr uint32_t encArchiveType(uint32_t ft) {
+  return ft & ~(kCastSource | kCountingSource | kFeedbackSource | kStochasticSource | kDeltaSource | kFp8Source | kFp8E5M2);
+}
 // whether single-block elements of such a call have kernels of their own (k_ans_encode_pair, k_stats_single)
-DGPU_HD constexpr bool encHasSingleBlockKernels(uint32_t ft) { return (ft & (kCastSource | kCountingSource | kDeltaSource)) == 0u && ft != kFloat32; }
+DGPU_HD constexpr bool encHasSingleBlockKernels(uint32_t ft) { return (ft & (kCastSource | kCountingSource | kDeltaSource | kFp8Source)) == 0u && ft != kFloat32; }
 
 // Encoder: blocks per tile = per workgroup.  8 (256 threads: 4 wave64 x 2 half-waves); 4 (128 threads) for batches whose
 // elements have at most 4 blocks -- an 8-block tile would leave half of its waves without a block there; a single

@@ -821,6 +821,67 @@ int64_t decompress_data_delta(
   return 0;
 }
 
+// FP8 archives (no reference ops; dgpu_fp8_cast_compress / dgpu_fp8_decode_accumulate).  fp8_type: 0 = float8_e4m3fn,
+// 1 = float8_e5m2.  scale / scale_dev as in decompress_data_accumulate_scaled.
+// compress_data(False, ...) of (ts_in[i] * s).to(float8), multiplied and rounded in the kernels.  -> (comp, sizes).
+std::tuple<at::Tensor, at::Tensor> compress_data_fp8(
+    const std::vector<at::Tensor>& tIns, int64_t fp8Type, double scale, const std::optional<at::Tensor>& scaleDev,
+    const std::optional<at::Tensor>& outCompressed, const std::optional<at::Tensor>& outCompressedSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(fp8Type == (int64_t)DGPU_FP8_E4M3FN || fp8Type == (int64_t)DGPU_FP8_E5M2, "dietgpu: fp8_type must be 0 (float8_e4m3fn) or 1 (float8_e5m2)");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  const size_t n = tIns.size();
+  std::vector<const void*> inPtrs(n);
+  std::vector<uint32_t> inSize(n);
+  uint64_t maxWords = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const at::Tensor& t = tIns[i];
+    TORCH_CHECK(t.device().is_cuda() && t.get_device() == dev && t.is_contiguous());
+    TORCH_CHECK(t.scalar_type() == at::ScalarType::Float, "dietgpu: the inputs of a cast call must be float32");
+    TORCH_CHECK((uint64_t)t.numel() <= std::numeric_limits<uint32_t>::max());
+    inPtrs[i] = t.data_ptr();
+    inSize[i] = (uint32_t)t.numel();
+    maxWords = std::max<uint64_t>(maxWords, inSize[i]);
+  }
+  uint32_t stride = 0;
+  const float* factors = scaleFactors(scaleDev, n, dev, &stride);
+  at::Tensor comp, sizes;
+  validateCompOut(outCompressed, outCompressedSizes, (int64_t)n, (int64_t)maxAnsSize(maxWords), dev, tIns[0].device(), comp, sizes);
+  std::vector<void*> compPtrs(n);
+  for (size_t i = 0; i < n; ++i) compPtrs[i] = (uint8_t*)comp.data_ptr() + i * comp.size(1);
+  check(dgpu_fp8_cast_compress((uint32_t)fp8Type, precision(), (uint32_t)n, inPtrs.data(), inSize.data(), (float)scale, factors, stride,
+                               compPtrs.data(), (uint32_t*)sizes.data_ptr(), streamOf(dev)),
+        "fp8CompressCast", false);
+  return {std::move(comp), std::move(sizes)};
+}
+
+// ts_acc[i] = [ts_acc[i] +] float32(decoded FP8 bytes of ts_in[i]) * s.  -> 0 (no temp memory).
+int64_t decompress_data_accumulate_fp8(
+    const std::vector<at::Tensor>& tIns, const std::vector<at::Tensor>& tAccs, int64_t fp8Type, bool accumulate, double scale,
+    const std::optional<at::Tensor>& scaleDev, const std::optional<at::Tensor>& outStatus, const std::optional<at::Tensor>& outSizes) {
+  TORCH_CHECK(!tIns.empty());
+  TORCH_CHECK(tIns.size() == tAccs.size());
+  TORCH_CHECK(tIns.front().device().is_cuda(), "dietgpu: tensors must be on the GPU");
+  TORCH_CHECK(fp8Type == (int64_t)DGPU_FP8_E4M3FN || fp8Type == (int64_t)DGPU_FP8_E5M2, "dietgpu: fp8_type must be 0 (float8_e4m3fn) or 1 (float8_e5m2)");
+  int dev = tIns.front().get_device();
+  c10::hip::HIPGuard guard(dev);
+  const size_t n = tIns.size();
+  // (capacities in accumulator words, as a float call's)
+  DecodeTensors m = marshalDecode(true, tIns, tAccs, dev, [&](size_t i) {
+    TORCH_CHECK(tAccs[i].scalar_type() == at::ScalarType::Float, "dietgpu: accumulators must be float32");
+  });
+  uint32_t stride = 0;
+  const float* factors = scaleFactors(scaleDev, n, dev, &stride);
+  validateStatus(outStatus, outSizes, (int64_t)n, dev);
+  check(dgpu_fp8_decode_accumulate((uint32_t)fp8Type, precision(), accumulate ? 1 : 0, (uint32_t)n, m.inPtrs.data(), m.inBytes.data(), (float)scale,
+                                   factors, stride, m.outPtrs.data(), m.outCapacity.data(), ptrOrNull<uint8_t>(outStatus),
+                                   ptrOrNull<uint32_t>(outSizes), streamOf(dev)),
+        "fp8DecompressAccumulate", false);
+  return 0;
+}
+
 // Rolling-table compress (no reference op): compress_data / compress_data_cast with the tables made from the counts the
 // last call left (counts_in) and this call's counts taken by the encoder (counts_out): dgpu_float_rolling_compress.
 // float_type (1 = float16, 2 = bfloat16) is that of the archives; source_float32: ts_in are float32 and are rounded.
@@ -1148,6 +1209,12 @@ TORCH_LIBRARY(dietgpu_amd, m) {
   m.def(
       "decompress_data_delta(Tensor[] ts_in, Tensor[] ts_base, Tensor[] ts_out, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
       &dietgpu_amd::decompress_data_delta);
+  m.def(
+      "compress_data_fp8(Tensor[] ts_in, int fp8_type, float scale=1.0, Tensor? scale_dev=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor)",
+      &dietgpu_amd::compress_data_fp8);
+  m.def(
+      "decompress_data_accumulate_fp8(Tensor[] ts_in, Tensor[] ts_acc, int fp8_type, bool accumulate, float scale=1.0, Tensor? scale_dev=None, Tensor? out_status=None, Tensor? out_sizes=None) -> int",
+      &dietgpu_amd::decompress_data_accumulate_fp8);
   m.def(
       "compress_data_rolling(Tensor[] ts_in, Tensor? counts_in, Tensor? counts_out, int float_type, bool source_float32=False, Tensor? temp_mem=None, Tensor? out_compressed=None, Tensor? out_compressed_sizes=None) -> (Tensor, Tensor, int)",
       &dietgpu_amd::compress_data_rolling);

@@ -38,11 +38,11 @@ struct LaunchGroup {
 
 // ---- Geometry ----
 // blocks per encoder tile for a batch whose largest element has `maxSize` symbols; ft: what is encoded (0: raw bytes; a
-// float type, with kCastSource for a cast call or kCountingSource for a counting one; kDeltaSource for a delta call of
-// raw bytes -- these have no single-block kernels: their single-block elements run on 2-block tiles)
+// float type, with kCastSource for a cast call or kCountingSource for a counting one; kDeltaSource for a delta call and
+// kFp8Source for an FP8 cast call of raw bytes -- these have no single-block kernels: their single-block elements run on 2-block tiles)
 inline uint32_t encTileBlocksFor(uint32_t maxSize, uint32_t ft = 0) {
   const uint32_t blocks = divUp(maxSize, kBlockSize);
-  if ((ft & (kCastSource | kCountingSource | kDeltaSource)) != 0u && blocks <= kBlocksPerTinyTile) return kBlocksPerTinyTile;
+  if ((ft & (kCastSource | kCountingSource | kDeltaSource | kFp8Source)) != 0u && blocks <= kBlocksPerTinyTile) return kBlocksPerTinyTile;
   return blocks <= kBlocksPerSingleTile ? kBlocksPerSingleTile
       : blocks <= kBlocksPerTinyTile    ? kBlocksPerTinyTile
       : blocks <= kBlocksPerSmallTile   ? kBlocksPerSmallTile

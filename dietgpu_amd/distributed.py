@@ -142,14 +142,17 @@ class GpuFloatCodec:
         self.dtype = tensors[0].dtype  # (what decompress_accumulate's rows hold: the collectives exchange one dtype)
         return comp, sizes
 
-    def compress_cast(self, tensors, dtype):
-        """float32 tensors -> archives of `dtype` (float16 / bfloat16), rounded in registers: no 16-bit scratch tensor"""
+    def compress_cast(self, tensors, dtype, scale=None):
+        """float32 tensors -> archives of `dtype` (float16 / bfloat16), rounded in registers: no 16-bit scratch tensor.
+        `dtype` float8_e4m3fn / float8_e5m2: raw-byte archives of the FP8 values of tensors[i] * `scale`
+        (ops.compress_data_cast's `scale`: a number, or a float32 tensor on the device that the host never reads), which
+        decompress_accumulate then widens; these do not use the rolling tables (the FP8 encoder has no counting form)"""
         from . import ops
 
         self.dtype = dtype
-        if self.rolling:
+        if self.rolling and scale is None and dtype in (torch.float16, torch.bfloat16):
             return self._compress_rolling(tensors, dtype, True)
-        comp, sizes, _ = ops.compress_data_cast(tensors, dtype, self.temp_mem)
+        comp, sizes, _ = ops.compress_data_cast(tensors, dtype, self.temp_mem, scale=scale)
         return comp, sizes
 
     def compress_cast_feedback(self, tensors, residuals, dtype, fresh=False):

@@ -338,21 +338,56 @@ def compress_data_simple(compress_as_float, ts_in, checksum=False, temp_mem=6710
 
 # ---------------------------------------------------------------- cast-compress
 # (no reference op: dgpu_float_cast_compress, include/dietgpu_amd.h)
+_DTYPE_TO_FP8 = {torch.float8_e4m3fn: 0, torch.float8_e5m2: 1}  # DGPU_FP8_E4M3FN, DGPU_FP8_E5M2
+
+
+def _compress_data_fp8(ts_in, dtype, scale, out_compressed, out_compressed_sizes, prob_bits):
+    """compress_data_cast to an FP8 dtype (dgpu_fp8_cast_compress) -> (comp, sizes, 0)."""
+    host, dev_scale = _scale_arg(scale, len(ts_in))
+    dev = ts_in[0].get_device()
+    _check(dev_scale is None or dev_scale.get_device() == dev, "a tensor scale must be on the tensors' GPU")
+    host = 1.0 if host is None else host
+    op = _amd_op(prob_bits, "compress_data_fp8")
+    if op is not None:
+        return (*op(ts_in, _DTYPE_TO_FP8[dtype], host, dev_scale, out_compressed, out_compressed_sizes), 0)
+    _, mx = _total_and_max(ts_in)
+    rows, cols = len(ts_in), max_any_compressed_size(mx)
+    with torch.cuda.device(dev):
+        comp, sizes = _validate_out(out_compressed, out_compressed_sizes, rows, cols, dev, ts_in[0].device)
+        row = comp.size(1)
+        out_ptrs = (C.c_void_p * rows)(*[comp.data_ptr() + i * row for i in range(rows)])
+        check(lib().dgpu_fp8_cast_compress(
+            _DTYPE_TO_FP8[dtype], prob_bits, rows, _ptr_array(ts_in), _u32_array([t.numel() for t in ts_in]), host,
+            _ptr(dev_scale), 0 if dev_scale is None or dev_scale.numel() == 1 else 1, out_ptrs, _ptr(sizes), _stream()))
+    return comp, sizes, 0
+
+
 def compress_data_cast(ts_in, dtype, temp_mem=None, out_compressed=None, out_compressed_sizes=None,
-                       prob_bits=K_DEFAULT_PRECISION):
+                       prob_bits=K_DEFAULT_PRECISION, scale=None):
     """Compresses float32 tensors into ordinary float16 / bfloat16 archives (`dtype`: of the archives): every word is
     rounded to `dtype` in registers -- round to nearest even, NaN to the canonical quiet NaN with its sign -- and the
     archive is byte for byte what `compress_data(True, [t.to(dtype)])` writes for the rounded tensor, without the
     16-bit scratch tensor -> (comp [B, maxSize] u8, sizes [B] i32, temp bytes used), as compress_data.  ts_in is not
-    modified.  There is no `checksum`: a checksum covers the 16-bit words, which never reach memory here."""
+    modified.  There is no `checksum`: a checksum covers the 16-bit words, which never reach memory here.
+
+    `dtype` torch.float8_e4m3fn / torch.float8_e5m2 (dgpu_fp8_cast_compress): every word is multiplied by `scale` -- one
+    IEEE float32 multiply; a number or a float32 CUDA tensor of 1 or len(ts_in) elements that the kernels read, as the
+    `scale` of decompress_data_accumulate; None: no factor -- and rounded to the FP8 type as torch's CPU cast rounds it
+    (nearest even, denormals produced, e4m3fn overflow to NaN, e5m2 to infinity: no saturation).  The archive is byte for
+    byte what `compress_data(False, [(t * s).to(dtype).view(torch.uint8)])` writes, an ordinary raw-byte archive.  No temp
+    memory is used (temp_mem is ignored).  `scale` is for these two dtypes only."""
     _check(len(ts_in) > 0)
-    _check(dtype in (torch.float16, torch.bfloat16), "dtype (of the archives) must be float16 or bfloat16")
+    fp8 = dtype in _DTYPE_TO_FP8
+    _check(fp8 or dtype in (torch.float16, torch.bfloat16), "dtype (of the archives) must be float16 or bfloat16")
+    _check(fp8 or scale is None, "scale: the float16 / bfloat16 cast kernels have no factor (float8 dtypes only)")
     _check(ts_in[0].is_cuda, "tensors must be on the GPU")
-    ft = _DTYPE_TO_FT[dtype]
     dev = ts_in[0].get_device()
     for t in ts_in:
         _check(t.is_cuda and t.is_contiguous() and t.get_device() == dev)
         _check(t.dtype == torch.float32, "the inputs of a cast call must be float32")
+    if fp8:
+        return _compress_data_fp8(ts_in, dtype, scale, out_compressed, out_compressed_sizes, prob_bits)
+    ft = _DTYPE_TO_FT[dtype]
     op = _amd_op(prob_bits, "compress_data_cast")
     if op is not None:
         return op(ts_in, ft, temp_mem, out_compressed, out_compressed_sizes)
@@ -794,7 +829,11 @@ def decompress_data_accumulate(ts_in, ts_acc, accumulate=True, temp_mem=None, ou
     call without it); a float32 CUDA tensor on the tensors' device, contiguous, with 1 element (one factor for the call)
     or len(ts_in) elements (one per archive) is read by the kernel when it runs and never by the host: it may hold any
     value (a 1 multiplies), may be the result of work enqueued before this call, and a captured call follows the value it
-    holds at each replay."""
+    holds at each replay.
+
+    `dtype` torch.float8_e4m3fn / torch.float8_e5m2 (dgpu_fp8_decode_accumulate): ts_in[i] is a RAW-BYTE archive of values
+    of that type, as compress_data_cast(dtype=float8) writes; every decoded byte is widened to float32 (exact),
+    multiplied by the factor and stored or added as above.  The type is never read from the archive, which has none."""
     _check(len(ts_in) > 0)
     _check(len(ts_in) == len(ts_acc))
     host, dev_scale = _scale_arg(scale, len(ts_in))
@@ -808,6 +847,17 @@ def decompress_data_accumulate(ts_in, ts_acc, accumulate=True, temp_mem=None, ou
         _check(ta.numel() <= _U32_MAX)
     n = len(ts_in)
     _validate_status(out_status, out_sizes, n, dev)
+    if dtype in _DTYPE_TO_FP8:
+        host = 1.0 if host is None else host
+        op = _amd_op(prob_bits, "decompress_data_accumulate_fp8")
+        if op is not None:
+            return op(ts_in, ts_acc, _DTYPE_TO_FP8[dtype], bool(accumulate), host, dev_scale, out_status, out_sizes)
+        with torch.cuda.device(dev):
+            check(lib().dgpu_fp8_decode_accumulate(
+                _DTYPE_TO_FP8[dtype], prob_bits, int(bool(accumulate)), n, _ptr_array(ts_in), _in_bytes(ts_in), host,
+                _ptr(dev_scale), 0 if dev_scale is None or dev_scale.numel() == 1 else 1, _ptr_array(ts_acc),
+                _u32_array([t.numel() for t in ts_acc]), _ptr(out_status), _ptr(out_sizes), _stream()))
+        return 0
     with torch.cuda.device(dev):
         tp, tb = _temp(temp_mem, dev)
         if dtype is not None:

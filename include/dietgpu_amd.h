@@ -75,7 +75,7 @@ const char* dgpu_version(void);
  * dgpu_float_decode_scaled were added at version 8, dgpu_float_feedback_compress and
  * dgpu_float_decode_accumulate_scaled after them, dgpu_float_decode_update after those,
  * dgpu_float_stochastic_compress after dgpu_float_decode_update, dgpu_ans_delta_encode and dgpu_ans_delta_decode after
- * that). */
+ * that, dgpu_fp8_cast_compress and dgpu_fp8_decode_accumulate after those). */
 #define DGPU_ABI_VERSION 8u
 uint32_t dgpu_abi_version(void);
 /* Text of the last error on the calling thread (HIP error string, failed
@@ -616,6 +616,56 @@ int dgpu_ans_delta_encode(
 int dgpu_ans_delta_decode(
     int probBits, uint32_t numInBatch, const void* const* in, const uint32_t* inBytes, const void* const* base,
     void* const* out, const uint32_t* outCapacity /* bytes */, uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
+
+/* ---- FP8 archives (no upstream equivalent) -------------------------------------------------
+ * The FP8 wire of a compressed exchange of float32 gradients: the sender rounds every word to an OCP FP8 type and
+ * entropy-codes the bytes in ONE call, the receiver decodes, widens and adds in one.  The FP8 tensor never exists in
+ * memory on either side.  fp8Type: */
+#define DGPU_FP8_E4M3FN 0u /* 1-4-3, bias 7, no infinity, one NaN per sign (0x7f), largest finite 448 */
+#define DGPU_FP8_E5M2 1u   /* 1-5-2, bias 15, IEEE-like: infinity 0x7c, NaN 0x7d..0x7f, largest finite 57344 */
+/* dgpu_fp8_cast_compress: out[i] / outSize_dev[i] are byte for byte what dgpu_ans_encode_batch_pointer(useChecksum = 0,
+ * no caller histogram) writes for the bytes q[k] = fp8(fl32(in[i][k] * s_i)), k < inSize[i]: an ORDINARY raw-byte ANS
+ * archive, no checksum, no new format, that every raw-byte decoder of this header reads; at most
+ * dgpu_ans_max_compressed_size(inSize[i]) bytes.
+ *   - The product is ONE IEEE float32 multiply, rounded once, never fused.  s_i is scale_dev[scalePerMember ? i : 0]
+ *     when scale_dev is given -- device memory, 4-byte aligned, read by the kernels when they run and never by the host,
+ *     any value, so the factor may be written by work enqueued before the call and a captured call follows the memory at
+ *     every replay -- else the host float `scale`, which must be finite and not zero (1.0f: no factor).
+ *   - fp8() is the conversion of a float32 to the type as the reference CPU cast of PyTorch performs it:
+ *       * round to nearest, ties to even, also into and inside the denormals (e4m3fn: steps of 2^-9, so 2^-10 rounds to
+ *         0; e5m2: steps of 2^-16); a zero keeps its sign;
+ *       * e4m3fn: 464 (the tie above 448) gives 0x7e; anything that rounds beyond 448, and an infinity, gives the NaN
+ *         sign | 0x7f -- there is NO saturation; a NaN gives sign | 0x7f;
+ *       * e5m2: overflow (from the tie 61440 on) and an infinity give sign | 0x7c; a NaN gives sign | 0x7f.
+ *     The histogram pass and the encoder each read the float32 words and round them in registers, with one function.
+ *   - in[i] is 4-byte aligned (anywhere modulo 16), holds inSize[i] float32 words and is never written.  out[i] is
+ *     16-byte aligned.  fp8Type one of the two above, probBits 9 / 10 / 11, numInBatch <= 65535, scalePerMember 0 or 1,
+ *     inSize[i] within the size guard of dgpu_ans_encode_batch_pointer, no array null when numInBatch > 0:
+ *     DGPU_ERR_INVALID_ARGUMENT with a dgpu_last_error() text otherwise, before anything is enqueued.  An empty batch
+ *     returns 0.
+ *   - Planned as dgpu_ans_delta_encode: the raw-byte plan, single-block elements on the 2-block tiles.
+ *
+ * dgpu_fp8_decode_accumulate: the contract of dgpu_float_decode_accumulate_scaled on the raw-byte archive in[i] of
+ * inBytes[i] bytes whose bytes are values of fp8Type.  Every decoded byte is widened to float32 (exact: every FP8 value
+ * is a float32; a NaN byte gives a NaN), multiplied by s_i (as above; ONE IEEE multiply, never fused with the add) and
+ * stored to acc[i][k] (accumulate == 0: the accumulator is not read) or added to it with ONE IEEE add (accumulate == 1).
+ *   - Every archive check of dgpu_ans_decode_batch_pointer_bounded applies, with accWords[i] (float32 words, one per
+ *     decoded byte) as the capacity; outSuccess_dev[i] and outSize_dev[i] behave as there.  A member that fails (a
+ *     malformed or truncated archive, one that states more bytes than accWords[i]) leaves its accumulator untouched and
+ *     does not disturb the others.  Nothing outside [acc[i], acc[i] + size) is written.
+ *   - in[i] 16-byte aligned, acc[i] 4-byte aligned, accWords[i] <= 0xfffff000, and the argument checks above.  One kernel
+ *     geometry per call, as dgpu_ans_delta_decode.
+ *
+ * Neither call has temp-memory parameters: temporaries come from the stream's library-owned slab
+ * (dgpu_release_stream_state).  Both are asynchronous and capturable into a HIP graph under the conditions of their
+ * siblings.  A saturating conversion is not offered. */
+int dgpu_fp8_cast_compress(
+    uint32_t fp8Type, int probBits, uint32_t numInBatch, const void* const* in, const uint32_t* inSize /* float32 words */,
+    float scale, const float* scale_dev, uint32_t scalePerMember, void* const* out, uint32_t* outSize_dev, void* stream);
+int dgpu_fp8_decode_accumulate(
+    uint32_t fp8Type, int probBits, int accumulate, uint32_t numInBatch, const void* const* in, const uint32_t* inBytes,
+    float scale, const float* scale_dev, uint32_t scalePerMember, void* const* acc, const uint32_t* accWords,
+    uint8_t* outSuccess_dev, uint32_t* outSize_dev, void* stream);
 
 /* ---- rolling-table compress (no upstream equivalent) ------------------------------------
  * (Named like its siblings dgpu_float_cast_compress and dgpu_float_reduce_compress: the call is a compress with a
